@@ -2,16 +2,24 @@
 """bench.py -- condition + predict on the BASELINE workload (c3: 2-D Poisson-Dirichlet,
 N = 16 384 collocation + 4 x 128 boundary observations, M = 64 x 64 prediction points).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over the synthetic workload: block-by-block
 conditioning (Gram/cross-block assembly, blocked Cholesky with block append, representer
 weights) + prediction (cross-covariance assembly, posterior mean, marginal variance).
 Point sets are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
-Order of a run at N = 1: the CPU baseline (the oracle on the bench workload itself, ~30 s of host time) FIRST, then
-the GPU section in one piece (warm-up, timed region, per-phase stamps, per-kernel HIP-event passes), so that the
-device is busy in one contiguous stretch.
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, and the line (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step).  `--dump-outputs DIR`
+writes the posterior mean and marginal variance of the last timed step as DIR/mean.npy and DIR/var.npy (float64; the
+workloads are seeded, so the same arguments give the same inputs on every run).
+
+`--full` adds everything else the line has carried: the CPU baseline and its parity, the per-phase stamps, the other
+schedules and the reference's call sequence, the per-kernel HIP-event passes and rooflines, and at N > 1 the link probe,
+the oracle parity of the timed workload and the BASELINE configuration for that GPU count.  Order of a --full run at
+N = 1: the CPU baseline (the oracle on the bench workload itself, ~30 s of host time) FIRST, then the GPU section in
+one piece (warm-up, timed region, per-phase stamps, per-kernel HIP-event passes), so that the device is busy in one
+contiguous stretch.
 
 N > 1 (launched by `python -m torch.distributed.run`, env RANK/LOCAL_RANK/WORLD_SIZE/
 MASTER_ADDR/MASTER_PORT): one process per GPU, all ranks factor ONE problem whose Gram matrix is
@@ -24,8 +32,8 @@ builder never had more than one GPU: `config.link_probe` (measured GB/s of every
 rank sending to all, of all to all, through the transport the panels use) and `config.trials` (the same
 workload for two steps each on the P x 1 grid with the split panel gather, on the P/2 x 2 grid, and on
 P x 1 with one ncclBroadcast per panel piece instead of the point-to-point group; the fastest variant runs
-the timed region; LPGP_GRID / LPGP_DIST_COLLECTIVE pin a variant and skip the trials).  After the timed
-region the run also factors the BASELINE configuration named for that GPU count -- c4 (256 x 256, N_tot =
+the timed region; LPGP_GRID / LPGP_DIST_COLLECTIVE pin a variant and skip the trials; the link probe runs with --full only).  After the timed
+region a --full run also factors the BASELINE configuration named for that GPU count -- c4 (256 x 256, N_tot =
 66 560) at 8 GPUs, c5 (heat, N_tot = 33 600) at 4 and 2 -- reported under `configs` with size-independent
 parity properties (LPGP_BENCH_EXTRA=c4,c5 / none overrides the choice).
 LPGP_BENCH_STRONG=1 shards c3 itself ("strong"); LPGP_BENCH_REPLICAS=1 runs one independent c3 per rank.
@@ -144,6 +152,21 @@ def parity_by_properties(problems, wl, u, mean, var):
         ok = ok and abs(out["mean_max"] - 0.5894) < 1e-2
     out["pass"] = bool(ok)
     return out
+
+
+DUMP_LIMIT_BYTES = 60 * 10**6       # what --dump-outputs writes in all, headers aside (the limit is 64 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: each array as DIR/<name>.npy in float64, flattened.  If they would exceed DUMP_LIMIT_BYTES together, every
+    array is cut to the same fixed, seeded sample of its entries (sorted indices from a generator seeded with 0)."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for k, v in arrays.items()}
+    cap = DUMP_LIMIT_BYTES // (8 * max(len(flat), 1))
+    for name, a in flat.items():
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def _weak_sides(world):
@@ -334,14 +357,21 @@ def main():
                          "problem at its own sizes (tests/linpde_gp/problems/test_heat.py:56-99, N_tot = 2 105, 50 x 50 test grid), "
                          "scattered2d = 16 384 noisy values at scattered points (not a BASELINE config: every block through the "
                          "per-entry assembly kernels, none through the Kronecker path)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--check", action="store_true", help="also compare with the CPU oracle at full size")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baseline, phases, other schedules, per-kernel passes, rooflines, "
+                         "link probe / oracle parity / BASELINE extras at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the posterior mean and variance of the last timed step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
     global T_START
     T_START = time.time()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a plain `python bench.py --gpus N`: this process becomes the launcher (no GPU call, no engine import) and exits
         # with the job's status; the N ranks are fresh children that re-enter main() with WORLD_SIZE set
@@ -383,7 +413,7 @@ def main():
 
     # ---- CPU baseline FIRST (N = 1 only): the host cores are idle, and the GPU section afterwards is one busy stretch ----
     cpu_json, ref = None, None
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         cpu_json, ref = cpu_baseline(problems, make_workload(args.n_side, args.m_side), args.cpu_side)
     elif world == 1 and args.check:
         from oracle import workloads as owl
@@ -479,7 +509,7 @@ def main():
     def budget_left():
         return comm.allreduce_max(-(budget_s - (time.time() - t_cal0))) * -1.0      # the MIN over ranks of what is left
 
-    if distributed and transport != "host":
+    if distributed and transport != "host" and args.full:
         try:
             link_probe = ctx.link_probe(32 << 20, 3)
         except Exception as exc:                # noqa: BLE001
@@ -533,6 +563,85 @@ def main():
     # ---- timed region: exactly K steps, no instrumentation ----
     dt, last = timed_steps(wl, prior, dev, args.steps)
     _, mean, var = last
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"mean": mean, "var": var})
+    mode_name = "two_pipelines" if (distributed or not bench_lazy) else "fused_factor_and_predict"
+
+    def headline():
+        """The fields of every line: what was timed, and how fast."""
+        flops_ = wl.total_flops()
+        line = {
+            "metric": "condition+predict fp64 GFLOP/s (algorithmic), N=16384 Poisson-2D",
+            # distributed: all ranks work on ONE problem; replicas: one problem per rank
+            "value": (world if replicas else 1) * flops_ / (dt / args.steps) / 1e9,
+            "unit": "GFLOP/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            # the N = 1, 2, 4, 8 series of the default mode grows the problem with N (flops per GPU fixed): weak scaling, and the
+            # N = 1 line is the first point of that series; "strong" only for LPGP_BENCH_STRONG=1 / an explicit --n-side
+            "scaling": "strong" if (strong or (distributed and not weak)) else "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": wl.name,
+                "n_collocation": int(wl.observations[-1].X.shape[0]) if args.workload in ("poisson1d", "poisson1d_c1") else
+                                 int(max(o.X.shape[0] for o in wl.observations)),
+                "n_other_observations": int(wl.n_total - max(o.X.shape[0] for o in wl.observations)),
+                "n_total": wl.n_total,
+                "m_predict": int(wl.Xtest.shape[0]),
+                "noise_var_per_block": [None if o.noise_var is None else float(o.noise_var) for o in wl.observations],
+                "algorithmic_flops_per_step": flops_,
+                "multi_gpu": ((dist_note or "single GPU") if world == 1 else
+                              (dist_note or "independent replicas (one problem per GPU)") if replicas else
+                              (dist_note or "") +
+                              f"one problem, Gram matrix / factor sharded in 2-D block-cyclic tiles (blocks of 512) over a "
+                              f"{ctx.grid[0]} x {ctx.grid[1]} process grid, "
+                              + {"host": "HOST-STAGED panel exchange (bring-up transport, not a benchmark configuration)",
+                                 "ipc": "panel gather by direct-peer pushes into IPC-mapped windows (device-to-device copies, barriers over the control plane)",
+                                 "rccl": "panel gather by grouped RCCL point-to-point sends"
+                                         + (" -- OVER LOOPBACK SOCKETS between ranks that share one GPU (LPGP_BENCH_RCCL_LOOPBACK=1: "
+                                            "bring-up aid, not a benchmark configuration)" if loopback else "")}[transport]
+                              + ", prediction points sharded over the ranks, factor streamed for the solves"
+                              + (f"; weak scaling: grid side {n_side} so that flops per GPU equal c3's" if weak else "")),
+                "rccl_ranks": world if (distributed and transport == "rccl") else 0,
+                "transport": None if not distributed else transport,
+                "process_grid": None if not distributed else list(ctx.grid),
+                "link_probe": link_probe,
+                "trials": None if trials is None else {"variants": trials, "chosen": chosen, "skipped": skipped_trials,
+                                                       "calibration_seconds": calibration_s, "budget_seconds": budget_s,
+                                                       "note": "two timed steps of the bench workload per variant, during warm-up; the fastest runs the timed region; "
+                                                               "link probe and trials share LPGP_BENCH_BUDGET_S"},
+                "device": info["name"].strip(),
+                "csrc_sha16": csrc_sha16(),
+                "lazy_factorization": bool(lp.config.lazy_factorization) and not distributed,
+                "fused_factor_and_predict": bool(lp.config.lazy_factorization) and not distributed,
+                "calibration_seconds": calibration_s,
+            },
+            "mode": mode_name,
+            "posterior": {"mean_max": float(np.max(mean)), "var_min": float(np.min(var)), "var_max": float(np.max(var))},
+        }
+        if args.workload != "poisson2d" or wl.n_total != 16896:
+            line["metric"] = f"condition+predict fp64 GFLOP/s (algorithmic), {wl.name} (N_tot={wl.n_total})"
+        if mode_name == "two_pipelines":         # the timed region IS the two-pipeline schedule: its step time, at no cost
+            line["two_pipeline_ms_per_step"] = line["ms_per_step"]
+            line["two_pipeline_value"] = line["value"]
+        if ref is not None:                       # (--check)
+            line["parity"] = parity_report(mean, var, ref, wl)
+        assert line["n_gpus"] == args.gpus, (line["n_gpus"], args.gpus)
+        return line
+
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            _libc.fflush(None)
+            sys.stdout.flush()
+            print(json.dumps(headline()), flush=True)
+        comm.close()
+        return
     # ---- the two phases of a step (un-instrumented steps; the conditioning phase ends with the read-back of the
     #      factorisation status, so a host stamp between the phases costs nothing): max over ranks ----
     ph = []
@@ -547,7 +656,6 @@ def main():
     # always run the two pipelines (the ranks agree on the factorisation's status inside the conditioning; lpgp_potrf_predict is
     # single-GPU), so a scaling curve must be read against `two_pipeline_ms_per_step` of the N = 1 line, not against its fused
     # `ms_per_step`.
-    mode_name = "two_pipelines" if (distributed or not bench_lazy) else "fused_factor_and_predict"
     two_pipeline_ms = dt / args.steps * 1e3 if mode_name == "two_pipelines" else None
     tp_syrk = None
     # (LPGP_BENCH_NO_MODES -- set by the profile collections only, scratch/collect_profiles.sh: the profiled process must contain ONE
@@ -784,66 +892,17 @@ def main():
             run_extras()
         comm.close()
         return
-    ms_per_step = dt / args.steps * 1e3
     flops = wl.total_flops()
-    # distributed: all ranks work on ONE problem; replicas: one problem per rank
-    value = (world if replicas else 1) * flops / (dt / args.steps) / 1e9
-
     sha = csrc_sha16()
     syrk = prof[ROOFLINE_SLOT]
     asm = prof["assemble"]
     achieved = syrk["flops"] / (syrk["ms"] * 1e-3) / 1e12 if syrk["ms"] > 0 else 0.0
     roof_symbol = ctx.roofline_kernel_symbol() if hasattr(ctx, "roofline_kernel_symbol") else "gemm_f64_kernel<false, false, 1>"
-    out = {
-        "metric": "condition+predict fp64 GFLOP/s (algorithmic), N=16384 Poisson-2D",
-        "value": value,
-        "unit": "GFLOP/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        # the N = 1, 2, 4, 8 series of the default mode grows the problem with N (flops per GPU fixed): weak scaling, and the
-        # N = 1 line is the first point of that series; "strong" only for LPGP_BENCH_STRONG=1 / an explicit --n-side
-        "scaling": "strong" if (strong or (distributed and not weak)) else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": wl.name,
-            "n_collocation": int(wl.observations[-1].X.shape[0]) if args.workload in ("poisson1d", "poisson1d_c1") else
-                             int(max(o.X.shape[0] for o in wl.observations)),
-            "n_other_observations": int(wl.n_total - max(o.X.shape[0] for o in wl.observations)),
-            "n_total": wl.n_total,
-            "m_predict": int(wl.Xtest.shape[0]),
-            "noise_var_per_block": [None if o.noise_var is None else float(o.noise_var) for o in wl.observations],
-            "algorithmic_flops_per_step": flops,
-            "multi_gpu": ((dist_note or "single GPU") if world == 1 else
-                          (dist_note or "independent replicas (one problem per GPU)") if replicas else
-                          (dist_note or "") +
-                          f"one problem, Gram matrix / factor sharded in 2-D block-cyclic tiles (blocks of 512) over a "
-                          f"{ctx.grid[0]} x {ctx.grid[1]} process grid, "
-                          + {"host": "HOST-STAGED panel exchange (bring-up transport, not a benchmark configuration)",
-                             "ipc": "panel gather by direct-peer pushes into IPC-mapped windows (device-to-device copies, barriers over the control plane)",
-                             "rccl": "panel gather by grouped RCCL point-to-point sends"
-                                     + (" -- OVER LOOPBACK SOCKETS between ranks that share one GPU (LPGP_BENCH_RCCL_LOOPBACK=1: "
-                                        "bring-up aid, not a benchmark configuration)" if loopback else "")}[transport]
-                          + ", prediction points sharded over the ranks, factor streamed for the solves"
-                          + (f"; weak scaling: grid side {n_side} so that flops per GPU equal c3's" if weak else "")),
-            "rccl_ranks": world if (distributed and transport == "rccl") else 0,
-            "transport": None if not distributed else transport,
-            "process_grid": None if not distributed else list(ctx.grid),
-            "link_probe": link_probe,
-            "trials": None if trials is None else {"variants": trials, "chosen": chosen, "skipped": skipped_trials,
-                                                   "calibration_seconds": calibration_s, "budget_seconds": budget_s,
-                                                   "note": "two timed steps of the bench workload per variant, during warm-up; the fastest runs the timed region; "
-                                                           "link probe and trials share LPGP_BENCH_BUDGET_S"},
-            "comm_per_rank_per_step": None if not distributed else [
-                {"rank": r, "bytes_sent": row[0], "bytes_received": row[1], "seconds_in_comm": row[2] * 1e-3}
-                for r, row in enumerate(comm_rows)],
-            "device": info["name"].strip(),
-            "csrc_sha16": sha,
-        },
+    out = headline()
+    out["config"]["comm_per_rank_per_step"] = None if not distributed else [
+        {"rank": r, "bytes_sent": row[0], "bytes_received": row[1], "seconds_in_comm": row[2] * 1e-3}
+        for r, row in enumerate(comm_rows)]
+    out.update({
         "roofline": {
             "kernel": f"{roof_symbol} (SYRK: rank-512 trailing update of the blocked Cholesky, remainder half of the look-ahead split, ~90 % of the factorisation flops)",
             "bound": "mfma",
@@ -874,9 +933,7 @@ def main():
                              "(cross-covariance, streamed solve, read-outs) of two extra steps with a device synchronisation between the phases "
                              "(an un-instrumented step has none: the factorisation is enqueued and the prediction follows it on the device, so "
                              "the two phases add up to more than ms_per_step); best of two, max over ranks"},
-        "posterior": {"mean_max": float(np.max(mean)), "var_min": float(np.min(var)), "var_max": float(np.max(var))},
-    }
-    out["mode"] = mode_name
+    })
     out["two_pipeline_ms_per_step"] = two_pipeline_ms
     out["two_pipeline_value"] = None if two_pipeline_ms is None else (world if replicas else 1) * flops / (two_pipeline_ms * 1e-3) / 1e9
     if tp_syrk is not None and tp_syrk["ms"] > 0:
@@ -884,8 +941,6 @@ def main():
         out["roofline"]["two_pipeline_mode"] = {
             "achieved": ach_tp, "frac": ach_tp / FP64_MFMA_PEAK_TFLOPS, "launches_per_step": tp_syrk["launches"],
             "note": "the same kernel in the two-pipeline schedule (package default; every N > 1 line): beside the panel chain only, not beside the riding substitution's updates"}
-    out["config"]["lazy_factorization"] = bool(lp.config.lazy_factorization) and not distributed
-    out["config"]["fused_factor_and_predict"] = bool(lp.config.lazy_factorization) and not distributed
     if modes is not None:
         out["modes"] = modes
         out["reference_sequence"] = ref_seq
@@ -908,12 +963,8 @@ def main():
                 "launches_per_step": p["launches"] / args.steps,
             }
     del asm
-    if args.workload != "poisson2d" or wl.n_total != 16896:
-        out["metric"] = f"condition+predict fp64 GFLOP/s (algorithmic), {wl.name} (N_tot={wl.n_total})"
     if cpu_json is not None:
         out["cpu_baseline"] = cpu_json
-    if ref is not None:
-        out["parity"] = parity_report(mean, var, ref, wl)
     if oracle_thread is not None:
         # the timed workload of this multi-GPU run against the oracle (rank 0's host cores, beside the extras)
         oracle_thread.join(max(30.0, deadline_s - (time.time() - T_START)) if (extra_names and not extras_first) else None)
@@ -922,8 +973,6 @@ def main():
             out["parity"]["oracle"] = "oracle.workloads.run_in_place on rank 0's host cores, in this run"
         else:
             out["parity"] = {"skipped": oracle_box.get("skipped", "the oracle had not finished when the line was due")}
-    out["config"]["calibration_seconds"] = calibration_s
-    assert out["n_gpus"] == args.gpus, (out["n_gpus"], args.gpus)
     _libc.fflush(None)
     sys.stdout.flush()
     print(json.dumps(out), flush=True)

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for b in 4 8 16 32; do
   echo -n "band=$b : "
-  LPGP_GEMM_BAND=$b python3 bench.py --steps 5 --warmup 2 --no-cpu 2>/dev/null | tail -n 1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms', round(d['ms_per_step'],2), 'syrk TF/s', round(d['roofline']['achieved'],2), 'solve gemm TF/s', round(d['kernels']['gemm']['tflops'],2))"
+  LPGP_GEMM_BAND=$b python3 bench.py --full --steps 5 --warmup 2 --no-cpu 2>/dev/null | tail -n 1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms', round(d['ms_per_step'],2), 'syrk TF/s', round(d['roofline']['achieved'],2), 'solve gemm TF/s', round(d['kernels']['gemm']['tflops'],2))"
 done
 for b in 4 8 16; do
   for c in FETCH_SIZE WRITE_SIZE; do

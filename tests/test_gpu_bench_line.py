@@ -1,10 +1,12 @@
 """The driver-facing contract of `bench.py`, end to end on the GPU: one process, the c2 workload (small enough for the CPU
-baseline to take seconds), the single JSON line on stdout with every field the round's measurement rules name."""
+baseline to take seconds), the single JSON line on stdout with every field the round's measurement rules name -- the lean
+headline of a plain run, and everything else behind `--full`."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_contract_line():
     env = dict(os.environ, OPENBLAS_NUM_THREADS=os.environ.get("OPENBLAS_NUM_THREADS", "16"))
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "poisson1d"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--workload", "poisson1d"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -60,6 +62,32 @@ def test_bench_prints_one_contract_line():
     assert seq["default_mode_ms"] <= 1.25 * line["two_pipeline_ms_per_step"], (seq, line["two_pipeline_ms_per_step"])
 
 
+def test_plain_run_prints_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without `--full` the run sets up, warms up, times its steps and prints the headline -- no CPU baseline, no per-kernel
+    passes -- and `--dump-outputs DIR` writes what the last timed step returned (posterior mean and variance, float64)."""
+    out_dir = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                          "--workload", "poisson1d", "--dump-outputs", str(out_dir)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.lstrip().startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in line, key
+    assert line["n_gpus"] == 1 and line["steps"] == 4 and line["warmup"] == 1
+    assert line["unit"] == "GFLOP/s" and line["dtype"] == "f64" and line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert abs(line["value"] * 1e9 * line["ms_per_step"] * 1e-3 / line["config"]["algorithmic_flops_per_step"] - 1.0) < 1e-6
+    for key in ("cpu_baseline", "roofline", "kernels", "modes", "phase_ms", "parity"):
+        assert key not in line, key
+    mean, var = np.load(out_dir / "mean.npy"), np.load(out_dir / "var.npy")
+    assert sorted(os.listdir(out_dir)) == ["mean.npy", "var.npy"]
+    assert mean.dtype == np.float64 and var.dtype == np.float64
+    assert mean.shape == var.shape == (line["config"]["m_predict"],)
+    assert np.all(np.isfinite(mean)) and np.all(np.isfinite(var))
+    assert float(np.max(mean)) == line["posterior"]["mean_max"] and float(np.max(var)) == line["posterior"]["var_max"]
+
+
 def test_plain_call_with_gpus_2_starts_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher around it (the way the driver calls N = 1, the way the reference is
     called: one process, `_conditional.py:253-294`): the process starts its two ranks itself, before any GPU call, and
@@ -68,7 +96,7 @@ def test_plain_call_with_gpus_2_starts_its_own_ranks():
     env = dict(os.environ, LPGP_DEVICE="0", LPGP_BENCH_RCCL_LOOPBACK="1", OPENBLAS_NUM_THREADS="8")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--n-side", "48", "--m-side", "16"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
