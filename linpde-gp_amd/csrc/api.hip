@@ -612,6 +612,13 @@ int lpgp_get_option(lpgp_ctx* ctx, const char* key, int64_t* value) {
   else if (std::strcmp(key, "ride_outer_min_tiles") == 0) *value = ctx->ride_outer_min_tiles;
   else if (std::strcmp(key, "ride_max_tiles") == 0) *value = ctx->ride_max_tiles;
   else if (std::strcmp(key, "ride_same_stream_max_tiles") == 0) *value = ctx->ride_same_stream_max_tiles;
+  else if (std::strcmp(key, "dense_tiles") == 0) *value = ctx->dense_tiles;
+  else if (std::strcmp(key, "min_supertiles") == 0) *value = ctx->min_supertiles;
+  else if (std::strcmp(key, "small_ring2") == 0) *value = ctx->small_ring2;
+  else if (std::strcmp(key, "nb_outer") == 0) *value = ctx->nb_outer;
+  else if (std::strcmp(key, "nb_outer_min_tiles") == 0) *value = ctx->nb_outer_min_tiles;
+  else if (std::strcmp(key, "nb_big") == 0) *value = ctx->nb_big;
+  else if (std::strcmp(key, "nb_big_min_tiles") == 0) *value = ctx->nb_big_min_tiles;
   else LPGP_CHECK(false, "unknown option %s", key);
   return 0;
 }

@@ -887,10 +887,27 @@ int64_t gemm_valid_tiles(const GemmArgs& g) {
   return n;
 }
 
+// alpha == 0: C <- beta C on the tiles a launch would write (beta == 0: zeros, whatever C held), A and B not read -- the
+// kernels start their accumulators from (beta / alpha) C and cannot take this case
+__global__ __launch_bounds__(256) void gemm_scale_kernel(double* __restrict__ C, int64_t ldc, int tri, double beta) {
+  const int tr = blockIdx.x, tc = blockIdx.y;
+  if (tri && tr < tc) return;
+  // thread: one row of the tile, one half of its columns
+  double* p = C + ((int64_t)tc * TILE + (threadIdx.x / TILE) * (TILE / 2)) * ldc + (int64_t)tr * TILE + threadIdx.x % TILE;
+  for (int j = 0; j < TILE / 2; ++j, p += ldc) *p = beta == 0.0 ? 0.0 : beta * *p;
+}
+
 int launch_gemm(lpgp_ctx* ctx, hipStream_t stream, int ta, int tb, const GemmArgs& g, int prof_kernel) {
   if (g.mt <= 0 || g.nt <= 0 || g.k <= 0) return 0;
   LPGP_CHECK(g.k % BK == 0, "gemm: k=%d not a multiple of %d", g.k, BK);
   LPGP_CHECK(!g.tri || (!ta && !tb), "gemm: the triangular update exists for the NT form only");
+  if (g.alpha == 0.0) {
+    LPGP_CHECK(!g.cyc, "gemm: alpha = 0 in a distributed update");
+    if (g.beta == 1.0) return 0;
+    hipLaunchKernelGGL(gemm_scale_kernel, dim3((unsigned)g.mt, (unsigned)g.nt), dim3(256), 0, stream, g.C, g.ldc, g.tri, g.beta);
+    LPGP_HIP(hipGetLastError());
+    return 0;
+  }
   // launches with fewer 128 x 128 tiles than CUs go to the 64 x 64-tile kernel (4x the workgroups)
   // (not for in-place products X <- X * B: with 64-column tiles another workgroup would still be
   //  reading the columns of X this one overwrites)

@@ -60,12 +60,20 @@ def probe_hbm_write(ctx: Context, nbytes: int = 1 << 30) -> float:
 
 
 def test_gemm(ctx: Context, ta: int, tb: int, lower_only: int, alpha: float, A: np.ndarray, B: np.ndarray,
-              beta: float, Cm: np.ndarray, k: int, reps: int = 0):
-    """Raw GEMM on column-major (Fortran-ordered) arrays; returns (C, ms_per_rep)."""
+              beta: float, Cm: np.ndarray, k: int, reps: int = 0, m: int | None = None, n: int | None = None):
+    """Raw GEMM on column-major (Fortran-ordered) arrays; returns (C, ms_per_rep).  The leading dimensions are the arrays' row
+    counts; `m`, `n` (default: the shape of `Cm`) may be smaller than them, so a logical operand can sit inside a larger buffer."""
     A = np.asfortranarray(A, dtype=np.double)
     B = np.asfortranarray(B, dtype=np.double)
     Cm = np.asfortranarray(Cm, dtype=np.double).copy(order="F")
-    m, n = Cm.shape
+    m = Cm.shape[0] if m is None else int(m)
+    n = Cm.shape[1] if n is None else int(n)
+    # the hook uploads ld * (columns) elements of each buffer: they must exist
+    a_cols, b_cols = (m if ta else k), (n if tb else k)
+    if A.shape[1] < a_cols or B.shape[1] < b_cols or Cm.shape[1] < n or Cm.shape[0] < m:
+        raise ValueError("test_gemm: a buffer is smaller than its logical operand")
+    if A.shape[0] < (k if ta else m) or B.shape[0] < (k if tb else n):
+        raise ValueError("test_gemm: a leading dimension is smaller than the logical rows")
     ms = C.c_double(0.0)
     pd = C.POINTER(C.c_double)
     check(lib.lpgp_test_gemm(ctx._h, ta, tb, lower_only, m, n, k, alpha,
