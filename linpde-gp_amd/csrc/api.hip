@@ -619,6 +619,16 @@ int lpgp_get_option(lpgp_ctx* ctx, const char* key, int64_t* value) {
   else if (std::strcmp(key, "nb_outer_min_tiles") == 0) *value = ctx->nb_outer_min_tiles;
   else if (std::strcmp(key, "nb_big") == 0) *value = ctx->nb_big;
   else if (std::strcmp(key, "nb_big_min_tiles") == 0) *value = ctx->nb_big_min_tiles;
+  else if (std::strcmp(key, "route_ride_done") == 0) *value = ctx->route.ride_done;
+  else if (std::strcmp(key, "route_ride_aug") == 0) *value = ctx->route.ride_aug;
+  else if (std::strcmp(key, "route_ride_b2b") == 0) *value = ctx->route.ride_b2b;
+  else if (std::strcmp(key, "route_ride") == 0) *value = ctx->route.ride;
+  else if (std::strcmp(key, "route_ride_vchain") == 0) *value = ctx->route.ride_vchain;
+  else if (std::strcmp(key, "route_ride_two") == 0) *value = ctx->route.ride_two;
+  else if (std::strcmp(key, "route_ride_outer") == 0) *value = ctx->route.ride_outer;
+  else if (std::strcmp(key, "route_solve_two_level") == 0) *value = ctx->route.solve_two_level;
+  else if (std::strcmp(key, "route_solve_ahead") == 0) *value = ctx->route.solve_ahead;
+  else if (std::strcmp(key, "route_solve_tiles") == 0) *value = ctx->route.solve_tiles;
   else LPGP_CHECK(false, "unknown option %s", key);
   return 0;
 }

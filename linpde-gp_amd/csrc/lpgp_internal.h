@@ -126,6 +126,20 @@ struct lpgp_ctx {
   int ride_outer_min_tiles = 64;       // ... from this many tile rows on
   int ride_max_tiles = 384;            // factors of at least this many tile rows: factorisation and substitution back to back instead (potrf.hip)
   int ride_gate_pct = -1;              // (-1: by size, potrf.hip)              // ... its steps are held back until at most this percentage of the tile rows is left to factor (>= 100: released at once)
+  // Route counters (read-only through lpgp_get_option, keys "route_*"): incremented on the host where a forward substitution
+  // picks its branch, for the tests that must prove which branch they ran (the profiling slots cannot tell these apart).
+  struct RouteCounts {
+    int64_t ride_done = 0;             // potrf_predict_blocked: nothing left to factor, the plain substitution
+    int64_t ride_aug = 0;              // ... the augmented form
+    int64_t ride_b2b = 0;              // ... factorisation and substitution back to back (ride_max_tiles)
+    int64_t ride = 0;                  // ... the substitution riding inside the factorisation
+    int64_t ride_vchain = 0;           // ride panel steps that followed the resident chain (panel_chain_v_kernel)
+    int64_t ride_two = 0;              // ride panel steps split into two halves on two streams
+    int64_t ride_outer = 0;            // ride outer blocks closed by their one outer update (two-level ride; once, not per half)
+    int64_t solve_two_level = 0;       // trsm_lower_blocked: the two-level form
+    int64_t solve_ahead = 0;           // ... fused look-ahead launches (panel_solve_kernel with the update in front)
+    int64_t solve_tiles = 0;           // ... panels solved tile by tile (not fused)
+  } route;
   hipEvent_t ev_panel[2] = {nullptr, nullptr};
   hipEvent_t ev_upd[2] = {nullptr, nullptr};
   int64_t nb = 512;                // panel width of the blocked Cholesky

@@ -154,6 +154,8 @@ static int ride_panel_now(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, R
   // they would only hold their CUs waiting.  (Under a profiler that SERIALISES kernels -- rocprofv3 --pmc -- a follower that is
   // picked before its chain kernel waits out its poll limit and the step fails with a negative status: LPGP_RIDE_VCHAIN=0 there.)
   if (vchain && rd->stream != ctx->s_main && ctx->ride_vchain_pre) LPGP_HIP(hipStreamWaitEvent(rd->stream, ctx->ev_chain_pre, 0));
+  if (vchain) ++ctx->route.ride_vchain;
+  if (two) ++ctx->route.ride_two;
   if (vchain)
     LPGP_TRY(launch_panel_chain_v(ctx, rd->stream, mat, p0, rd->v + (int64_t)p0 * tb, rd->ldv, (int64_t)rd->mtl * tb, ctx->d_info_cur));
   if (sync_first && (rd->stream != ctx->s_main || two)) {
@@ -209,6 +211,7 @@ static int ride_panel_now(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, R
       }
       if (outer_from >= 0 && outer_from < T) {
         // the outer block [outer_q0, q1) is solved: everything from its margin on in ONE update with K = its height
+        if (h == 0) ++ctx->route.ride_outer;
         GemmArgs g = mk(a + (int64_t)outer_from * tb + (int64_t)outer_q0 * tb * ld, ld, vh + (int64_t)outer_q0 * tb, rd->ldv,
                         vh + (int64_t)outer_from * tb, rd->ldv, T - outer_from, mtl, (q1 - outer_q0) * TILE, -1.0, 1.0, 0);
         g.occ3 = ctx->ride_occ3;
@@ -436,6 +439,7 @@ int potrf_predict_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t 
   if (rd.stream2 && rd.stream2 != ctx->s_main) LPGP_HIP(hipStreamWaitEvent(rd.stream2, ctx->ev_ride[2], 0));
   if (t_done >= T) {
     // nothing left to factor: the plain substitution
+    ++ctx->route.ride_done;
     return trsm_lower_blocked(ctx, mat, T, v, ldv, m_pad);
   }
   if (ctx->ride_aug && (T + rd.mtl) * (int64_t)TILE <= mat->cap && !ctx->single_stream) {
@@ -444,6 +448,7 @@ int potrf_predict_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t 
     // substitution's updates then are tiles of the factorisation's own trailing-update launches (ONE grid, no second claimant
     // of the chip) and its panel steps rows of the panel chain's tile solves.  K_Xx is transposed into the free rows below the
     // matrix's blocks and back: 2 x 8 N M bytes through HBM.
+    ++ctx->route.ride_aug;
     double* vt = mat->a + T * (int64_t)TILE;
     LPGP_TRY(transpose(ctx->s_main, vt, mat->cap, v, ldv, T * (int64_t)TILE, m_pad));
     LPGP_TRY(potrf_blocked_impl(ctx, mat, t_done, T, nullptr, nullptr, (int)T + rd.mtl));
@@ -454,9 +459,11 @@ int potrf_predict_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t 
     // columns of right-hand side) the factorisation's outer updates with K = 2 048 and the substitution's with K = 4 096 have
     // the chip to themselves for seconds and the chain-bound parts are a per-cent effect; riding inside costs 1.8 % there
     // (2 718 against 2 670 ms) where it gains 6 % at c3, 13 % at c2 and 3 % at c5.
+    ++ctx->route.ride_b2b;
     LPGP_TRY(potrf_blocked_impl(ctx, mat, t_done, T, nullptr, nullptr));
     return trsm_lower_blocked(ctx, mat, T, v, ldv, m_pad);
   }
+  ++ctx->route.ride;
   LPGP_TRY(potrf_blocked_impl(ctx, mat, t_done, T, nullptr, &rd));
   if (rd.stream != ctx->s_main) {
     LPGP_HIP(hipEventRecord(ctx->ev_ride[2], rd.stream));
@@ -721,8 +728,10 @@ int trsm_lower_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int
   const bool la = ctx->lookahead != 0 && mtl >= 8;       // worth it only for wide right-hand sides
   {
     const int NBt = (int)(ctx->nb_outer_solve / TILE), nbi = (int)(ctx->nb / TILE);
-    if (la && ctx->fused_solve && ctx->nb_solve == 0 && nbi <= 4 && NBt > nbi && NBt % nbi == 0 && T >= ctx->nb_outer_solve_min_tiles && T >= 2 * NBt)
+    if (la && ctx->fused_solve && ctx->nb_solve == 0 && nbi <= 4 && NBt > nbi && NBt % nbi == 0 && T >= ctx->nb_outer_solve_min_tiles && T >= 2 * NBt) {
+      ++ctx->route.solve_two_level;
       return trsm_lower_two_level(ctx, mat, T, v, ldv, mtl, nbi, NBt);
+    }
   }
   hipStream_t sP = ctx->s_main, sU = la ? ctx->s_upd_all : ctx->s_main;
   bool have_upd_event = false;
@@ -747,6 +756,7 @@ int trsm_lower_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int
                                  p1 - p0, mtl, LPGP_K_PANEL));
     else
     for (int jt = p0; jt < p1; ++jt) {
+      if (jt == p0) ++ctx->route.solve_tiles;
       double* Vj = v + (int64_t)jt * tb;
       LPGP_TRY(launch_trsv_tile(ctx, sP, Vj, ldv, mat->linv + (int64_t)jt * tb * tb, a + (int64_t)jt * tb * (ld + 1), ld, mtl,
                                 LPGP_K_TRSM));
@@ -776,6 +786,7 @@ int trsm_lower_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int
     if (ahead_ok && p1 - p0 == 4 && t_b_us >= (double)ctx->fused_ahead_min_us) {
       LPGP_HIP(hipEventRecord(evp, sP));                                                   // panel [p0, p1) is solved
       if (have_upd_event) LPGP_HIP(hipStreamWaitEvent(sP, ctx->ev_upd[(it + 1) & 1], 0));     // rows [p1, p2): last written by the previous remainder update
+      ++ctx->route.solve_ahead;
       LPGP_TRY(launch_trsv_panel_ahead(ctx, sP, v + (int64_t)p1 * tb, ldv, mat->linv + (int64_t)p1 * tb * tb, a + (int64_t)p1 * tb * (ld + 1),
                                        a + (int64_t)p1 * tb + (int64_t)p0 * tb * ld, ld, p2 - p1, mtl, LPGP_K_PANEL));
       solved = true;

@@ -17,12 +17,11 @@ import numpy as np
 import pytest
 import scipy.linalg
 
+from _backward import EPS, LD, Appender, backward_error, gram_points, restored
+from _backward import matern52 as _matern52, mv as _mv, scale as _scale
+
 pytestmark = pytest.mark.gpu
 
-EPS = np.finfo(np.float64).eps
-LD = np.longdouble
-PROBES = 8
-FULL_MAX = 512
 # Bars, set from the first MI355X run (the largest measured value in brackets).  The device factor's backward error is a few
 # times LAPACK's on the well-conditioned kinds (a), (c) [7.6 at n = 100, 6.0 at n = 8320] and below it on kind (b) [0.4]: at
 # most 0.2 n eps in all.  Its solves: [4.8 x cho_solve's normwise backward error].
@@ -44,27 +43,12 @@ def ctx():
 @pytest.fixture
 def sched(ctx):
     """sched(dict) applies a schedule row; every option of `OPTIONS` is restored afterwards, profiling switched off."""
-    saved = {k: ctx.get_option(k) for k in OPTIONS}
-
-    def apply(row):
-        for k, v in row.items():
-            ctx.set_option(k, v)
-    try:
+    with restored(ctx, OPTIONS) as apply:
         yield apply
-    finally:
-        ctx.profile_enable(False)
-        for k, v in saved.items():
-            ctx.set_option(k, v)
 
 
 # ---- matrices (module cache: the host references dominate the cost) ----------------------------------------------------
 _cache = {}
-
-
-def _matern52(n, rng):
-    X = rng.uniform(0, 1, (n, 2))
-    r = np.sqrt(5.0) * np.sqrt(np.sum((X[:, None, :] - X[None, :, :]) ** 2, axis=-1)) / 0.3
-    return (1 + r + r * r / 3) * np.exp(-r) + 1e-8 * np.eye(n)
 
 
 def matrix(kind, n):
@@ -82,47 +66,6 @@ def matrix(kind, n):
             A = d[:, None] * matrix("a", n) * d[None, :]
         _cache[key] = np.ascontiguousarray((A + A.T) / 2)        # exactly symmetric
     return _cache[key]
-
-
-def _scale(A):
-    return 1.0 / np.sqrt(np.diag(A))
-
-
-def _probes(n):
-    return np.random.default_rng(n).standard_normal((n, PROBES)).astype(LD)
-
-
-def _mv(M, X):
-    """M @ X in long double, in row slabs (n = 8320 would need 1 GB as one long-double array)."""
-    out = np.empty((M.shape[0], X.shape[1]), dtype=LD)
-    for i in range(0, M.shape[0], 1024):
-        out[i:i + 1024] = M[i:i + 1024].astype(LD) @ X
-    return out
-
-
-def _mtv(M, X):
-    """M^T @ X in long double."""
-    out = np.zeros((M.shape[1], X.shape[1]), dtype=LD)
-    for i in range(0, M.shape[0], 1024):
-        out += M[i:i + 1024].astype(LD).T @ X[i:i + 1024]
-    return out
-
-
-def backward_error(A, L):
-    """max |S (A - L L^T) S| (n <= FULL_MAX) or max |S (A - L L^T) S X| / max_j ||X_j||_2 on the probes X."""
-    n = A.shape[0]
-    s = _scale(A).astype(LD)
-    if n <= FULL_MAX:
-        Ls = L.astype(LD) * s[:, None]
-        R = A.astype(LD) * s[:, None] * s[None, :] - Ls @ Ls.T
-        return float(np.max(np.abs(R)))
-    X = _probes(n)
-    key = ("AX", id(A), n)
-    if key not in _cache:
-        _cache[key] = s[:, None] * _mv(A, s[:, None] * X)
-    AX = _cache[key]
-    R = AX - s[:, None] * _mv(L, _mtv(L, s[:, None] * X))
-    return float(np.max(np.abs(R)) / np.max(np.sqrt(np.sum(X * X, axis=0))))
 
 
 def lapack(A):
@@ -152,54 +95,6 @@ def factor(ctx, A):
     mat = new_matrix(ctx, A)
     assert mat.potrf() == 0
     return mat
-
-
-# appended block rows: a Matern-5/2 Gram on scattered 2-D points plus diagonal noise of three kinds
-NOISE = {"m": lambda rng, n: np.ones(n),                                  # well conditioned
-         "b": lambda rng, n: np.full(n, 1e-8),                            # condition ~1e9
-         "s": lambda rng, n: 10.0 ** rng.uniform(-6, 6, n)}               # rows scaled over twelve decades
-
-
-def gram_points(kind, n):
-    rng = np.random.default_rng(7 * n + ord(kind))
-    return rng.uniform(0, 1, (n, 2)), NOISE[kind](rng, n)
-
-
-class Appender:
-    """Appends block rows of the Gram of `X` plus diag(`noise`) to a GramMatrix as a conditioning does: all blocks of the new
-    row assembled on the device, then the noise (plus `extra`, a diagonal perturbation of the new block) added."""
-
-    def __init__(self, ctx, X, noise):
-        from linpde_gp_amd import _engine
-        from linpde_gp_amd.randprocs import covfuncs
-        self.ctx, self.X, self.noise = ctx, X, noise
-        self.kd = covfuncs.Matern((2,), nu=2.5, lengthscales=0.3).lower()
-        self.mat = _engine.GramMatrix(ctx, X.shape[0])
-        self.pts = []
-
-    def add(self, nb, extra=None):
-        from linpde_gp_amd import _engine
-        mat, lo = self.mat, self.mat.n
-        bi = mat.add_block(nb)
-        P = _engine.Points(self.ctx, np.ascontiguousarray(self.X[lo:lo + nb]))
-        self.pts.append(P)
-        for bj in range(bi):
-            mat.assemble(self.kd, P, self.pts[bj], bi, bj)
-        mat.assemble(self.kd, P, None, bi, bi)
-        v = self.noise[lo:lo + nb].copy()
-        if extra is not None:
-            v += extra
-        mat.add_diag(bi, v)
-        return bi
-
-    def drop(self, nblocks, truncate=False):
-        """Rollback to `nblocks` blocks (pop_block of the last, or truncate)."""
-        if truncate:
-            self.mat.truncate(nblocks)
-        else:
-            assert self.mat.num_blocks == nblocks + 1
-            self.mat.pop_block()
-        del self.pts[nblocks:]
 
 
 def appended_matrix(kind, n, blocks):
