@@ -81,8 +81,10 @@ const char* lpgp_last_error(void);
 /* name (<= len bytes), compute units, HBM bytes of the device behind ctx */
 int  lpgp_device_info(lpgp_ctx* ctx, char* name, int len, int* cus, int64_t* hbm_bytes);
 int  lpgp_sync(lpgp_ctx* ctx);                       /* hipDeviceSynchronize */
-/* tuning knobs (env LPGP_NB / LPGP_LOOKAHEAD give the defaults): panel width of the
- * blocked Cholesky (multiple of 128) and look-ahead on/off                              */
+/* tuning options of the context, one row each in the table of csrc/options.cpp: its key, its environment variable
+ * (read by lpgp_init), its default and the values it accepts.  get reads every row, and also the read-only state
+ * "live_mats" and "route_*" (route counters of the forward substitution); set refuses the rows read at init only
+ * (reserve_cus, reserve_narrow, single_stream).                                                                    */
 int  lpgp_set_option(lpgp_ctx* ctx, const char* key, int64_t value);
 int  lpgp_get_option(lpgp_ctx* ctx, const char* key, int64_t* value);
 

@@ -339,6 +339,7 @@ int lpgp_init(int device, lpgp_ctx** out) {
   LPGP_HIP(hipSetDevice(device));
   lpgp_ctx* ctx = new lpgp_ctx();
   ctx->device = device;
+  options_from_env(*ctx);
   hipDeviceProp_t prop;
   LPGP_HIP(hipGetDeviceProperties(&prop, device));
   ctx->cus = prop.multiProcessorCount;
@@ -347,16 +348,13 @@ int lpgp_init(int device, lpgp_ctx** out) {
   LPGP_HIP(hipStreamCreateWithPriority(&ctx->s_main, hipStreamNonBlocking, hi));
   // The trailing-update stream may use all CUs except a few reserved ones, so that the
   // panel kernels of the look-ahead (a 156-KB-LDS tile Cholesky needs a whole CU) never queue
-  // behind thousands of resident update workgroups.  LPGP_RESERVE_CUS=0 disables the mask.
+  // behind thousands of resident update workgroups.  reserve_cus = 0 (LPGP_RESERVE_CUS=0) disables the mask.
   // 32 = four CUs per XCD.  In steady state the mask costs the rank-512 update 10 % whether 1, 8 or 32 CUs are missing (65.1 ->
   // 58.8 / 58.5 TFLOP/s: the dispatcher feeds the shader engines evenly, so the first missing CU of an engine already sets
   // its pace; 64 missing cost 22 %; profiles/r03_clock_power.txt) -- so the chain may as well have the 32: c3 55.03-55.21 ms
   // against 55.18-55.64 with 8, c2 / c4 / c5 within their spread (MEASUREMENTS.md).
-  int reserve = 32;
-  if (const char* e = std::getenv("LPGP_RESERVE_CUS")) reserve = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RESERVE_CUS_NARROW")) ctx->reserve_narrow = std::atoi(e);
   // mask bit i = CU (i / 8) of XCD (i % 8) (measured, scratch/cumask.hip): clearing the low
-  // `reserve` bits takes the CUs round-robin from the XCDs, reserve / 8 per XCD,
+  // `reserve_cus` bits takes the CUs round-robin from the XCDs, reserve_cus / 8 per XCD,
   // so a single workgroup of the panel stream finds a free CU on whichever XCD it is dealt to
   auto masked_stream = [&](int nreserve, hipStream_t* out) {
     *out = nullptr;
@@ -370,15 +368,13 @@ int lpgp_init(int device, lpgp_ctx** out) {
       *out = nullptr;
     }
   };
-  // LPGP_SINGLE_STREAM=1: every stream of the context is the panel stream (no concurrency between chain and update).  For
+  // single_stream (LPGP_SINGLE_STREAM=1): every stream of the context is the panel stream (no concurrency between chain and update).  For
   // jobs whose ranks SHARE one GPU (tests: eight processes x six queues oversubscribe the device's hardware queues and a
   // small eight-rank case takes 300 s; with one queue per process it takes a fraction of that).  Never a production setting.
-  const bool single_stream = [] { const char* e = std::getenv("LPGP_SINGLE_STREAM"); return e && std::atoi(e) != 0; }();
-  if (single_stream) {
+  if (ctx->single_stream) {
     ctx->s_upd = ctx->s_upd_narrow = ctx->s_upd_all = ctx->s_outer = ctx->s_main;
-    ctx->single_stream = 1;
   } else {
-  masked_stream(reserve, &ctx->s_upd);
+  masked_stream(ctx->reserve_cus, &ctx->s_upd);
   if (!ctx->s_upd) LPGP_HIP(hipStreamCreateWithPriority(&ctx->s_upd, hipStreamNonBlocking, lo));
   // While the panel chain bounds the pipeline (small trailing matrix) the update can spare a
   // quarter of the chip: with only 8 reserved CUs the chain's TRSM / in-panel update wait for
@@ -388,14 +384,9 @@ int lpgp_init(int device, lpgp_ctx** out) {
   //  with 8 CUs removed (tile-count quantisation on 496 instead of 512 slots), 44.3 with 64
   //  removed; LPGP_TEST_GEMM_STREAM + scratch/gemm_sweep.py.  Only the factorisation needs it.)
   LPGP_HIP(hipStreamCreateWithPriority(&ctx->s_upd_all, hipStreamNonBlocking, lo));
-  masked_stream(reserve, &ctx->s_outer);
+  masked_stream(ctx->reserve_cus, &ctx->s_outer);
   if (!ctx->s_outer) LPGP_HIP(hipStreamCreateWithPriority(&ctx->s_outer, hipStreamNonBlocking, lo));
   }
-  if (const char* e = std::getenv("LPGP_NB_OUTER")) {
-    long v = std::atol(e);
-    if (v >= 0 && v % TILE == 0) ctx->nb_outer = v;
-  }
-  if (const char* e = std::getenv("LPGP_NB_OUTER_MIN_TILES")) ctx->nb_outer_min_tiles = std::atoi(e);
   for (int i = 0; i < 2; ++i) {
     LPGP_HIP(hipEventCreateWithFlags(&ctx->ev_outer[i], hipEventDisableTiming));
     LPGP_HIP(hipEventCreateWithFlags(&ctx->ev_outer_fact[i], hipEventDisableTiming));
@@ -406,29 +397,6 @@ int lpgp_init(int device, lpgp_ctx** out) {
   LPGP_HIP(hipEventCreateWithFlags(&ctx->ev_chain_rows, hipEventDisableTiming));
   LPGP_HIP(hipEventCreateWithFlags(&ctx->ev_append[0], hipEventDisableTiming));
   LPGP_HIP(hipEventCreateWithFlags(&ctx->ev_append[1], hipEventDisableTiming));
-  if (const char* e = std::getenv("LPGP_RIDE_STREAM")) ctx->ride_stream = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_CHAIN_RESIDENT")) ctx->chain_resident_max_rows = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_TRSV_RESIDENT")) ctx->trsv_resident = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_CHAIN_RESIDENT2")) ctx->chain_resident2_max_rows = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_CHAIN_AHEAD")) ctx->chain_ahead = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_CHAIN_AHEAD_MIN_ROWS")) ctx->chain_ahead_min_rows = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RIDE_OCC3")) ctx->ride_occ3 = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RIDE_AUG")) ctx->ride_aug = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RIDE_B_ON_RIDE")) ctx->ride_b_on_ride = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_APPEND_SPLIT")) ctx->append_split = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_APPEND_SPLIT_MIN_TILES")) ctx->append_split_min_tiles = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RIDE_OLD_UNGATED")) ctx->ride_old_ungated = std::atoi(e);
-  // A profiler that SERIALISES kernels (rocprofv3 --pmc / counter groups: ROCPROF_COUNTER_COLLECTION) breaks the one assumption of
-  // the follower -- that its chain kernel is dispatched beside it: it would wait out its poll limit, ~1 s per panel, and the step
-  // would fail with a negative status.  Off there unless asked for explicitly.
-  if (const char* e = std::getenv("ROCPROF_COUNTER_COLLECTION")) { if (e[0] != '\0' && e[0] != '0' && e[0] != 'F' && e[0] != 'f') ctx->ride_vchain_max_wgs = 0; }
-  if (const char* e = std::getenv("LPGP_RIDE_VCHAIN")) ctx->ride_vchain_max_wgs = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RIDE_VCHAIN_PRE")) ctx->ride_vchain_pre = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RIDE_GATE_PCT")) ctx->ride_gate_pct = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RIDE_OUTER_ROWS")) ctx->ride_outer_rows = std::atol(e);
-  if (const char* e = std::getenv("LPGP_RIDE_OUTER_MIN_TILES")) ctx->ride_outer_min_tiles = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RIDE_MAX_TILES")) ctx->ride_max_tiles = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_RIDE_SAME_STREAM_MAX_TILES")) ctx->ride_same_stream_max_tiles = std::atoi(e);
   for (int i = 0; i < 2; ++i) {
     LPGP_HIP(hipEventCreateWithFlags(&ctx->ev_panel[i], hipEventDisableTiming));
     LPGP_HIP(hipEventCreateWithFlags(&ctx->ev_upd[i], hipEventDisableTiming));
@@ -440,48 +408,6 @@ int lpgp_init(int device, lpgp_ctx** out) {
   }
   LPGP_HIP(hipMalloc(&ctx->d_info, sizeof(int)));
   LPGP_HIP(hipHostMalloc(&ctx->h_info_pinned, 64, hipHostMallocDefault));
-  if (const char* e = std::getenv("LPGP_NB")) {
-    long v = std::atol(e);
-    if (v >= TILE && v % TILE == 0) ctx->nb = v;
-  }
-  if (const char* e = std::getenv("LPGP_NB_OUTER_SOLVE")) {
-    long v = std::atol(e);
-    if (v >= 0 && v % TILE == 0) ctx->nb_outer_solve = v;
-  }
-  if (const char* e = std::getenv("LPGP_NB_OUTER_SOLVE_MIN_TILES")) ctx->nb_outer_solve_min_tiles = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_NB_SOLVE")) {
-    long v = std::atol(e);
-    if (v >= 0 && v % TILE == 0) ctx->nb_solve = v;
-  }
-  if (const char* e = std::getenv("LPGP_LOOKAHEAD")) ctx->lookahead = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LPGP_CHAIN_US_TILE")) ctx->chain_us_tile = std::atof(e);
-  if (const char* e = std::getenv("LPGP_SOLVE_CHAIN_US_TILE")) ctx->solve_chain_us_tile = std::atof(e);
-  if (const char* e = std::getenv("LPGP_CHAIN_US_FIXED")) ctx->chain_us_fixed = std::atof(e);
-  if (const char* e = std::getenv("LPGP_DENSE_TILES")) ctx->dense_tiles = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LPGP_FUSED_SOLVE")) ctx->fused_solve = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LPGP_GEMM3")) ctx->gemm3 = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_SMALL_RING2")) ctx->small_ring2 = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_SMALL_TILES_MAX")) ctx->small_tiles_max = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_FUSED_AHEAD")) ctx->fused_ahead = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_PANEL_EXCLUSIVE")) ctx->panel_exclusive = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_FUSED_AHEAD_MIN_US")) ctx->fused_ahead_min_us = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_GEMM3_MARGIN")) ctx->gemm3_margin = std::atof(e);
-  if (const char* e = std::getenv("LPGP_GEMM3_FACT")) ctx->gemm3_fact = std::atoi(e);
-  if (const char* e = std::getenv("LPGP_ASM_FACTORS")) ctx->asm_factors = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LPGP_ASM_FAST")) ctx->asm_fast = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LPGP_ASM_CT")) ctx->asm_ct = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("LPGP_ASM_BATCH")) ctx->asm_batch = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LPGP_KRON_WIDE")) ctx->kron_wide = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LPGP_DIST_COLLECTIVE")) ctx->dist_bcast = std::strcmp(e, "bcast") == 0;
-  if (const char* e = std::getenv("LPGP_DIST_SPLIT_GATHER")) ctx->split_gather = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LPGP_DIST_SCOPED_GATHER")) ctx->scoped_gather = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LPGP_DIST_CHAIN_US_COMM")) ctx->dist_chain_us_comm = std::atof(e);
-  if (const char* e = std::getenv("LPGP_GEMM_BAND")) { const int v = std::atoi(e); if (v == 2 || v == 4 || v == 8 || v == 16 || v == 32) ctx->gemm_band = v; }
-  if (const char* e = std::getenv("LPGP_NB_BIG")) {
-    long v = std::atol(e);
-    if (v >= 0 && v % TILE == 0) ctx->nb_big = v;
-  }
-  if (const char* e = std::getenv("LPGP_NB_BIG_MIN_TILES")) ctx->nb_big_min_tiles = std::atoi(e);
   *out = ctx;
   return 0;
 }
@@ -574,167 +500,32 @@ int lpgp_sync(lpgp_ctx* ctx) {
   return 0;
 }
 
+// read-only state beside the options: the matrices alive and the route counters (lpgp_ctx::RouteCounts)
+#define ROUTE(name) {"route_" #name, &lpgp_ctx::RouteCounts::name}
+static const struct { const char* key; int64_t lpgp_ctx::RouteCounts::*count; } kRoutes[] = {
+    ROUTE(ride_done), ROUTE(ride_aug), ROUTE(ride_b2b), ROUTE(ride), ROUTE(ride_vchain), ROUTE(ride_two), ROUTE(ride_outer),
+    ROUTE(solve_two_level), ROUTE(solve_ahead), ROUTE(solve_tiles)};
+#undef ROUTE
+
 int lpgp_get_option(lpgp_ctx* ctx, const char* key, int64_t* value) {
   LPGP_CHECK(ctx && key && value, "lpgp_get_option: null argument");
-  if (std::strcmp(key, "nb") == 0) *value = ctx->nb;
-  else if (std::strcmp(key, "gemm3") == 0) *value = ctx->gemm3;
-  else if (std::strcmp(key, "gemm3_fact") == 0) *value = ctx->gemm3_fact;
-  else if (std::strcmp(key, "dist_bcast") == 0) *value = ctx->dist_bcast;
-  else if (std::strcmp(key, "split_gather") == 0) *value = ctx->split_gather;
-  else if (std::strcmp(key, "scoped_gather") == 0) *value = ctx->scoped_gather;
-  else if (std::strcmp(key, "lookahead") == 0) *value = ctx->lookahead;
-  else if (std::strcmp(key, "fused_solve") == 0) *value = ctx->fused_solve;
-  else if (std::strcmp(key, "small_tiles_max") == 0) *value = ctx->small_tiles_max;
-  else if (std::strcmp(key, "live_mats") == 0) *value = ctx->live_mats;
-  else if (std::strcmp(key, "asm_ct") == 0) *value = ctx->asm_ct;
-  else if (std::strcmp(key, "asm_batch") == 0) *value = ctx->asm_batch;
-  else if (std::strcmp(key, "kron_wide") == 0) *value = ctx->kron_wide;
-  else if (std::strcmp(key, "asm_fast") == 0) *value = ctx->asm_fast;
-  else if (std::strcmp(key, "fused_ahead") == 0) *value = ctx->fused_ahead;
-  else if (std::strcmp(key, "fused_ahead_min_us") == 0) *value = ctx->fused_ahead_min_us;
-  else if (std::strcmp(key, "nb_outer_solve") == 0) *value = ctx->nb_outer_solve;
-  else if (std::strcmp(key, "nb_outer_solve_min_tiles") == 0) *value = ctx->nb_outer_solve_min_tiles;
-  else if (std::strcmp(key, "nb_solve") == 0) *value = ctx->nb_solve;
-  else if (std::strcmp(key, "solve_chain_us_tile") == 0) *value = (int64_t)ctx->solve_chain_us_tile;
-  else if (std::strcmp(key, "chain_us_fixed") == 0) *value = (int64_t)ctx->chain_us_fixed;
-  else if (std::strcmp(key, "ride_stream") == 0) *value = ctx->ride_stream;
-  else if (std::strcmp(key, "chain_resident_max_rows") == 0) *value = ctx->chain_resident_max_rows;
-  else if (std::strcmp(key, "trsv_resident") == 0) *value = ctx->trsv_resident;
-  else if (std::strcmp(key, "chain_resident2_max_rows") == 0) *value = ctx->chain_resident2_max_rows;
-  else if (std::strcmp(key, "chain_ahead") == 0) *value = ctx->chain_ahead;
-  else if (std::strcmp(key, "chain_ahead_min_rows") == 0) *value = ctx->chain_ahead_min_rows;
-  else if (std::strcmp(key, "ride_vchain_max_wgs") == 0) *value = ctx->ride_vchain_max_wgs;
-  else if (std::strcmp(key, "ride_occ3") == 0) *value = ctx->ride_occ3;
-  else if (std::strcmp(key, "ride_aug") == 0) *value = ctx->ride_aug;
-  else if (std::strcmp(key, "append_split") == 0) *value = ctx->append_split;
-  else if (std::strcmp(key, "ride_gate_pct") == 0) *value = ctx->ride_gate_pct;
-  else if (std::strcmp(key, "ride_outer_rows") == 0) *value = ctx->ride_outer_rows;
-  else if (std::strcmp(key, "ride_outer_min_tiles") == 0) *value = ctx->ride_outer_min_tiles;
-  else if (std::strcmp(key, "ride_max_tiles") == 0) *value = ctx->ride_max_tiles;
-  else if (std::strcmp(key, "ride_same_stream_max_tiles") == 0) *value = ctx->ride_same_stream_max_tiles;
-  else if (std::strcmp(key, "dense_tiles") == 0) *value = ctx->dense_tiles;
-  else if (std::strcmp(key, "min_supertiles") == 0) *value = ctx->min_supertiles;
-  else if (std::strcmp(key, "small_ring2") == 0) *value = ctx->small_ring2;
-  else if (std::strcmp(key, "nb_outer") == 0) *value = ctx->nb_outer;
-  else if (std::strcmp(key, "nb_outer_min_tiles") == 0) *value = ctx->nb_outer_min_tiles;
-  else if (std::strcmp(key, "nb_big") == 0) *value = ctx->nb_big;
-  else if (std::strcmp(key, "nb_big_min_tiles") == 0) *value = ctx->nb_big_min_tiles;
-  else if (std::strcmp(key, "route_ride_done") == 0) *value = ctx->route.ride_done;
-  else if (std::strcmp(key, "route_ride_aug") == 0) *value = ctx->route.ride_aug;
-  else if (std::strcmp(key, "route_ride_b2b") == 0) *value = ctx->route.ride_b2b;
-  else if (std::strcmp(key, "route_ride") == 0) *value = ctx->route.ride;
-  else if (std::strcmp(key, "route_ride_vchain") == 0) *value = ctx->route.ride_vchain;
-  else if (std::strcmp(key, "route_ride_two") == 0) *value = ctx->route.ride_two;
-  else if (std::strcmp(key, "route_ride_outer") == 0) *value = ctx->route.ride_outer;
-  else if (std::strcmp(key, "route_solve_two_level") == 0) *value = ctx->route.solve_two_level;
-  else if (std::strcmp(key, "route_solve_ahead") == 0) *value = ctx->route.solve_ahead;
-  else if (std::strcmp(key, "route_solve_tiles") == 0) *value = ctx->route.solve_tiles;
-  else LPGP_CHECK(false, "unknown option %s", key);
-  return 0;
+  const int rc = option_get(*ctx, key, value);
+  if (rc == 0) return 0;
+  if (std::strcmp(key, "live_mats") == 0) {
+    *value = ctx->live_mats;
+    return 0;
+  }
+  for (const auto& r : kRoutes)
+    if (std::strcmp(key, r.key) == 0) {
+      *value = ctx->route.*r.count;
+      return 0;
+    }
+  return rc;       // (unknown option <key>, set by option_get)
 }
 
 int lpgp_set_option(lpgp_ctx* ctx, const char* key, int64_t value) {
   LPGP_DEVICE(ctx);
-  if (std::strcmp(key, "nb") == 0) {
-    LPGP_CHECK(value >= TILE && value % TILE == 0, "nb must be a positive multiple of %d", TILE);
-    ctx->nb = value;
-  } else if (std::strcmp(key, "small_tiles_max") == 0) {
-    ctx->small_tiles_max = (int)value;
-  } else if (std::strcmp(key, "chain_us_tile") == 0) {
-    ctx->chain_us_tile = (double)value;
-  } else if (std::strcmp(key, "solve_chain_us_tile") == 0) {
-    ctx->solve_chain_us_tile = (double)value;
-  } else if (std::strcmp(key, "chain_us_fixed") == 0) {
-    ctx->chain_us_fixed = (double)value;
-  } else if (std::strcmp(key, "dense_tiles") == 0) {
-    ctx->dense_tiles = (int)value;
-  } else if (std::strcmp(key, "fused_solve") == 0) {
-    ctx->fused_solve = (int)value;
-  } else if (std::strcmp(key, "dist_bcast") == 0) {
-    ctx->dist_bcast = value != 0;           // (the same on every rank)
-  } else if (std::strcmp(key, "split_gather") == 0) {
-    ctx->split_gather = value != 0;
-  } else if (std::strcmp(key, "scoped_gather") == 0) {
-    ctx->scoped_gather = value != 0;          // (the same on every rank)
-  } else if (std::strcmp(key, "asm_factors") == 0) {
-    ctx->asm_factors = value != 0;
-  } else if (std::strcmp(key, "asm_fast") == 0) {
-    ctx->asm_fast = value != 0;
-  } else if (std::strcmp(key, "asm_batch") == 0) {
-    ctx->asm_batch = value != 0;
-  } else if (std::strcmp(key, "kron_wide") == 0) {
-    ctx->kron_wide = value != 0;
-  } else if (std::strcmp(key, "asm_ct") == 0) {
-    LPGP_CHECK(value >= 1 && value <= 64, "asm_ct must be in 1 .. 64");
-    ctx->asm_ct = (int)value;
-  } else if (std::strcmp(key, "gemm3_fact") == 0) {
-    ctx->gemm3_fact = value != 0;
-  } else if (std::strcmp(key, "gemm3") == 0) {
-    ctx->gemm3 = value < 0 ? lpgp_ctx().gemm3 : (int)value;       // (negative: back to the built-in default)
-  } else if (std::strcmp(key, "small_ring2") == 0) {
-    ctx->small_ring2 = (int)value;
-  } else if (std::strcmp(key, "fused_ahead") == 0) {
-    ctx->fused_ahead = (int)value;
-  } else if (std::strcmp(key, "fused_ahead_min_us") == 0) {
-    ctx->fused_ahead_min_us = (int)value;
-  } else if (std::strcmp(key, "min_supertiles") == 0) {
-    ctx->min_supertiles = (int)value;
-  } else if (std::strcmp(key, "nb_solve") == 0) {
-    LPGP_CHECK(value >= 0 && value % TILE == 0, "nb_solve must be a multiple of %d (0: nb)", TILE);
-    ctx->nb_solve = value;
-  } else if (std::strcmp(key, "nb_outer_solve") == 0) {
-    LPGP_CHECK(value >= 0 && value % TILE == 0, "nb_outer_solve must be a multiple of %d (0 disables)", TILE);
-    ctx->nb_outer_solve = value;
-  } else if (std::strcmp(key, "nb_outer_solve_min_tiles") == 0) {
-    LPGP_CHECK(value >= 0, "nb_outer_solve_min_tiles must be >= 0");
-    ctx->nb_outer_solve_min_tiles = (int)value;
-  } else if (std::strcmp(key, "nb_outer") == 0) {
-    LPGP_CHECK(value >= 0 && value % TILE == 0, "nb_outer must be a multiple of %d (0 disables)", TILE);
-    ctx->nb_outer = value;
-  } else if (std::strcmp(key, "nb_outer_min_tiles") == 0) {
-    ctx->nb_outer_min_tiles = (int)value;
-  } else if (std::strcmp(key, "nb_big") == 0) {
-    LPGP_CHECK(value >= 0 && value % TILE == 0, "nb_big must be a multiple of %d (0 disables)", TILE);
-    ctx->nb_big = value;
-  } else if (std::strcmp(key, "nb_big_min_tiles") == 0) {
-    ctx->nb_big_min_tiles = (int)value;
-  } else if (std::strcmp(key, "lookahead") == 0) {
-    ctx->lookahead = value != 0;
-  } else if (std::strcmp(key, "ride_stream") == 0) {
-    ctx->ride_stream = (int)value;
-  } else if (std::strcmp(key, "chain_resident_max_rows") == 0) {
-    ctx->chain_resident_max_rows = (int)value;
-  } else if (std::strcmp(key, "trsv_resident") == 0) {
-    ctx->trsv_resident = value != 0;
-  } else if (std::strcmp(key, "chain_resident2_max_rows") == 0) {
-    ctx->chain_resident2_max_rows = (int)value;
-  } else if (std::strcmp(key, "chain_ahead") == 0) {
-    ctx->chain_ahead = value != 0;
-  } else if (std::strcmp(key, "chain_ahead_min_rows") == 0) {
-    ctx->chain_ahead_min_rows = (int)value;
-  } else if (std::strcmp(key, "ride_vchain_max_wgs") == 0) {
-    ctx->ride_vchain_max_wgs = (int)value;
-  } else if (std::strcmp(key, "ride_occ3") == 0) {
-    ctx->ride_occ3 = value != 0;
-  } else if (std::strcmp(key, "ride_aug") == 0) {
-    ctx->ride_aug = (int)value;
-  } else if (std::strcmp(key, "append_split") == 0) {
-    ctx->append_split = value != 0;
-  } else if (std::strcmp(key, "ride_gate_pct") == 0) {
-    ctx->ride_gate_pct = (int)value;
-  } else if (std::strcmp(key, "ride_outer_rows") == 0) {
-    LPGP_CHECK(value >= 0 && value % (4 * TILE) == 0, "ride_outer_rows must be a multiple of %d (0 disables)", 4 * TILE);
-    ctx->ride_outer_rows = value;
-  } else if (std::strcmp(key, "ride_outer_min_tiles") == 0) {
-    ctx->ride_outer_min_tiles = (int)value;
-  } else if (std::strcmp(key, "ride_max_tiles") == 0) {
-    ctx->ride_max_tiles = (int)value;
-  } else if (std::strcmp(key, "ride_same_stream_max_tiles") == 0) {
-    ctx->ride_same_stream_max_tiles = (int)value;
-  } else {
-    LPGP_CHECK(false, "unknown option %s", key);
-  }
-  return 0;
+  return option_set(*ctx, key, value);
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

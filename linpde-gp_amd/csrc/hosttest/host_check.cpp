@@ -3,11 +3,13 @@
 // (`build.sh --host-asan`), so that the non-trivial host C++ of the library -- exact polynomial tables,
 // parity-class folding, the isotropic-group folding, descriptor validation -- runs under a sanitizer on
 // the CPU box (GPU AddressSanitizer is not available).  tests/test_host_asan.py drives it
-// over the descriptor zoo and compares with the oracle.
+// over the descriptor zoo and compares with the oracle.  The option table of options.cpp is in it too
+// (tests/test_host_options.py).
 #include <cstdint>
 #include <vector>
 
 #include "../eval_entries.h"
+#include "../options.h"
 
 using namespace lpgp;
 
@@ -112,5 +114,18 @@ void lpgp_host_exp_neg(const double* s, int64_t n, double* out) {
   const ExpTab tab{g_exp_table};
   for (int64_t i = 0; i < n; ++i) out[i] = lpgp_exp_neg(s[i], tab);
 }
+
+// the option table (options.cpp) on one Options object, as lpgp_init / lpgp_get_option / lpgp_set_option drive it
+// (tests/test_host_options.py)
+static Options g_options;
+
+void lpgp_host_options_from_env(void) {
+  g_options = Options();
+  options_from_env(g_options);
+}
+int lpgp_host_options_get(const char* key, int64_t* value) { return option_get(g_options, key, value); }
+int lpgp_host_options_set(const char* key, int64_t value) { return option_set(g_options, key, value); }
+int lpgp_host_options_count(void) { return option_count(); }
+const char* lpgp_host_options_name(int i) { return option_name(i); }
 
 }  // extern "C"

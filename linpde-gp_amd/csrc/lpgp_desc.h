@@ -9,6 +9,8 @@
 
 namespace lpgp {
 
+constexpr int TILE = 128;          // base tile: potrf_tile block, GEMM block tile, padding unit
+
 void set_error(const char* fmt, ...);
 const char* last_error();
 
