@@ -341,6 +341,28 @@ int  lpgp_rhs_matmul(lpgp_ctx* ctx, const lpgp_rhs* A, const double* B_host, int
  * `L @ L.T` of `gram.todense()`.  beta == 0: C is not read.  Single GPU.                                           */
 int  lpgp_gemm_host(lpgp_ctx* ctx, int32_t transa, int32_t transb, int64_t m, int64_t n, int64_t k, double alpha,
                     const double* A_host, const double* B_host, double beta, double* C_host);
+/* ---- joint draws: replaces probnum's `Normal.sample` / `Normal.cov_cholesky` behind `RandomProcess.sample(rng, x, size)`
+ *      (the reference's call sites: utils/plotting.py `plot_random_process_samples`, experiments/0000 - 0003, cpu.py).
+ *      A draw at M points is  mean + C z  with  C C^T = Sigma(x, x) + delta I:  S = k(x, x) assembled into a matrix of its own
+ *      (lpgp_gram_assemble), lpgp_mat_sub_inner, lpgp_mat_add_diag, lpgp_potrf, lpgp_mat_factor_matmul -- the M x M
+ *      covariance never visits the host.  Both single GPU.                                                                  */
+/* Diagonal block bi of the UNFACTORED matrix S  -=  V^T V  (lower tiles; tiles above the diagonal may be written, they are
+ * never read): the Schur complement `k_xx - kLas_x0 @ gram.solve(kLas_x1.T)` of `CovarianceFunction._evaluate`
+ * (_conditional.py:223-231) with V = L^{-1} K_Xx (lpgp_trsm_lower) and x0 = x1, kept on the device.  V must have as many
+ * logical columns as the block has rows.  The existing fp64 MFMA product (transposed-transposed form) in bands of four tile
+ * columns from the diagonal down.  The two paddings differ (S: round_up(M, 128), identity tail; V: round_up(M + 1, 128), column M is
+ * the spare column that carries a residual after lpgp_predict): the spare columns of V the product reads are CLEARED first,
+ * so the identity tail of S survives.                                                                                     */
+int  lpgp_mat_sub_inner(lpgp_ctx* ctx, lpgp_mat* S, int32_t bi, lpgp_rhs* V);
+/* out_host (n x s, C-order) = shift_host[:, None] + L Z_host  for the lower Cholesky factor L of a fully FACTORED matrix in
+ * its logical layout (n = lpgp_mat_size; the padding rows between the blocks are skipped), Z_host n x s C-order, shift_host n
+ * doubles or NULL: `mean + cov_cholesky @ z` of probnum's `Normal.sample`.  Nothing above the diagonal of the storage reaches
+ * the result.  The same bits on every call (no atomics, fixed order of summation).  Fails on a matrix that is not fully
+ * factored, whose enqueued factorisation has not been checked (lpgp_mat_check), that is poisoned, or in a multi-GPU job.
+ * csrc/trmm.hip; bound by reading the lower triangle of L once, 4 n^2 bytes, for s <= 16.                                    */
+int  lpgp_mat_factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host,
+                            double* out_host);
+
 /* diag of sum_g (kd[g])(x, x): a constant for the stationary kernels supported here     */
 int  lpgp_kernel_diag(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, double* out_value);
 
@@ -394,7 +416,8 @@ enum lpgp_kernel_id { LPGP_K_ASSEMBLE = 0, LPGP_K_SYRK = 1 /* rank-nb trailing u
                       LPGP_K_ASSEMBLE_GRID = 9 /* tensor-grid (Kronecker) expansion kernels; LPGP_K_ASSEMBLE = per-entry kernel */,
                       LPGP_K_PANEL = 10 /* fused panel factorisation / fused substitution tile steps */,
                       LPGP_K_COMM = 11 /* multi-GPU panel exchanges (bytes = sent + received by this rank) */,
-                      LPGP_K_COUNT = 12 };
+                      LPGP_K_TRMM = 12 /* factor times tall matrix (lpgp_mat_factor_matmul): product and its fixed-order reduction */,
+                      LPGP_K_COUNT = 13 };
 /* mask: bit k enables HIP-event bracketing of kernel id k (0 = off, -1 = all)          */
 int  lpgp_profile_enable(lpgp_ctx* ctx, int32_t mask);
 int  lpgp_profile_reset(lpgp_ctx* ctx);

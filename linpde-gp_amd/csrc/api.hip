@@ -1766,6 +1766,44 @@ int lpgp_rhs_matmul(lpgp_ctx* ctx, const lpgp_rhs* A, const double* B_host, int6
   return 0;
 }
 
+int lpgp_mat_sub_inner(lpgp_ctx* ctx, lpgp_mat* S, int32_t bi, lpgp_rhs* V) {
+  LPGP_CHECK(ctx && S && V, "lpgp_mat_sub_inner: null argument");
+  LPGP_DEVICE(ctx);
+  LPGP_MAT_ALIVE(S, "lpgp_mat_sub_inner");
+  LPGP_CHECK(!ctx->distributed(), "lpgp_mat_sub_inner: single GPU only");
+  LPGP_CHECK(bi >= 0 && bi < (int)S->blocks.size(), "lpgp_mat_sub_inner: bad block %d", bi);
+  const lpgp_block& B = S->blocks[(size_t)bi];
+  LPGP_CHECK(B.poff >= S->pn_fact, "lpgp_mat_sub_inner: block %d is already factored", bi);
+  LPGP_CHECK(V->m == B.n, "lpgp_mat_sub_inner: V has %lld columns, block %d has %lld rows", (long long)V->m, bi, (long long)B.n);
+  LPGP_CHECK(V->ld % TILE == 0 && V->m_pad >= B.pn, "lpgp_mat_sub_inner: bad right-hand-side layout");
+  // the columns of V behind the logical ones that the product reads (the spare column may hold L^{-1} r after a prediction)
+  if (B.pn > V->m)
+    LPGP_HIP(hipMemsetAsync(V->v + V->m * V->ld, 0, (size_t)((B.pn - V->m) * V->ld) * sizeof(double), ctx->s_main));
+  // C[c0:, c0 : c0 + BW] -= V[:, c0:]^T V[:, c0 : c0 + BW], band by band: the triangular form of the product exists for
+  // row-major operands only, bands of BW tile columns from the diagonal down do (1 + 1 / nbands) / 2 of the full square's work
+  const int T = (int)(B.pn / TILE), BW = 4;
+  double* const C0 = S->a + B.poff * (S->lr_cap + 1);
+  for (int c0 = 0; c0 < T; c0 += BW) {
+    GemmArgs g;
+    g.A = V->v + (int64_t)c0 * TILE * V->ld; g.B = g.A; g.C = C0 + (int64_t)c0 * TILE * (S->lr_cap + 1);
+    g.lda = V->ld; g.ldb = V->ld; g.ldc = S->lr_cap;
+    g.mt = T - c0; g.nt = std::min(BW, T - c0); g.k = (int)V->ld; g.alpha = -1.0; g.beta = 1.0;
+    g.tri = 0;
+    LPGP_TRY(launch_gemm(ctx, ctx->s_main, 1, 1, g, LPGP_K_GEMM));
+  }
+  return 0;        // asynchronous: consumers are ordered behind it on the main stream
+}
+
+int lpgp_mat_factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host, double* out_host) {
+  LPGP_CHECK(ctx && mat && Z_host && out_host && s >= 1, "lpgp_mat_factor_matmul: bad argument");
+  LPGP_DEVICE(ctx);
+  LPGP_MAT_ALIVE(mat, "lpgp_mat_factor_matmul");
+  LPGP_CHECK(!ctx->distributed(), "lpgp_mat_factor_matmul: single GPU only");
+  LPGP_CHECK(mat->pn > 0 && mat->pn_fact == mat->pn, "lpgp_mat_factor_matmul: matrix is not (fully) factored");
+  LPGP_CHECK(!mat->unchecked, "lpgp_mat_factor_matmul: the status of an enqueued factorisation has not been read (lpgp_mat_check)");
+  return factor_matmul(ctx, mat, Z_host, s, shift_host, out_host);
+}
+
 int lpgp_gemm_host(lpgp_ctx* ctx, int32_t transa, int32_t transb, int64_t m, int64_t n, int64_t k, double alpha,
                    const double* A_host, const double* B_host, double beta, double* C_host) {
   LPGP_CHECK(ctx && A_host && B_host && C_host && m >= 1 && n >= 1 && k >= 1, "lpgp_gemm_host: bad argument");

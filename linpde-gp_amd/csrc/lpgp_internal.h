@@ -369,6 +369,8 @@ int trsm_lower_t_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, int
 int solve_vec(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, double* tmp, int* info);
 int solve_vec_resident(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, double* tmp, int* info);      // trsv.hip
 int solve_vec_fwd(lpgp_ctx* ctx, hipStream_t st, lpgp_mat* mat, int64_t T, double* b, double* x);
+// trmm.hip: out (n x s, C-order, logical rows) = shift[:, None] + L Z for the lower factor of a fully factored single-GPU matrix
+int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host, double* out_host);
 
 // assemble.hip ----------------------------------------------------------------------------
 // Every assembly kernel writes element (row_off + i, col_off + j) of the GLOBAL padded matrix to where `lay` keeps

@@ -434,6 +434,29 @@ class GramMatrix:
             self.block_sizes.append(int(n))
         return info.value
 
+    def sub_inner(self, bi: int, V: "Rhs") -> None:
+        """Diagonal block `bi` (not factored yet) -= V^T V on the device (`lpgp_mat_sub_inner`): the Schur complement of a
+        posterior covariance without a host copy.  Clears the spare columns of `V`."""
+        check(lib.lpgp_mat_sub_inner(self.ctx._h, self._h, int(bi), V._h), "lpgp_mat_sub_inner")
+
+    def factor_matmul(self, Z: np.ndarray, shift: np.ndarray | None = None) -> np.ndarray:
+        """shift[:, None] + L @ Z for the lower Cholesky factor L of this (factored) matrix, Z of shape (n, s)
+        (`lpgp_mat_factor_matmul`, csrc/trmm.hip).  Bit-identical from call to call."""
+        n = self.n
+        Z = np.ascontiguousarray(Z, dtype=np.double)
+        if Z.ndim != 2 or Z.shape[0] != n:
+            raise ValueError(f"shape mismatch: factor of order {n} @ {Z.shape}")
+        if shift is not None:
+            shift = np.ascontiguousarray(shift, dtype=np.double)
+            if shift.shape != (n,):
+                raise ValueError(f"shift must have shape ({n},), got {shift.shape}")
+        out = np.empty((n, Z.shape[1]))
+        if Z.shape[1] == 0:
+            return out
+        check(lib.lpgp_mat_factor_matmul(self.ctx._h, self._h, as_pd(Z), Z.shape[1], as_pd(shift) if shift is not None else None, as_pd(out)),
+              "lpgp_mat_factor_matmul")
+        return out
+
     def potrf_enqueue(self) -> None:
         """The factorisation enqueued, no host synchronisation (`lpgp_potrf_enqueue`): its status is read by `check`."""
         check(lib.lpgp_potrf_enqueue(self.ctx._h, self._h), "lpgp_potrf_enqueue")

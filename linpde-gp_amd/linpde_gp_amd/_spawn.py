@@ -310,6 +310,9 @@ class RemoteConditionalGaussianProcess:
     def predict(self, x, *, return_var: bool = True):
         return self._call("predict", x, return_var=return_var)
 
+    def sample(self, rng, x, size=(), *, damping=None):
+        raise NotImplementedError("`sample` is not available through the `lp.spawn` multi-GPU front (single GPU only)")
+
     @property
     def cov(self):
         return _RemoteCov(self)

@@ -60,3 +60,9 @@ matrix_free_device_iteration: bool = True        # iterates / residuals / search
 # the prediction riding inside -- only if it has at least this many rows; smaller ones are factored when the next conditioning
 # arrives (their kernels run while the host prepares it).
 defer_min_rows: int = 4096
+
+# `sample(rng, x, size)`: a joint draw is  mean + C z  with  C C^T = Sigma(x, x) + delta I  and  delta = sample_damping x (prior
+# variance of the sampled field), so the knob is scale-free.  A convention, not a measurement: computed variances are held to 1e-8
+# of the largest one, so a covariance that is singular in exact arithmetic (noise-free observations) has computed eigenvalues of
+# either sign at that level; two decades above it inflates a standard deviation that was zero by 1e-3 of the prior's.
+sample_damping: float = 1e-6

@@ -80,6 +80,42 @@ class GaussianProcess:
     def std(self, x):
         return np.sqrt(np.maximum(self.var(x), 0.0))
 
+
+    def sample(self, rng, x, size=(), *, damping=None):
+        """Joint draws of the process at the points `x` (probnum `RandomProcess.sample(rng, args, size)`).
+
+        `x` has shape batch + input_shape, the result shape size + batch; `size` is an int or a tuple, `size=()` gives one
+        draw of shape batch.  THE RANDOM STREAM IS PART OF THE CONTRACT: exactly one call
+        `z = rng.standard_normal(size + (M,))` with M = prod(batch), the points flattened in C order, and
+        `draw[s] = mean(x) + C z[s]` with the lower Cholesky factor `C C^T = k(x, x) + delta I`,
+        `delta = damping * k(x_0, x_0)` (the prior variance: the knob is scale-free; default `lp.config.sample_damping`).
+        Draws are therefore reproducible from a seed.  The covariance is assembled, factored (`lpgp_potrf`) and multiplied
+        (`lpgp_mat_factor_matmul`) on the device; the factor of the last point set is kept, so further draws at the same
+        points cost one product.  Raises `ValueError` for `damping < 0`, `np.linalg.LinAlgError` (naming the damping) if
+        the damped covariance does not factor."""
+        size = _sample_size(size)
+        damping = _sample_damping(damping)
+        X, batch = _sample_points(self, x)
+        M = X.shape[0]
+        z = np.asarray(rng.standard_normal(size + (M,)), dtype=np.double)
+        if z.shape != size + (M,):
+            raise ValueError(f"`rng.standard_normal` returned shape {z.shape}, expected {size + (M,)}")
+        if M == 0:
+            return np.empty(size + batch)
+        ctx = _sample_context()
+        lowered = self.cov.lower()
+        delta = damping * _engine.kernel_diag(ctx, lowered)
+        hit = _cached_factor(self, X, delta, None)
+        if hit is None:
+            mean = np.array(np.broadcast_to(np.asarray(self.mean(x), dtype=np.double), batch), dtype=np.double).reshape(-1)
+            S = _engine.GramMatrix(ctx, capacity_hint=M)
+            S.add_block(M)
+            S.assemble(lowered, _engine.Points(ctx, X), None, 0, 0)
+            _factor_damped(S, delta, damping)
+            self._sample_cache = ((_engine.option_epoch(), delta, None), X.copy(), S, mean)
+            hit = (S, mean)
+        return _draws(hit[0], hit[1], z, size, batch)
+
     def condition_on_observations(self, Y, X=None, *, L=None, b=None):
         from .. import _spawn
         if _spawn.active() is not None:
@@ -90,6 +126,65 @@ class GaussianProcess:
             from ._matrix_free import MatrixFreeConditionalGaussianProcess
             return MatrixFreeConditionalGaussianProcess.from_observations(self, Y, X, L=L, b=b)
         return ConditionalGaussianProcess.from_observations(self, Y, X, L=L, b=b)
+
+
+# ---- joint draws (`RandomProcess.sample` of probnum, behind it `Normal.sample` / `cov_cholesky`) ------------------------
+def _sample_size(size) -> tuple:
+    if isinstance(size, (int, np.integer)):
+        size = (int(size),)
+    size = tuple(int(k) for k in size)
+    if any(k < 0 for k in size):
+        raise ValueError(f"`size` must not be negative, got {size}")
+    return size
+
+
+def _sample_damping(damping) -> float:
+    from .. import config
+    d = float(config.sample_damping if damping is None else damping)
+    if not d >= 0.0:
+        raise ValueError(f"`damping` must be a non-negative number, got {damping!r}")
+    return d
+
+
+def _sample_context():
+    from .. import _spawn
+    if _spawn.active() is not None:
+        raise NotImplementedError("`sample` is not available through the `lp.spawn` multi-GPU front (single GPU only)")
+    ctx = _engine.default_context()
+    if ctx.distributed:
+        raise NotImplementedError("`sample` is not available in a multi-GPU job (single GPU only)")
+    return ctx
+
+
+def _sample_points(gp, x):
+    x = np.asarray(x, dtype=np.double)
+    nd = gp.input_ndim
+    if nd and (x.ndim < nd or x.shape[x.ndim - nd:] != tuple(gp.input_shape)):
+        raise ValueError(f"The shape of the input {x.shape} is not compatible with the input shape {tuple(gp.input_shape)} of the process.")
+    return gp._flat(x)
+
+
+def _factor_damped(S: "_engine.GramMatrix", delta: float, damping: float) -> None:
+    S.add_diag(0, None, delta)
+    info = S.potrf()
+    if info != 0:
+        raise np.linalg.LinAlgError(
+            f"{info}-th leading minor of the (padded) covariance at the sample points is not positive definite with damping = {damping:g} "
+            f"(delta = {delta:g} on the diagonal); pass a larger `damping`")
+
+
+def _cached_factor(gp, X, delta, coeffs_key):
+    c = getattr(gp, "_sample_cache", None)
+    if c is None or c[0] != (_engine.option_epoch(), delta, coeffs_key) or c[1].shape != X.shape or not np.array_equal(c[1], X):
+        return None
+    return c[2], c[3]
+
+
+def _draws(S: "_engine.GramMatrix", mean: np.ndarray, z: np.ndarray, size: tuple, batch: tuple) -> np.ndarray:
+    """draw[s] = mean + C z[s] for every z[s] of `z` (shape size + (M,)): one product on the device."""
+    M = mean.size
+    out = S.factor_matmul(np.ascontiguousarray(z.reshape(-1, M).T), mean)          # (M, number of draws)
+    return np.ascontiguousarray(out.T).reshape(size + batch)
 
 
 class _ObservationBlock:
@@ -651,6 +746,49 @@ class ConditionalGaussianProcess(GaussianProcess):
 
     def var(self, x):
         return self.predict(x, return_var=True)[1]
+
+    def sample(self, rng, x, size=(), *, damping=None):
+        """Joint draws of the posterior (of the read-out `D(u)` if this object is one) at the points `x`.
+
+        Shapes and the random stream as `GaussianProcess.sample`: `x` of shape batch + input_shape, result size + batch,
+        exactly one call `z = rng.standard_normal(size + (M,))`, points flattened in C order, `draw[s] = mean(x) + C z[s]`
+        with `C C^T = Sigma(x, x) + delta I`, `delta = damping *` (prior variance of the sampled field).  `Sigma(x, x) =
+        k(x, x) - V^T V`, `V = L^{-1} K_Xx` (`_conditional.py:223-231`), is formed in a device matrix of its own
+        (`lpgp_mat_sub_inner`) and factored there; the M x M covariance never visits the host, and the posterior's Gram
+        matrix is neither extended nor copied: a posterior is a value, sampling changes nothing observable.  The factor of
+        the last point set (points by value, damping, read-out) is kept: more draws at the same points cost one product.
+        Lazy mode: a deferred factorisation is flushed and verified first, as `cov.matrix` does."""
+        size = _sample_size(size)
+        damping = _sample_damping(damping)
+        X, batch = _sample_points(self, x)
+        M = X.shape[0]
+        z = np.asarray(rng.standard_normal(size + (M,)), dtype=np.double)
+        if z.shape != size + (M,):
+            raise ValueError(f"`rng.standard_normal` returned shape {z.shape}, expected {size + (M,)}")
+        if M == 0:
+            return np.empty(size + batch)
+        _sample_context()
+        self._check_current()
+        ctx = self._state.ctx
+        delta = damping * self._prior_diag()
+        key = tuple(sorted(self._test_coeffs.items()))
+        hit = _cached_factor(self, X, delta, key)
+        if hit is None:
+            mean = np.array(self.predict(x, return_var=False), dtype=np.double).reshape(-1)
+            self._check_current()
+            P = _engine.Points(ctx, X)
+            S = _engine.GramMatrix(ctx, capacity_hint=M)
+            S.add_block(M)
+            S.assemble(_lowered(self._prior.cov, self._test_coeffs, self._test_coeffs), P, None, 0, 0)
+            if self._blocks:
+                V = self._cross(P)
+                V.trsm_lower()
+                S.sub_inner(0, V)
+                del V
+            _factor_damped(S, delta, damping)
+            self._sample_cache = ((_engine.option_epoch(), delta, key), X.copy(), S, mean)
+            hit = (S, mean)
+        return _draws(hit[0], hit[1], z, size, batch)
 
     def __call__(self, x) -> randvars.Normal:
         X, batch = self._flat(x)

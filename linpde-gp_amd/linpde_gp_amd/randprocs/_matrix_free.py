@@ -420,6 +420,9 @@ class MatrixFreeConditionalGaussianProcess:
     def std(self, x):
         return np.sqrt(np.maximum(self.var(x), 0.0))
 
+    def sample(self, rng, x, size=(), *, damping=None):
+        raise NotImplementedError("`sample` needs the dense factorisation: a matrix-free posterior has no Cholesky factor to draw with")
+
     @property
     def cov(self):
         return _MatrixFreeCovariance(self)

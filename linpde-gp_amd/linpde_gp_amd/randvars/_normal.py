@@ -66,6 +66,70 @@ class Normal:
     def size(self):
         return self._mean.size
 
+    def _device_factor(self):
+        """The dense covariance as a factored device matrix (`lpgp_mat_add_dense`, `lpgp_potrf`), built once."""
+        S = getattr(self, "_cov_factor", None)
+        if S is None:
+            from .. import _engine, _spawn
+            from ..randprocs import covfuncs
+            if _spawn.active() is not None:
+                raise NotImplementedError("`cov_cholesky` / `sample` are not available through the `lp.spawn` multi-GPU front")
+            ctx = _engine.default_context()
+            if ctx.distributed:
+                raise NotImplementedError("`cov_cholesky` / `sample` are not available in a multi-GPU job")
+            n = self._mean.size
+            S = _engine.GramMatrix(ctx, n)
+            bi = S.add_block(n)
+            S.assemble(covfuncs.Zero(()).lower(), _engine.Points(ctx, np.zeros((n, 1))), None, bi, bi)   # clear the block, then add the covariance
+            S.add_dense(bi, np.ascontiguousarray(self._cov.reshape(n, n)))
+            info = S.potrf()
+            if info != 0:
+                raise np.linalg.LinAlgError(f"{info}-th leading minor of the covariance is not positive definite")
+            self._cov_factor = S
+        return S
+
+    @property
+    def cov_cholesky(self) -> np.ndarray:
+        """Dense lower Cholesky factor of the covariance (probnum `Normal.cov_cholesky`), cached.  A dense covariance is
+        factored on the device; scalar and diagonal covariances are square roots on the host."""
+        C = getattr(self, "_cov_cholesky", None)
+        if C is None:
+            if self._mean.ndim == 0:
+                C = np.sqrt(self._cov)
+            elif self._cov_diag is not None:
+                C = np.diag(np.sqrt(self._cov_diag))
+            else:
+                C = self._device_factor().todense("factor")
+            if np.any(np.isnan(C)):
+                raise np.linalg.LinAlgError("the covariance has a negative variance")
+            self._cov_cholesky = C
+        return C
+
+    def sample(self, rng, size=()):
+        """Draws of shape size + self.shape (probnum `Normal.sample(rng, size)`).  THE RANDOM STREAM IS PART OF THE CONTRACT:
+        exactly one call `z = rng.standard_normal(size + self.shape)` and `draw[s] = mean + C z[s]` with the lower Cholesky
+        factor `C` of the covariance (the mean flattened in C order).  A dense covariance is factored and multiplied on the
+        device (`lpgp_potrf`, `lpgp_mat_factor_matmul`); scalar and diagonal ones are scaled on the host, no device call."""
+        if isinstance(size, (int, np.integer)):
+            size = (int(size),)
+        size = tuple(int(k) for k in size)
+        if any(k < 0 for k in size):
+            raise ValueError(f"`size` must not be negative, got {size}")
+        shape = tuple(self._mean.shape)
+        z = np.asarray(rng.standard_normal(size + shape), dtype=np.double)
+        if z.shape != size + shape:
+            raise ValueError(f"`rng.standard_normal` returned shape {z.shape}, expected {size + shape}")
+        if self._mean.ndim == 0 or self._cov_diag is not None:
+            var = self._cov if self._mean.ndim == 0 else self._cov_diag.reshape(shape)
+            if np.any(var < 0.0):
+                raise ValueError("the covariance has a negative variance")
+            return self._mean + np.sqrt(var) * z
+        n = self._mean.size
+        if n == 0 or z.size == 0:
+            return np.empty(size + shape)
+        out = self._device_factor().factor_matmul(np.ascontiguousarray(z.reshape(-1, n).T), self._mean.reshape(-1))
+        return np.ascontiguousarray(out.T).reshape(size + shape)
+
 
 class Constant:
     def __init__(self, support):

@@ -1,0 +1,500 @@
+"""Joint draws on the device: `GaussianProcess.sample(rng, x, size)`, `ConditionalGaussianProcess.sample`, `Normal.sample` /
+`Normal.cov_cholesky` (probnum's `RandomProcess.sample`) and the two entry points behind them, `lpgp_mat_sub_inner` and
+`lpgp_mat_factor_matmul` (csrc/trmm.hip).  Oracle: `oracle.gp` / `oracle.covfuncs` + LAPACK.
+
+Stand-in generators: the random stream is part of the contract (exactly one `rng.standard_normal(size + (M,))`), so a test may
+pass an object whose `standard_normal` returns chosen vectors: the identity (`size=(M,)` draws give `draws - mean = C^T`),
+zeros (the draw is the mean), or a recorder."""
+import gc
+
+import numpy as np
+import pytest
+
+from oracle import covfuncs as ocf
+from oracle import gp as ogp
+
+pytestmark = pytest.mark.gpu
+
+U = 2.0 ** -53
+
+
+@pytest.fixture
+def lp():
+    import linpde_gp_amd as lp
+    return lp
+
+
+@pytest.fixture(params=["eager", "lazy"])
+def mode(lp, request):
+    """Both factorisation modes (`lp.config.lazy_factorization`): set, yield, restore."""
+    saved = lp.config.lazy_factorization
+    lp.config.lazy_factorization = request.param == "lazy"
+    yield request.param
+    lp.config.lazy_factorization = saved
+
+
+class _Gen:
+    """Stand-in for `numpy.random.Generator`: records every request, answers with `fn(shape)`."""
+
+    def __init__(self, fn):
+        self._fn, self.calls = fn, []
+
+    def standard_normal(self, shape):
+        shape = tuple(shape)
+        self.calls.append(shape)
+        return self._fn(shape)
+
+
+def eye_gen():
+    return _Gen(lambda shape: np.eye(shape[-1]).reshape(shape))
+
+
+def zero_gen():
+    return _Gen(np.zeros)
+
+
+def _ctx():
+    from linpde_gp_amd import _engine
+    return _engine.default_context()
+
+
+def _chain_1d(lp, sizes=(2, 3, 2, 4), noise=((np.ones(2), 0.6**2), None, None, (np.zeros(4), 0.3**2)), span=1.0):
+    """The reference's integration case (`test_posterior_gp.py:152-178`): four batches, two with noise, 4 * ExpQuad(l = 0.25)
+    (the helper of tests/test_gpu_cov_linop.py; `sizes` / `noise` generalise it to longer blocks)."""
+    cf = lp.randprocs.covfuncs
+    prior = lp.GaussianProcess(lp.functions.Zero((1,)), 2.0**2 * cf.ExpQuad((1,), lengthscales=0.25))
+    okern = [(4.0, [("expquad", 0.25)])]
+    Xs = np.linspace(-span, span, sum(sizes))[:, None]
+    Ys = 2.0 * np.sin(np.pi * Xs[:, 0])
+    u, oblocks = prior, []
+    for X, Y, nz in zip(np.array_split(Xs, np.cumsum(sizes)[:-1]), np.array_split(Ys, np.cumsum(sizes)[:-1]), noise):
+        u = u.condition_on_observations(Y, X, b=None if nz is None else lp.randvars.Normal(nz[0], nz[1] * np.eye(len(Y))))
+        oblocks.append(ogp.ObsBlock(X, ocf.identity(1), Y, None if nz is None else nz[0], None if nz is None else nz[1]))
+    return u, ogp.condition(okern, oblocks)
+
+
+def _scattered_2d(lp, n=700):
+    cf = lp.randprocs.covfuncs
+    rng = np.random.default_rng(8)
+    X = rng.uniform(-1, 1, (n, 2))
+    Y = np.sin(3 * X[:, 0]) * np.cos(2 * X[:, 1])
+    prior = lp.GaussianProcess(lp.functions.Zero((2,)), 1.3**2 * cf.TensorProduct(cf.Matern((), nu=2.5, lengthscales=0.4), cf.Matern((), nu=2.5, lengthscales=0.4)))
+    okern = [(1.69, [("matern", 2.5, 0.4), ("matern", 2.5, 0.4)])]
+    u = prior.condition_on_observations(Y, X, b=lp.randvars.Normal(np.zeros(n), 1e-3 * np.eye(n)))
+    return u, ogp.condition(okern, [ogp.ObsBlock(X, ocf.identity(2), Y, 0.0, 1e-3)])
+
+
+# ---- 1. the product kernel alone -----------------------------------------------------------------------------------------
+def _factored_dense(lp, A):
+    """A dense SPD matrix as a factored device matrix: clear the block (zero kernel), `add_dense`, `potrf`."""
+    from linpde_gp_amd import _engine
+    ctx = _ctx()
+    n = A.shape[0]
+    mat = _engine.GramMatrix(ctx, n)
+    bi = mat.add_block(n)
+    mat.assemble(lp.randprocs.covfuncs.Zero(()).lower(), _engine.Points(ctx, np.zeros((n, 1))), None, bi, bi)
+    mat.add_dense(bi, A)
+    assert mat.potrf() == 0
+    return mat
+
+
+def _check_product(mat, L, rng, cols=(1, 5, 128, 130)):
+    n = L.shape[0]
+    Ll, aL = np.tril(L).astype(np.longdouble), np.abs(np.tril(L))
+    for s in cols:
+        Z = rng.standard_normal((n, s))
+        for shift in (None, rng.standard_normal(n) * 3.0):
+            out = mat.factor_matmul(Z, shift)
+            sh = np.zeros(n) if shift is None else shift
+            ref = sh[:, None].astype(np.longdouble) + Ll @ Z.astype(np.longdouble)
+            bound = (n + 2) * U * (aL @ np.abs(Z) + np.abs(sh)[:, None])
+            err = np.abs(out.astype(np.longdouble) - ref)
+            worst = float(np.max(err / np.maximum(bound, 1e-300)))
+            print(f"factor_matmul n={n} s={s} shift={shift is not None}: max err / bound = {worst:.3e}")
+            assert np.all(err <= bound), (n, s, worst)
+            row0 = sh[0] + L[0, 0] * Z[0]
+            assert np.all(np.abs(out[0] - row0) <= 2 * U * (np.abs(sh[0]) + np.abs(L[0, 0] * Z[0])))
+            again = mat.factor_matmul(Z, shift)
+            assert np.array_equal(out, again)            # bit-identical from call to call
+
+
+@pytest.mark.parametrize("n", [1, 37, 128, 129, 300, 1000, 2100])
+def test_factor_matmul_entrywise_bound(lp, n):
+    """`out = shift + tril(L) Z` entry by entry within the bound of an inner product of length n in any order of summation,
+    `(n + 2) u (|tril(L)| |Z| + |shift|)` (reference product in extended precision), for 1, 5, 128 and 130 columns, with and
+    without a shift; row 0 is `shift[0] + L[0, 0] Z[0]` to two roundings; two calls agree bit for bit.
+
+    A further case one would want -- the same bound on a matrix whose storage ABOVE the diagonal tiles was filled with large entries
+    by an assembly before `add_dense` -- cannot be built that way and is dropped: no assembly ever writes a tile above the
+    diagonal of a diagonal block (`lower_only` skips them in every assembly kernel, `lpgp_mat_add_dense` adds to the lower
+    part, and the symmetric `what = 0` copy-out mirrors the lower triangle, so it cannot show them either).  The one writer
+    of those tiles is `lpgp_mat_sub_inner`; `test_sub_inner_then_product_ignores_the_upper_tiles` covers that route."""
+    rng = np.random.default_rng(100 + n)
+    B = rng.standard_normal((n, n))
+    A = B @ B.T + n * np.eye(n)
+    mat = _factored_dense(lp, A)
+    L = mat.todense("factor")
+    _check_product(mat, L, rng)
+
+
+def test_sub_inner_then_product_ignores_the_upper_tiles(lp):
+    """`S -= V^T V` (`lpgp_mat_sub_inner`) writes whole tiles, also above the diagonal, with entries as large as the lower
+    ones; after the factorisation the product must not see them (n = 300 and 1000: three and eight tile rows).  Also the
+    padding contract: the right-hand side has been through `predict` on the same points, so its spare column M holds
+    L^{-1} r when `sub_inner` reads it -- the identity tail of S must survive (the padded matrix still factors, and its
+    logical factor reproduces k(x, x) - V^T V + delta I formed on the host)."""
+    from linpde_gp_amd import _engine
+    ctx = _ctx()
+    cf = lp.randprocs.covfuncs
+    rng = np.random.default_rng(5)
+    for M in (300, 1000):
+        Xo = rng.uniform(-1, 1, (90, 1))
+        prior = lp.GaussianProcess(lp.functions.Zero((1,)), 30.0 * cf.ExpQuad((1,), lengthscales=0.3))
+        u = prior.condition_on_observations(np.sin(3 * Xo[:, 0]), Xo, b=lp.randvars.Normal(np.zeros(90), 0.5 * np.eye(90)))
+        x = np.sort(rng.uniform(-1, 1, (M, 1)), axis=0)
+        P = _engine.Points(ctx, x)
+        u._check_current()
+        V = u._cross(P)
+        u._ensure_residual()
+        V.predict(np.zeros(M), np.full(M, 30.0))          # forward substitution in place; the spare column carries L^{-1} r
+        Vh = V.to_host()                                  # (90, M) = L^{-1} K_Xx
+        S = _engine.GramMatrix(ctx, M)
+        S.add_block(M)
+        S.assemble(prior.cov.lower(), P, None, 0, 0)
+        Kxx = S.todense("gram")
+        S.sub_inner(0, V)
+        got = S.todense("gram")
+        ref = Kxx - Vh.T @ Vh
+        assert np.max(np.abs(got - ref)) <= 1e-12 * np.max(np.abs(Kxx))
+        S.add_diag(0, None, 1e-3)
+        assert S.potrf() == 0                              # (an identity tail hit by the spare column would not stay 1)
+        L = S.todense("factor")
+        A = ref + 1e-3 * np.eye(M)
+        assert np.max(np.abs(L @ L.T - A)) <= 4 * (M + 1) * U * np.max(np.abs(A)) + 1e-12 * np.max(np.abs(Kxx))
+        _check_product(S, L, rng, cols=(5,))
+
+
+# ---- 2. a multi-block factor ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sizes", [(2, 3, 2, 4), (130, 300)])
+def test_factor_matmul_multi_block_layout(lp, sizes):
+    """The logical layout: padding rows between the observation blocks are skipped.  `u.gram.cholesky()` on the host against
+    the product with Z = I."""
+    if sizes == (2, 3, 2, 4):
+        u, _ = _chain_1d(lp)
+    else:
+        u, _ = _chain_1d(lp, sizes=sizes, noise=((np.zeros(130), 0.05), (np.zeros(300), 0.02)), span=3.0)
+    L = u.gram.cholesky()
+    n = L.shape[0]
+    assert n == sum(sizes)
+    mat = u._state.mat
+    out = mat.factor_matmul(np.eye(n))
+    assert np.all(np.abs(out - L) <= (n + 2) * U * np.abs(L))
+    rng = np.random.default_rng(3)
+    _check_product(mat, L, rng, cols=(5,))
+
+
+# ---- 3. the posterior factor reproduces the oracle's covariance -------------------------------------------------------------
+def _check_posterior_factor(u, x, Sigma_o, prior_var, damping, eta):
+    """With the identity generator C = (draws - mean)^T is lower triangular with a positive diagonal and
+    max |C C^T - (Sigma_o + delta I)| <= (eta + 4 (M + 1) u) max |Sigma_o + delta I|; the zero generator returns `u.mean(x)`
+    bit for bit.  Returns C."""
+    M = Sigma_o.shape[0]
+    g0 = zero_gen()
+    m0 = u.sample(g0, x, damping=damping)
+    mean = u.mean(x)
+    assert m0.shape == mean.shape and np.array_equal(m0, mean)
+    assert g0.calls == [(M,)]
+    g = eye_gen()
+    draws = u.sample(g, x, size=(M,), damping=damping)
+    assert g.calls == [(M, M)] and draws.shape == (M,) + mean.shape
+    C = (draws.reshape(M, M) - mean.reshape(1, M)).T
+    assert np.all(np.triu(C, 1) == 0.0)
+    assert np.all(np.diag(C) > 0.0)
+    A = Sigma_o + damping * prior_var * np.eye(M)
+    err = float(np.max(np.abs(C @ C.T - A)))
+    bar = (eta + 4 * (M + 1) * U) * float(np.max(np.abs(A)))
+    print(f"posterior factor M={M} damping={damping:g}: max |C C^T - A| = {err:.3e}, bar {bar:.3e}")
+    assert err <= bar
+    return C
+
+
+def test_posterior_factor_1d_chain(lp, mode):
+    u, post = _chain_1d(lp)
+    x = np.linspace(-1.0, 1.0, 50)[:, None]
+    _check_posterior_factor(u, x, post.cov(x), 4.0, 1e-6, 1e-9)          # (lazy: the sample is the first use of the deferred blocks)
+
+
+@pytest.mark.parametrize("M", [900, 256, 1])
+def test_posterior_factor_2d_scattered(lp, mode, M):
+    """700 observations, noise 1e-3.  M = 900: ragged, eight tile rows of S, V padded one column further; M = 256: the padding
+    edge, round_up(M, 128) != round_up(M + 1, 128); M = 1."""
+    u, post = _scattered_2d(lp)
+    x = np.random.default_rng(11).uniform(-1, 1, (M, 2))
+    _check_posterior_factor(u, x, post.cov(x), 1.69, 1e-6, 1e-9)
+
+
+def test_posterior_factor_through_a_read_out(lp, mode):
+    """`D(u).sample` samples the derived field: the Laplacian of the 1-D chain at 23 points (bar 1e-8, as the covariance of a
+    read-out is held to in tests/test_gpu_cov_linop.py)."""
+    from linpde_gp_amd.linfuncops import diffops
+    u, post = _chain_1d(lp)
+    xt = np.linspace(-0.9, 0.9, 23)[:, None]
+    Lu = diffops.Laplacian((1,))(u)
+    ref = post.cov(xt, Ltest={(2,): 1.0})
+    prior_var = float(ocf.k_diag([(4.0, [("expquad", 0.25)])], {(2,): 1.0}, {(2,): 1.0}, xt[:1])[0])
+    _check_posterior_factor(Lu, xt, ref, prior_var, 1e-6, 1e-8)
+
+
+def test_sample_right_after_predict_on_the_same_points(lp, mode):
+    """A prediction leaves L^{-1} r in the spare column of its right-hand side; a sample at the same points that follows at
+    once must not see it (M = 900: the spare column lies inside the last tile of S)."""
+    u, post = _scattered_2d(lp)
+    x = np.random.default_rng(12).uniform(-1, 1, (900, 2))
+    u.predict(x)
+    _check_posterior_factor(u, x, post.cov(x), 1.69, 1e-6, 1e-9)
+
+
+# ---- 4. a seeded draw equals the oracle's draw where that is well posed ------------------------------------------------------
+def _check_seeded_draw(u, post, x, prior_var):
+    damping, size = 1e-4, (3, 2)
+    M = x.shape[0]
+    A = post.cov(x) + damping * prior_var * np.eye(M)
+    kappa = float(np.linalg.cond(A, 2))
+    assert kappa <= 1e5, kappa                      # a condition of the test's own points: the bound below cannot grow into vacuity
+    mean_o = post.mean(x)
+    C_o = np.linalg.cholesky(A)
+    z = np.random.default_rng(7).standard_normal(size + (M,))
+    ref = mean_o + z @ C_o.T
+    got = u.sample(np.random.default_rng(7), x, size=size, damping=damping)
+    assert got.shape == size + (M,)
+    eta = 1e-9 + 4 * (M + 1) * U
+    dA = M * eta * np.max(np.abs(A))
+    dC = kappa / np.sqrt(2.0) * dA / np.linalg.norm(A, 2) * np.linalg.norm(C_o, 2)        # Sun 1991; Higham section 10.3.1
+    tol = 2.0 * dC * float(np.max(np.linalg.norm(z, axis=-1))) + 1e-8 * float(np.max(np.abs(mean_o)))
+    err = float(np.max(np.abs(got - ref)))
+    print(f"seeded draw M={M}: kappa_2 = {kappa:.3e}, max |draw - oracle| = {err:.3e}, tolerance {tol:.3e}")
+    assert err <= tol
+
+
+@pytest.mark.parametrize("M", [9, 12])
+def test_seeded_draw_equals_the_oracle_1d(lp, M):
+    u, post = _chain_1d(lp)
+    _check_seeded_draw(u, post, np.linspace(-1.2, 1.2, M)[:, None], 4.0)
+
+
+def test_seeded_draw_equals_the_oracle_2d(lp):
+    u, post = _scattered_2d(lp)
+    g = np.linspace(-1.0, 1.0, 5)
+    x = np.stack(np.meshgrid(g, g, indexing="ij"), axis=-1).reshape(-1, 2)
+    _check_seeded_draw(u, post, x, 1.69)
+
+
+# ---- 5. prior ------------------------------------------------------------------------------------------------------------------
+def _check_prior_factor(prior, x, K_o, prior_var, mean_o, damping=1e-6):
+    M = K_o.shape[0]
+    m0 = prior.sample(zero_gen(), x, damping=damping)
+    assert np.array_equal(m0, mean_o)
+    draws = prior.sample(eye_gen(), x, size=(M,), damping=damping)
+    C = (draws - mean_o[None, :]).T
+    assert np.all(np.triu(C, 1) == 0.0) and np.all(np.diag(C) > 0.0)
+    A = K_o + damping * prior_var * np.eye(M)
+    err = float(np.max(np.abs(C @ C.T - A)))
+    bar = (4e-15 + 4 * (M + 1) * U) * float(np.max(np.abs(A)))
+    print(f"prior factor M={M}: max |C C^T - A| = {err:.3e}, bar {bar:.3e}")
+    assert err <= bar
+
+
+def test_prior_sample_tensor_product_matern(lp):
+    """The README's prior (2^2 * Matern-5/2 x Matern-5/2) on 300 scattered points against the oracle's kernel matrix."""
+    cf = lp.randprocs.covfuncs
+    prior = lp.GaussianProcess(lp.functions.Zero((2,)), 2.0**2 * cf.TensorProduct(cf.Matern((), nu=2.5), cf.Matern((), nu=2.5)))
+    x = np.random.default_rng(21).uniform(-1, 1, (300, 2))
+    K_o = ocf.LkL([(4.0, [("matern", 2.5, 1.0), ("matern", 2.5, 1.0)])], ocf.identity(2), ocf.identity(2), x)
+    _check_prior_factor(prior, x, K_o, 4.0, np.zeros(300))
+
+
+def test_prior_sample_expquad_constant_mean(lp):
+    cf = lp.randprocs.covfuncs
+    prior = lp.GaussianProcess(lp.functions.Constant((1,), 1.75), 0.5 * cf.ExpQuad((1,), lengthscales=0.25))
+    x = np.linspace(-1.0, 1.0, 40)[:, None]
+    K_o = ocf.LkL([(0.5, [("expquad", 0.25)])], ocf.identity(1), ocf.identity(1), x)
+    _check_prior_factor(prior, x, K_o, 0.5, np.full(40, 1.75))
+
+
+# ---- 6. shapes and stream --------------------------------------------------------------------------------------------------
+def test_shapes_and_stream(lp):
+    cf = lp.randprocs.covfuncs
+    prior2 = lp.GaussianProcess(lp.functions.Zero((2,)), cf.TensorProduct(cf.Matern((), nu=2.5), cf.Matern((), nu=2.5)))
+    x = np.random.default_rng(0).uniform(-1, 1, (6, 5, 2))
+    for size, want in (((), ()), (4, (4,)), ((2, 3), (2, 3))):
+        g = _Gen(np.random.default_rng(1).standard_normal)
+        out = prior2.sample(g, x, size=size, damping=1e-6)
+        assert out.shape == want + (6, 5)
+        assert g.calls == [want + (30,)]                      # exactly one request, size + (M,)
+    # the points are flattened in C order: the batch-shaped call is the flat call reshaped
+    flat = prior2.sample(np.random.default_rng(2), x.reshape(30, 2), size=3, damping=1e-6)
+    shaped = prior2.sample(np.random.default_rng(2), x, size=3, damping=1e-6)
+    assert np.array_equal(shaped.reshape(3, 30), flat)
+    # input shape (): x of shape (17,)
+    prior0 = lp.GaussianProcess(lp.functions.Zero(()), cf.Matern((), nu=1.5, lengthscales=0.7))
+    g = _Gen(np.random.default_rng(3).standard_normal)
+    out = prior0.sample(g, np.linspace(0, 1, 17), size=(2,), damping=1e-6)
+    assert out.shape == (2, 17) and g.calls == [(2, 17)]
+    # a posterior: the same conventions
+    u, _ = _scattered_2d(lp, n=60)
+    g = _Gen(np.random.default_rng(4).standard_normal)
+    out = u.sample(g, x, size=(2, 3), damping=1e-6)
+    assert out.shape == (2, 3, 6, 5) and g.calls == [(2, 3, 30)]
+    assert u.sample(np.random.default_rng(5), x, damping=1e-6).shape == (6, 5)
+    # reproducible from a seed
+    a = u.sample(np.random.default_rng(6), x, size=2, damping=1e-6)
+    b = u.sample(np.random.default_rng(6), x, size=2, damping=1e-6)
+    assert np.array_equal(a, b)
+    # the default damping is `lp.config.sample_damping`
+    assert lp.config.sample_damping == 1e-6
+    assert np.array_equal(u.sample(np.random.default_rng(6), x, size=2), a)
+
+
+# ---- 7. value semantics -----------------------------------------------------------------------------------------------------
+def test_sampling_changes_nothing_observable(lp, mode):
+    ctx = _ctx()
+    gc.collect()
+    live0 = ctx.get_option("live_mats")
+    u, post = _scattered_2d(lp, n=300)
+    x = np.random.default_rng(31).uniform(-1, 1, (200, 2))
+    m_before, v_before = u.predict(x)
+    blocks_before = u._state.mat.num_blocks_total
+    first = u.sample(np.random.default_rng(9), x, size=3, damping=1e-6)
+    m_after, v_after = u.predict(x)
+    assert np.array_equal(m_before, m_after) and np.array_equal(v_before, v_after)
+    assert u._state.mat.num_blocks_total == blocks_before          # the posterior's Gram matrix was not extended
+    # a second sample at the same points does not factor (nor assemble, nor solve) again: counted through the profiling slots
+    # of `lpgp_profile_get` -- every slot but the product's own ("trmm") stays at zero launches
+    ctx.profile_enable(True)
+    try:
+        ctx.profile_reset()
+        second = u.sample(np.random.default_rng(9), x, size=3, damping=1e-6)
+        prof = ctx.profile_get()
+    finally:
+        ctx.profile_enable(False)
+    assert np.array_equal(first, second)
+    assert prof["trmm"]["launches"] == 1
+    assert all(v["launches"] == 0 for k, v in prof.items() if k != "trmm"), prof
+    # conditioning further and sampling the NEW posterior leaves a repeated draw from the old one bit-identical -- from the
+    # kept factor, and also when the factor is rebuilt from the shared device matrix (another view of it is current by then)
+    Xn = np.random.default_rng(32).uniform(-1, 1, (150, 2))
+    u2 = u.condition_on_observations(np.zeros(150), Xn, b=lp.randvars.Normal(np.zeros(150), 1e-2 * np.eye(150)))
+    other = u2.sample(np.random.default_rng(9), x, size=3, damping=1e-6)
+    assert np.max(np.abs(other - first)) > 1e-6
+    assert np.array_equal(u.sample(np.random.default_rng(9), x, size=3, damping=1e-6), first)
+    u._sample_cache = None
+    assert np.array_equal(u.sample(np.random.default_rng(9), x, size=3, damping=1e-6), first)
+    assert np.array_equal(u2.sample(np.random.default_rng(9), x, size=3, damping=1e-6), other)
+    # no leak: the kept factors go with their posteriors
+    del u, u2, post
+    gc.collect()
+    assert ctx.get_option("live_mats") == live0
+
+
+# ---- 8. a posterior whose block was dropped ----------------------------------------------------------------------------------
+def test_sample_on_a_dropped_block_raises(lp, mode):
+    cf = lp.randprocs.covfuncs
+    prior = lp.GaussianProcess(lp.functions.Zero((1,)), cf.ExpQuad((1,), lengthscales=1.0))
+    X = np.array([[0.0], [0.0], [0.5]])             # duplicated point, negative noise: not positive definite
+    b = lp.randvars.Normal(np.zeros(3), -1e-3 * np.eye(3))
+    x = np.array([[0.1], [0.2]])
+    if mode == "eager":
+        with pytest.raises(np.linalg.LinAlgError):
+            prior.condition_on_observations(np.zeros(3), X, b=b)
+        return
+    child = prior.condition_on_observations(np.zeros(3), X, b=b)
+    g = zero_gen()
+    with pytest.raises(np.linalg.LinAlgError):
+        child.sample(g, x, damping=1e-6)            # the sample is the first use of the factor
+    with pytest.raises(np.linalg.LinAlgError):
+        child.sample(g, x, damping=1e-6)
+
+
+# ---- 9. Normal --------------------------------------------------------------------------------------------------------------
+def test_normal_sample_and_cov_cholesky(lp):
+    rng = np.random.default_rng(41)
+    n = 300
+    B = rng.standard_normal((n, n))
+    A = B @ B.T / n + 0.5 * np.eye(n)
+    mean = rng.standard_normal(n)
+    N = lp.randvars.Normal(mean, A)
+    C = N.cov_cholesky
+    assert C is N.cov_cholesky                       # cached
+    assert np.all(np.triu(C, 1) == 0.0) and np.all(np.diag(C) > 0.0)
+    assert np.max(np.abs(C @ C.T - A)) <= 4 * (n + 1) * U * np.max(np.abs(A))
+    C_o = np.linalg.cholesky(A)
+    kappa = np.linalg.cond(A, 2)
+    assert np.max(np.abs(C - C_o)) <= 2 * kappa * 4 * (n + 1) * U * n * np.max(np.abs(A)) / np.linalg.norm(A, 2) * np.linalg.norm(C_o, 2)
+    g = _Gen(np.random.default_rng(42).standard_normal)
+    draws = N.sample(g, size=(2, 3))
+    assert g.calls == [(2, 3, n)] and draws.shape == (2, 3, n)
+    z = np.random.default_rng(42).standard_normal((2, 3, n))
+    ref = mean + z @ C.T
+    assert np.all(np.abs(draws - ref) <= 2 * (n + 2) * U * (np.abs(z) @ np.abs(C).T + np.abs(mean)))
+    assert np.array_equal(N.sample(zero_gen()), mean)
+    # `u(x).sample(rng, size)`: the reference's other spelling
+    u, post = _scattered_2d(lp, n=200)
+    x = np.random.default_rng(43).uniform(-1, 1, (20, 2))           # a scattered handful: cov(x) is well conditioned (noise 1e-3)
+    Nx = u(x)
+    out = Nx.sample(np.random.default_rng(44), size=4)
+    assert out.shape == (4, 20)
+    Cx = Nx.cov_cholesky
+    assert np.max(np.abs(Cx @ Cx.T - Nx.cov)) <= 4 * 21 * U * np.max(np.abs(Nx.cov))
+    with pytest.raises(np.linalg.LinAlgError):
+        lp.randvars.Normal(np.zeros(3), np.array([[1.0, 2.0, 0.0], [2.0, 1.0, 0.0], [0.0, 0.0, 1.0]])).cov_cholesky
+
+
+# ---- 10. errors ---------------------------------------------------------------------------------------------------------------
+def test_errors(lp):
+    from linpde_gp_amd import _engine, _lib
+    cf = lp.randprocs.covfuncs
+    u, _ = _scattered_2d(lp, n=50)
+    x = np.zeros((4, 2))
+    rng = np.random.default_rng(0)
+    with pytest.raises(ValueError):
+        u.sample(rng, x, damping=-1.0)
+    with pytest.raises(ValueError):
+        u.prior.sample(rng, x, damping=-1.0)
+    with pytest.raises(ValueError):
+        u.sample(rng, np.zeros((5, 3)))               # wrong trailing shape (`predict` raises ValueError on it too)
+    with pytest.raises(ValueError):
+        u.predict(np.zeros((5, 3)))
+    with pytest.raises(ValueError):
+        u.prior.sample(rng, np.zeros((5, 3)))
+    # a covariance that does not factor: the message names the damping
+    unit = lp.GaussianProcess(lp.functions.Zero((1,)), cf.ExpQuad((1,), lengthscales=1.0))
+    with pytest.raises(np.linalg.LinAlgError, match="damping"):
+        unit.sample(rng, np.zeros((3, 1)), damping=0.0)          # three copies of one point, no damping: the second pivot is exactly 0
+    # matrix-free posterior
+    saved = lp.config.matrix_free
+    lp.config.matrix_free = True
+    try:
+        prior = lp.GaussianProcess(lp.functions.Zero((1,)), cf.Matern((1,), nu=2.5, lengthscales=0.5))
+        Xo = np.linspace(-1, 1, 20)[:, None]
+        mf = prior.condition_on_observations(np.sin(Xo[:, 0]), Xo, b=lp.randvars.Normal(np.zeros(20), 1e-2 * np.eye(20)))
+    finally:
+        lp.config.matrix_free = saved
+    assert type(mf).__name__ == "MatrixFreeConditionalGaussianProcess"
+    with pytest.raises(NotImplementedError):
+        mf.sample(rng, Xo)
+    # spawn proxy (no worker group is started: the proxy refuses before it would talk to one)
+    from linpde_gp_amd import _spawn
+    proxy = _spawn.RemoteConditionalGaussianProcess.__new__(_spawn.RemoteConditionalGaussianProcess)
+    proxy._group = type("G", (), {"_conns": None})()
+    with pytest.raises(NotImplementedError):
+        proxy.sample(rng, x)
+    # `lpgp_mat_factor_matmul` on a matrix that is not factored
+    ctx = _ctx()
+    mat = _engine.GramMatrix(ctx, 8)
+    mat.add_block(8)
+    mat.assemble(cf.Zero(()).lower(), _engine.Points(ctx, np.zeros((8, 1))), None, 0, 0)
+    mat.add_dense(0, np.eye(8))
+    with pytest.raises(_lib.LpgpError, match="not \\(fully\\) factored"):
+        mat.factor_matmul(np.ones((8, 2)))
+    with pytest.raises(ValueError):
+        mat.factor_matmul(np.ones((7, 2)))
