@@ -3,6 +3,7 @@
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 #include <rccl/rccl.h>
 
@@ -275,12 +276,12 @@ static int mat_alloc(lpgp_ctx* ctx, lpgp_mat* mat, int64_t cap) {
   if (lc < TILE) lc = TILE;
   lpgp_mat fresh_dims;
   fresh_dims.lr_cap = lr; fresh_dims.lc_cap = lc;
-  void *na = nullptr, *nl = nullptr, *nw = nullptr, *nd = nullptr;
-  int rc = pool_alloc(ctx, &na, mat_bytes_a(&fresh_dims), nullptr);
-  if (rc == 0) rc = pool_alloc(ctx, &nl, mat_bytes_l(cap), nullptr);
-  if (rc == 0) rc = pool_alloc(ctx, &nw, mat_bytes_w(cap), nullptr);
-  if (rc == 0 && ctx->distributed()) rc = pool_alloc(ctx, &nd, mat_bytes_d(ctx, cap), nullptr);
-  if (rc != 0) return rc;
+  DevBuf ba, bl, bw, bd;
+  LPGP_TRY(DevBuf::pool(ctx, mat_bytes_a(&fresh_dims), &ba));
+  LPGP_TRY(DevBuf::pool(ctx, mat_bytes_l(cap), &bl));
+  LPGP_TRY(DevBuf::pool(ctx, mat_bytes_w(cap), &bw));
+  if (ctx->distributed()) LPGP_TRY(DevBuf::pool(ctx, mat_bytes_d(ctx, cap), &bd));
+  double *const na = ba.as(), *const nl = bl.as(), *const nw = bw.as(), *const nd = bd.as();
   const int64_t pn_all = mat->hidden.empty() ? mat->pn : mat->hidden.back().poff + mat->hidden.back().pn;
   if (mat->a && pn_all > 0) {
     const int64_t lru = local_rows(ctx, pn_all), lcu = local_cols(ctx, pn_all);
@@ -301,11 +302,11 @@ static int mat_alloc(lpgp_ctx* ctx, lpgp_mat* mat, int64_t cap) {
   if (!(mat->a && pn_all > 0)) LPGP_HIP(hipMemsetAsync((double*)nw + 2 * cap, 0, sizeof(double), ctx->s_main));       // a new / empty matrix: status clear
   LPGP_HIP(hipStreamSynchronize(ctx->s_main));
   if (mat->a) mat_release(ctx, mat);
-  mat->a = (double*)na;
-  mat->linv = (double*)nl;
-  mat->w = (double*)nw;
-  mat->d_status = reinterpret_cast<int*>((double*)nw + 2 * cap);
-  mat->dblk = (double*)nd;
+  mat->a = (double*)ba.release();
+  mat->linv = (double*)bl.release();
+  mat->w = (double*)bw.release();
+  mat->d_status = reinterpret_cast<int*>(mat->w + 2 * cap);
+  mat->dblk = (double*)bd.release();
   mat->cap = cap;
   mat->lr_cap = lr;
   mat->lc_cap = lc;
@@ -688,7 +689,7 @@ int lpgp_pts_create(lpgp_ctx* ctx, const double* X_host, int64_t n, int32_t d, l
   LPGP_CHECK(ctx && X_host && out, "lpgp_pts_create: null argument");
   LPGP_DEVICE(ctx);
   LPGP_CHECK(n >= 0 && d >= 1 && d <= LPGP_MAXD, "lpgp_pts_create: n=%lld d=%d", (long long)n, d);
-  lpgp_pts* p = new lpgp_pts();
+  std::unique_ptr<lpgp_pts> p(new lpgp_pts());
   p->ctx = ctx;
   p->n = n;
   p->d = d;
@@ -696,7 +697,7 @@ int lpgp_pts_create(lpgp_ctx* ctx, const double* X_host, int64_t n, int32_t d, l
   const size_t bytes = (size_t)p->n_pad * d * sizeof(double);
   const bool recycle = !ctx->distributed() && !ctx->single_stream;
   // the buffer: a recycled one of about the size (lpgp_internal.h: pts_pool), else a new one
-  p->x = nullptr;
+  DevBuf x;
   if (recycle) {
     int best = -1;
     for (int i = 0; i < (int)ctx->pts_pool.size(); ++i) {
@@ -704,18 +705,13 @@ int lpgp_pts_create(lpgp_ctx* ctx, const double* X_host, int64_t n, int32_t d, l
       if (b.bytes >= bytes && b.bytes <= 2 * bytes + 4096 && (best < 0 || b.bytes < ctx->pts_pool[best].bytes)) best = i;
     }
     if (best >= 0) {
-      p->x = (double*)ctx->pts_pool[best].p;
+      x.adopt_raw(ctx->pts_pool[best].p);
       p->bytes = ctx->pts_pool[best].bytes;
       ctx->pts_pool.erase(ctx->pts_pool.begin() + best);
     }
   }
-  if (!p->x) {
-    hipError_t e = hipMalloc(&p->x, bytes);
-    if (e != hipSuccess) {
-      set_error("lpgp_pts_create: device allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-      delete p;
-      return -1;
-    }
+  if (!x.as()) {
+    LPGP_TRY(DevBuf::raw(bytes, &x));
     p->bytes = bytes;
   }
   auto fill = [&](double* soa) {
@@ -723,37 +719,30 @@ int lpgp_pts_create(lpgp_ctx* ctx, const double* X_host, int64_t n, int32_t d, l
     for (int64_t i = 0; i < n; ++i)
       for (int j = 0; j < d; ++j) soa[(size_t)j * p->n_pad + i] = X_host[i * d + j];
   };
-  hipError_t e = hipSuccess;
   if (recycle && bytes <= lpgp_ctx::PTS_SLOT_BYTES) {
     // small: through the next pinned slot, on the panel stream, no wait (the slot is reused after its copy has completed)
     lpgp_ctx::PtsSlot& sl = ctx->pts_ring[ctx->pts_next];
     ctx->pts_next = (ctx->pts_next + 1) % lpgp_ctx::PTS_SLOTS;
     if (!sl.h) {
-      e = hipHostMalloc(&sl.h, lpgp_ctx::PTS_SLOT_BYTES, hipHostMallocDefault);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
+      LPGP_HIP(hipHostMalloc(&sl.h, lpgp_ctx::PTS_SLOT_BYTES, hipHostMallocDefault));
+      LPGP_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     } else if (sl.used) {
-      e = hipEventSynchronize(sl.done);
+      LPGP_HIP(hipEventSynchronize(sl.done));
     }
-    if (e == hipSuccess) {
-      fill((double*)sl.h);
-      e = hipMemcpyAsync(p->x, sl.h, bytes, hipMemcpyHostToDevice, ctx->s_main);
-    }
-    if (e == hipSuccess) e = hipEventRecord(sl.done, ctx->s_main);
-    if (e == hipSuccess) sl.used = true;
+    fill((double*)sl.h);
+    LPGP_HIP(hipMemcpyAsync(x.as(), sl.h, bytes, hipMemcpyHostToDevice, ctx->s_main));
+    LPGP_HIP(hipEventRecord(sl.done, ctx->s_main));
+    sl.used = true;
   } else {
     std::vector<double> soa((size_t)p->n_pad * d);
     fill(soa.data());
+    StreamDrain drain{ctx->s_main};
     // (a recycled buffer may still be read by kernels on the panel stream: the copy is ordered behind them there)
-    e = hipMemcpyAsync(p->x, soa.data(), bytes, hipMemcpyHostToDevice, ctx->s_main);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_main);
+    LPGP_HIP(hipMemcpyAsync(x.as(), soa.data(), bytes, hipMemcpyHostToDevice, ctx->s_main));
+    LPGP_TRY(drain.wait());
   }
-  if (e != hipSuccess) {
-    set_error("lpgp_pts_create: upload: %s", hipGetErrorString(e));
-    (void)hipFree(p->x);
-    delete p;
-    return -1;
-  }
-  *out = p;
+  p->x = (double*)x.release();
+  *out = p.release();
   return 0;
 }
 
@@ -774,7 +763,7 @@ int lpgp_pts_destroy(lpgp_pts* p) {
 int lpgp_mat_create(lpgp_ctx* ctx, int64_t capacity_hint, lpgp_mat** out) {
   LPGP_CHECK(ctx && out, "lpgp_mat_create: null argument");
   LPGP_DEVICE(ctx);
-  lpgp_mat* m = new lpgp_mat();
+  std::unique_ptr<lpgp_mat> m(new lpgp_mat());
   m->ctx = ctx;
   m->cap = 0;
   m->a = m->linv = m->w = nullptr;
@@ -782,13 +771,9 @@ int lpgp_mat_create(lpgp_ctx* ctx, int64_t capacity_hint, lpgp_mat** out) {
   m->has_w = 0;
   m->has_r = 0;
   int64_t cap = round_up(capacity_hint > 0 ? capacity_hint : 8 * TILE, TILE);      // (no hint: room for 1 024 rows, 8 MB -- the reference's own problem sizes start here)
-  int rc = mat_alloc(ctx, m, cap);
-  if (rc != 0) {
-    delete m;
-    return rc;
-  }
+  LPGP_TRY(mat_alloc(ctx, m.get(), cap));
   ++ctx->live_mats;
-  *out = m;
+  *out = m.release();
   return 0;
 }
 
@@ -884,6 +869,12 @@ int lpgp_mat_set_view(lpgp_ctx* ctx, lpgp_mat* mat, int32_t nblocks) {
   return 0;
 }
 
+// deleter of a handle that is still under construction but already owns device memory and is counted in live_mats
+struct LPGP_LOCAL Destroy {
+  void operator()(lpgp_mat* m) const { (void)lpgp_mat_destroy(m); }
+  void operator()(lpgp_rhs* r) const { (void)lpgp_rhs_destroy(r); }
+};
+
 int lpgp_mat_clone(lpgp_ctx* ctx, const lpgp_mat* src, int32_t nblocks, lpgp_mat** out) {
   LPGP_CHECK(ctx && src && out, "lpgp_mat_clone: null argument");
   LPGP_DEVICE(ctx);
@@ -896,24 +887,18 @@ int lpgp_mat_clone(lpgp_ctx* ctx, const lpgp_mat* src, int32_t nblocks, lpgp_mat
   const lpgp_block& last = all[nblocks - 1];
   const int64_t pn = last.poff + last.pn;
   LPGP_CHECK(pn <= fact_all, "lpgp_mat_clone: block %d is not factored yet", nblocks - 1);
-  lpgp_mat* m = nullptr;
-  int rc = lpgp_mat_create(ctx, pn, &m);
-  if (rc != 0) return rc;
-  hipError_t e = hipMemcpy2DAsync(m->a, (size_t)m->lr_cap * sizeof(double), src->a, (size_t)src->lr_cap * sizeof(double),
-                                  (size_t)pn * sizeof(double), (size_t)pn, hipMemcpyDeviceToDevice, ctx->s_main);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(m->linv, src->linv, (size_t)pn * TILE * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_main);
-  if (e != hipSuccess) {
-    set_error("lpgp_mat_clone: %s", hipGetErrorString(e));
-    lpgp_mat_destroy(m);
-    return -1;
-  }
+  lpgp_mat* created = nullptr;
+  LPGP_TRY(lpgp_mat_create(ctx, pn, &created));
+  std::unique_ptr<lpgp_mat, Destroy> m(created);
+  LPGP_HIP(hipMemcpy2DAsync(m->a, (size_t)m->lr_cap * sizeof(double), src->a, (size_t)src->lr_cap * sizeof(double),
+                            (size_t)pn * sizeof(double), (size_t)pn, hipMemcpyDeviceToDevice, ctx->s_main));
+  LPGP_HIP(hipMemcpyAsync(m->linv, src->linv, (size_t)pn * TILE * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main));
+  LPGP_HIP(hipStreamSynchronize(ctx->s_main));
   m->blocks.assign(all.begin(), all.begin() + nblocks);
   m->n = last.off + last.n;
   m->pn = pn;
   m->pn_fact = pn;
-  *out = m;
+  *out = m.release();
   return 0;
 }
 
@@ -973,12 +958,10 @@ int lpgp_gram_assemble_grid(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups
   LPGP_CHECK(n0 == Bi.n && n1 == Bj.n, "lpgp_gram_assemble_grid: grids have %lld x %lld points, block (%d,%d) is %lld x %lld",
              (long long)n0, (long long)n1, bi, bj, (long long)Bi.n, (long long)Bj.n);
   const size_t wd = kron_work_doubles(D, n0d, n1d);
-  void* work = nullptr;
-  if (pool_alloc(ctx, &work, wd * sizeof(double), nullptr) != 0) return -1;
-  int rc = launch_assemble_kron(ctx, ctx->s_main, kd, ngroups, f0, n0d, f1, n1d, (double*)work, wd, mat->a, mat->lr_cap,
-                                Bi.poff, Bj.poff, sym ? 1 : 0, mat_layout(ctx));
-  pool_free(ctx, work, wd * sizeof(double));       // reuse is ordered behind this launch on the main stream
-  return rc;
+  DevBuf work;                                     // (reuse is ordered behind the launch on the main stream)
+  LPGP_TRY(DevBuf::pool(ctx, wd * sizeof(double), &work));
+  return launch_assemble_kron(ctx, ctx->s_main, kd, ngroups, f0, n0d, f1, n1d, work.as(), wd, mat->a, mat->lr_cap,
+                              Bi.poff, Bj.poff, sym ? 1 : 0, mat_layout(ctx));
 }
 
 int lpgp_mat_add_diag(lpgp_ctx* ctx, lpgp_mat* mat, int32_t bi, const double* v_host, double scalar) {
@@ -1024,6 +1007,17 @@ static int dist_fail(lpgp_ctx* ctx, int rc) {
     ctx->dist_broken = 1;
   }
   return rc;
+}
+
+// V <- L^{-1} V and V <- L^{-T} V for the whole view of `mat`: streamed over the ranks of a multi-GPU job (a failure of one
+// rank aborts the communicator), blocked on a single GPU
+static int solve_lower(lpgp_ctx* ctx, lpgp_mat* mat, double* v, int64_t ldv, int64_t m_pad) {
+  return ctx->distributed() ? dist_fail(ctx, trsm_lower_dist(ctx, mat, mat->pn / TILE, v, ldv, m_pad))
+                            : trsm_lower_blocked(ctx, mat, mat->pn / TILE, v, ldv, m_pad);
+}
+static int solve_lower_t(lpgp_ctx* ctx, lpgp_mat* mat, double* v, int64_t ldv, int64_t m_pad) {
+  return ctx->distributed() ? dist_fail(ctx, trsm_lower_t_dist(ctx, mat, mat->pn / TILE, v, ldv, m_pad))
+                            : trsm_lower_t_blocked(ctx, mat, mat->pn / TILE, v, ldv, m_pad);
 }
 
 int lpgp_mat_to_host(lpgp_ctx* ctx, lpgp_mat* mat, int32_t what, double* out_host) {
@@ -1299,29 +1293,34 @@ int lpgp_potrs(lpgp_ctx* ctx, lpgp_mat* mat, double* b_host, int64_t nrhs) {
   LPGP_MAT_ALIVE(mat, "lpgp_potrs");
   LPGP_CHECK(mat->pn_fact == mat->pn && mat->pn > 0, "lpgp_potrs: matrix is not factored");
   const int64_t pn = mat->pn, n = mat->n, m_pad = round_up(nrhs, TILE);
-  double* dv = nullptr;
-  LPGP_HIP(hipMalloc(&dv, (size_t)pn * m_pad * sizeof(double)));
   std::vector<double> hp((size_t)pn * m_pad, 0.0);
+  DevBuf dv;                                     // (released by hipFree, which waits for the device: behind hp, so in front of it on the way out)
+  LPGP_TRY(DevBuf::raw(hp.size() * sizeof(double), &dv));
   for (int64_t j = 0; j < nrhs; ++j) scatter_padded(mat, b_host + j * n, hp.data() + j * pn);
-  int rc = 0;
-  do {
-    if (hipMemcpyAsync(dv, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->s_main) != hipSuccess) { rc = -1; break; }
-    rc = ctx->distributed() ? dist_fail(ctx, trsm_lower_dist(ctx, mat, pn / TILE, dv, pn, m_pad)) : trsm_lower_blocked(ctx, mat, pn / TILE, dv, pn, m_pad);
-    if (rc) break;
-    rc = ctx->distributed() ? dist_fail(ctx, trsm_lower_t_dist(ctx, mat, pn / TILE, dv, pn, m_pad)) : trsm_lower_t_blocked(ctx, mat, pn / TILE, dv, pn, m_pad);
-    if (rc) break;
-    // (wait FIRST, watched: the copy into pageable memory below is synchronous and would wait unwatched behind a streamed
-    //  solve whose peer is gone)
-    if ((rc = sync_stream(ctx, ctx->s_main)) != 0) break;
-    if (hipMemcpyAsync(hp.data(), dv, hp.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess) { rc = -1; break; }
-    rc = sync_stream(ctx, ctx->s_main);          // (behind a streamed solve: polls, so that a failed peer cannot block this rank)
-  } while (0);
-  (void)hipFree(dv);
-  if (rc != 0) {
-    if (rc == -1) set_error("lpgp_potrs: HIP failure (%s)", hipGetErrorString(hipGetLastError()));
-    return rc;
-  }
+  LPGP_HIP(hipMemcpyAsync(dv.as(), hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
+  LPGP_TRY(solve_lower(ctx, mat, dv.as(), pn, m_pad));
+  LPGP_TRY(solve_lower_t(ctx, mat, dv.as(), pn, m_pad));
+  // (wait FIRST, watched: the copy into pageable memory below is synchronous and would wait unwatched behind a streamed
+  //  solve whose peer is gone)
+  LPGP_TRY(sync_stream(ctx, ctx->s_main));
+  LPGP_HIP(hipMemcpyAsync(hp.data(), dv.as(), hp.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
+  LPGP_TRY(sync_stream(ctx, ctx->s_main));       // (behind a streamed solve: polls, so that a failed peer cannot block this rank)
   for (int64_t j = 0; j < nrhs; ++j) gather_padded(mat, hp.data() + j * pn, b_host + j * n);
+  return 0;
+}
+
+// multi-GPU form of lpgp_solve_weights: the factor is streamed; the vector rides as column 0 of a 128-column block on every
+// rank (all ranks end with the same weights, no further communication)
+static int solve_weights_dist(lpgp_ctx* ctx, lpgp_mat* mat) {
+  const int64_t pn = mat->pn;
+  const size_t vb = (size_t)pn * TILE * sizeof(double);
+  DevBuf dv;
+  LPGP_TRY(DevBuf::pool(ctx, vb, &dv));
+  LPGP_HIP(hipMemsetAsync(dv.as(), 0, vb, ctx->s_main));
+  LPGP_HIP(hipMemcpyAsync(dv.as(), mat->w, (size_t)pn * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main));
+  LPGP_TRY(solve_lower(ctx, mat, dv.as(), pn, TILE));
+  LPGP_TRY(solve_lower_t(ctx, mat, dv.as(), pn, TILE));
+  LPGP_HIP(hipMemcpyAsync(mat->w, dv.as(), (size_t)pn * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main));
   return 0;
 }
 
@@ -1331,37 +1330,23 @@ int lpgp_solve_weights(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, doubl
   LPGP_MAT_ALIVE(mat, "lpgp_solve_weights");
   LPGP_CHECK(mat->pn_fact == mat->pn && mat->pn > 0, "lpgp_solve_weights: matrix is not factored");
   const int64_t pn = mat->pn;
-  int rc = ensure_tmp(ctx, pn + 2);                 // (+ 2: the ticket words of the resident solve, trsv.hip)
-  if (rc != 0) return rc;
+  LPGP_TRY(ensure_tmp(ctx, pn + 2));                // (+ 2: the ticket words of the resident solve, trsv.hip)
   // through pinned staging: the residual up and the weights + the solve's status word back are asynchronous copies, ONE wait
   // (round 6; until then two blocking copies through pageable memory around 2 x T dependent launches)
-  rc = ensure_stage(ctx, pn);
-  if (rc != 0) return rc;
+  LPGP_TRY(ensure_stage(ctx, pn));
   double* const hs = ctx->h_stage;
   int* const hinfo = ctx->h_info_pinned + 6;
   scatter_padded(mat, r_host, hs);
   LPGP_HIP(hipMemcpyAsync(mat->w, hs, (size_t)pn * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
   if (ctx->distributed()) {
-    // multi-GPU: the factor is streamed; the vector rides as column 0 of a 128-column block on every rank (all
-    // ranks end with the same weights, no further communication)
-    void* pv = nullptr;
-    const size_t vb = (size_t)pn * TILE * sizeof(double);
-    if (pool_alloc(ctx, &pv, vb, nullptr) != 0) return dist_fail(ctx, -1);      // (the peers are about to enter the streamed solve)
-    double* dv = (double*)pv;
-    hipError_t e = hipMemsetAsync(dv, 0, vb, ctx->s_main);
-    if (e == hipSuccess) e = hipMemcpyAsync(dv, mat->w, (size_t)pn * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main);
-    rc = dist_fail(ctx, e == hipSuccess ? trsm_lower_dist(ctx, mat, pn / TILE, dv, pn, TILE) : -1);
-    if (rc == 0) rc = dist_fail(ctx, trsm_lower_t_dist(ctx, mat, pn / TILE, dv, pn, TILE));
-    if (rc == 0 && hipMemcpyAsync(mat->w, dv, (size_t)pn * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main) != hipSuccess) rc = dist_fail(ctx, -1);
-    pool_free(ctx, pv, vb);
+    LPGP_TRY(dist_fail(ctx, solve_weights_dist(ctx, mat)));     // (any failure: the peers are inside the streamed solve, or about to enter it)
     *hinfo = 0;
+    LPGP_TRY(sync_stream(ctx, ctx->s_main));      // (watched: a copy behind a streamed solve whose peer is gone would wait for ever)
   } else {
     LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), ctx->s_main));
-    rc = solve_vec(ctx, mat, pn / TILE, mat->w, ctx->d_tmp, ctx->d_info);
-    if (rc == 0) LPGP_HIP(hipMemcpyAsync(hinfo, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->s_main));
+    LPGP_TRY(solve_vec(ctx, mat, pn / TILE, mat->w, ctx->d_tmp, ctx->d_info));
+    LPGP_HIP(hipMemcpyAsync(hinfo, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->s_main));
   }
-  if (rc != 0) return rc;
-  if (ctx->distributed()) LPGP_TRY(sync_stream(ctx, ctx->s_main));      // (watched: a copy behind a streamed solve whose peer is gone would wait for ever)
   LPGP_HIP(hipMemcpyAsync(hs, mat->w, (size_t)pn * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
   LPGP_TRY(sync_stream(ctx, ctx->s_main));
   LPGP_CHECK(*hinfo >= 0, "resident single-vector solve: a hand-over between workgroups timed out (device status %d); set LPGP_TRSV_RESIDENT=0", *hinfo);
@@ -1435,21 +1420,27 @@ __global__ void rhs_pad_kernel(double* v, int64_t ld, int64_t m, int64_t m_pad, 
   }
 }
 
+// a right-hand side of ld rows x m columns: allocated (contents undefined) and counted in live_mats
+static int rhs_new(lpgp_ctx* ctx, int64_t ld, int64_t m, std::unique_ptr<lpgp_rhs, Destroy>* out) {
+  const int64_t m_pad = round_up(m + 1, TILE);       // at least one spare column (see lpgp_predict)
+  DevBuf v;
+  LPGP_TRY(DevBuf::pool(ctx, (size_t)ld * m_pad * sizeof(double), &v));
+  lpgp_rhs* r = new lpgp_rhs();
+  r->ctx = ctx;
+  r->ld = ld;
+  r->m = m;
+  r->m_pad = m_pad;
+  r->v = (double*)v.release();
+  ++ctx->live_mats;
+  out->reset(r);
+  return 0;
+}
+
 int lpgp_rhs_create(lpgp_ctx* ctx, const lpgp_mat* mat, int64_t m, lpgp_rhs** out) {
   LPGP_CHECK(ctx && mat && out && m >= 1, "lpgp_rhs_create: bad argument");
   LPGP_DEVICE(ctx);
-  lpgp_rhs* r = new lpgp_rhs();
-  r->ctx = ctx;
-  r->ld = mat->pn;
-  r->m = m;
-  r->m_pad = round_up(m + 1, TILE);       // at least one spare column (see lpgp_predict)
-  r->v = nullptr;
-  void* pv = nullptr;
-  if (pool_alloc(ctx, &pv, (size_t)r->ld * r->m_pad * sizeof(double), nullptr) != 0) {
-    delete r;
-    return -1;
-  }
-  r->v = (double*)pv;
+  std::unique_ptr<lpgp_rhs, Destroy> r;
+  LPGP_TRY(rhs_new(ctx, mat->pn, m, &r));
   // lpgp_cross_assemble writes every logical row of every logical column: only the spare columns and
   // the rows of the blocks' padding tails have to be cleared (c3: 17 MB instead of 571 MB per prediction)
   {
@@ -1474,17 +1465,10 @@ int lpgp_rhs_create(lpgp_ctx* ctx, const lpgp_mat* mat, int64_t m, lpgp_rhs** ou
         if (jb.nj == RHS_PAD_JOBS) flush();
       }
     if (jb.nj > 0 || spare) flush();
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("lpgp_rhs_create: %s", hipGetErrorString(e));
-      pool_free(ctx, r->v, (size_t)r->ld * r->m_pad * sizeof(double));
-      delete r;
-      return -1;
-    }
+    LPGP_HIP(hipGetLastError());
   }
   r->assembled.assign(mat->blocks.size(), 0);
-  ++ctx->live_mats;
-  *out = r;
+  *out = r.release();
   return 0;
 }
 
@@ -1567,12 +1551,31 @@ int lpgp_trsm_lower(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_rhs* V) {
   LPGP_DEVICE(ctx);
   LPGP_MAT_ALIVE(mat, "lpgp_trsm_lower");
   LPGP_CHECK(mat->pn_fact == mat->pn && V->ld == mat->pn, "lpgp_trsm_lower: matrix not factored or size mismatch");
-  int rc = rhs_clear_unassembled(ctx, mat, V);
-  if (rc != 0) return rc;
-  rc = ctx->distributed() ? dist_fail(ctx, trsm_lower_dist(ctx, mat, mat->pn / TILE, V->v, V->ld, V->m_pad))
-                          : trsm_lower_blocked(ctx, mat, mat->pn / TILE, V->v, V->ld, V->m_pad);
-  if (rc != 0) return rc;
+  LPGP_TRY(rhs_clear_unassembled(ctx, mat, V));
+  LPGP_TRY(solve_lower(ctx, mat, V->v, V->ld, V->m_pad));
   LPGP_TRY(sync_stream(ctx, ctx->s_main));
+  return 0;
+}
+
+// The read-back tail of a prediction: the column reductions of K (dots with `dot`, if given; sums of squares, if `squares`) into
+// d_tmp, ONE asynchronous copy of them into the pinned staging buffer -- and one of the matrix's status word into `h_status`,
+// if given -- ONE watched wait, then  mean = prior_mean + dots,  var = kxx - squares.
+static int reduce_read_back(lpgp_ctx* ctx, const lpgp_mat* mat, const lpgp_rhs* K, const double* dot, bool squares, const double* prior_mean_host,
+                            const double* kxx_host, double* mean_host, double* var_host, int* h_status) {
+  const int64_t m = K->m, sq0 = dot && squares ? K->m_pad : 0;
+  if (dot && squares)
+    hipLaunchKernelGGL(col_reduce2_kernel, dim3((unsigned)m), dim3(256), 0, ctx->s_main, K->v, K->ld, mat->pn, dot, ctx->d_tmp, ctx->d_tmp + sq0);
+  else
+    hipLaunchKernelGGL(col_reduce_kernel, dim3((unsigned)m), dim3(256), 0, ctx->s_main, K->v, K->ld, mat->pn, dot, ctx->d_tmp);
+  LPGP_HIP(hipGetLastError());
+  double* const hs = ctx->h_stage;
+  LPGP_HIP(hipMemcpyAsync(hs, ctx->d_tmp, (size_t)(sq0 + m) * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
+  if (h_status) LPGP_HIP(hipMemcpyAsync(h_status, mat->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->s_main));
+  LPGP_TRY(sync_stream(ctx, ctx->s_main));
+  if (dot)
+    for (int64_t j = 0; j < m; ++j) mean_host[j] = (prior_mean_host ? prior_mean_host[j] : 0.0) + hs[j];
+  if (squares)
+    for (int64_t j = 0; j < m; ++j) var_host[j] = kxx_host[j] - hs[sq0 + j];
   return 0;
 }
 
@@ -1582,16 +1585,11 @@ int lpgp_predict(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_rhs* K, const double* prior_
   LPGP_DEVICE(ctx);
   LPGP_MAT_ALIVE(mat, "lpgp_predict");
   LPGP_CHECK(mat->pn_fact == mat->pn && K->ld == mat->pn, "lpgp_predict: matrix not factored or size mismatch");
-  const int64_t m = K->m;
-  int rc = ensure_tmp(ctx, 2 * K->m_pad);
-  if (rc != 0) return rc;
-  rc = rhs_clear_unassembled(ctx, mat, K);
-  if (rc != 0) return rc;
+  LPGP_TRY(ensure_tmp(ctx, 2 * K->m_pad));
+  LPGP_TRY(rhs_clear_unassembled(ctx, mat, K));
   // results come back through pinned staging: the copy is asynchronous (the one wait polls, so that a failed peer of a
   // multi-GPU job cannot block this rank inside a copy) and mean + variance are ONE copy, not two blocking round trips
-  rc = ensure_stage(ctx, 2 * K->m_pad);
-  if (rc != 0) return rc;
-  double* const hs = ctx->h_stage;
+  LPGP_TRY(ensure_stage(ctx, 2 * K->m_pad));
   // Mean and variance together: the variance needs V = L^{-1} K_Xx anyway, and
   //   K_xX G^{-1} r = V^T z  with  z = L^{-1} r,
   // so no representer weights are needed: the residual rides through the blocked solve as
@@ -1602,37 +1600,15 @@ int lpgp_predict(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_rhs* K, const double* prior_
   if (mean_host && !via_z) {
     LPGP_CHECK(mat->has_w, "lpgp_predict: representer weights not computed (call lpgp_solve_weights%s)",
                var_host ? " or lpgp_mat_set_residual" : "");
-    hipLaunchKernelGGL(col_reduce_kernel, dim3((unsigned)m), dim3(256), 0, ctx->s_main, K->v, K->ld, mat->pn,
-                       (const double*)mat->w, ctx->d_tmp);
-    LPGP_HIP(hipGetLastError());
-    LPGP_HIP(hipMemcpyAsync(hs, ctx->d_tmp, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
-    LPGP_TRY(sync_stream(ctx, ctx->s_main));
-    for (int64_t j = 0; j < m; ++j) mean_host[j] = (prior_mean_host ? prior_mean_host[j] : 0.0) + hs[j];
+    LPGP_TRY(reduce_read_back(ctx, mat, K, mat->w, false, prior_mean_host, nullptr, mean_host, nullptr, nullptr));
   }
   if (var_host) {
     LPGP_CHECK(kxx_host != nullptr, "lpgp_predict: kxx_host required for the variance");
-    double* zcol = K->v + (int64_t)m * K->ld;
+    double* zcol = K->v + (int64_t)K->m * K->ld;
     if (via_z)
       LPGP_HIP(hipMemcpyAsync(zcol, mat->r(), (size_t)mat->pn * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main));
-    rc = ctx->distributed() ? dist_fail(ctx, trsm_lower_dist(ctx, mat, mat->pn / TILE, K->v, K->ld, K->m_pad))
-                            : trsm_lower_blocked(ctx, mat, mat->pn / TILE, K->v, K->ld, K->m_pad);
-    if (rc != 0) return rc;
-    if (via_z) {
-      hipLaunchKernelGGL(col_reduce2_kernel, dim3((unsigned)m), dim3(256), 0, ctx->s_main, K->v, K->ld, mat->pn,
-                         (const double*)zcol, ctx->d_tmp, ctx->d_tmp + K->m_pad);
-      LPGP_HIP(hipGetLastError());
-      LPGP_HIP(hipMemcpyAsync(hs, ctx->d_tmp, (size_t)(K->m_pad + m) * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
-      LPGP_TRY(sync_stream(ctx, ctx->s_main));
-      for (int64_t j = 0; j < m; ++j) mean_host[j] = (prior_mean_host ? prior_mean_host[j] : 0.0) + hs[j];
-      for (int64_t j = 0; j < m; ++j) var_host[j] = kxx_host[j] - hs[K->m_pad + j];
-    } else {
-      hipLaunchKernelGGL(col_reduce_kernel, dim3((unsigned)m), dim3(256), 0, ctx->s_main, K->v, K->ld, mat->pn,
-                         (const double*)nullptr, ctx->d_tmp);
-      LPGP_HIP(hipGetLastError());
-      LPGP_HIP(hipMemcpyAsync(hs, ctx->d_tmp, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
-      LPGP_TRY(sync_stream(ctx, ctx->s_main));
-      for (int64_t j = 0; j < m; ++j) var_host[j] = kxx_host[j] - hs[j];
-    }
+    LPGP_TRY(solve_lower(ctx, mat, K->v, K->ld, K->m_pad));
+    LPGP_TRY(reduce_read_back(ctx, mat, K, via_z ? zcol : nullptr, true, prior_mean_host, kxx_host, mean_host, var_host, nullptr));
   }
   return 0;
 }
@@ -1646,18 +1622,14 @@ int lpgp_potrf_predict(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_rhs* K, const double* 
   LPGP_CHECK(mat->hidden.empty(), "lpgp_potrf_predict: a strict prefix of the blocks is in view");
   LPGP_CHECK(K->ld == mat->pn && mat->pn > 0, "lpgp_potrf_predict: right-hand side built for another matrix size");
   LPGP_CHECK(mat->has_r, "lpgp_potrf_predict: no residual resident (lpgp_mat_set_residual)");
-  const int64_t m = K->m;
-  int rc = ensure_tmp(ctx, 2 * K->m_pad);
-  if (rc != 0) return rc;
-  rc = ensure_stage(ctx, 2 * K->m_pad);
-  if (rc != 0) return rc;
-  rc = rhs_clear_unassembled(ctx, mat, K);
-  if (rc != 0) return rc;
-  double* zcol = K->v + (int64_t)m * K->ld;             // the residual rides as the spare column: z = L^{-1} r, mean = V^T z
+  LPGP_TRY(ensure_tmp(ctx, 2 * K->m_pad));
+  LPGP_TRY(ensure_stage(ctx, 2 * K->m_pad));
+  LPGP_TRY(rhs_clear_unassembled(ctx, mat, K));
+  double* zcol = K->v + (int64_t)K->m * K->ld;          // the residual rides as the spare column: z = L^{-1} r, mean = V^T z
   LPGP_HIP(hipMemcpyAsync(zcol, mat->r(), (size_t)mat->pn * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main));
   const bool fresh = mat->pn_fact < mat->pn;
   ctx->d_info_cur = mat->d_status;
-  rc = potrf_predict_blocked(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, K->v, K->ld, K->m_pad);
+  const int rc = potrf_predict_blocked(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, K->v, K->ld, K->m_pad);
   if (rc != 0) {
     if (fresh) mat->poisoned = 1;    // (partly factored in place with pn_fact unchanged -- a retry would factor a half-factored matrix)
     return rc;
@@ -1668,24 +1640,14 @@ int lpgp_potrf_predict(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_rhs* K, const double* 
     mat->has_w = 0;
   }
   mat->status_known = 0;
-  hipLaunchKernelGGL(col_reduce2_kernel, dim3((unsigned)m), dim3(256), 0, ctx->s_main, K->v, K->ld, mat->pn, (const double*)zcol, ctx->d_tmp,
-                     ctx->d_tmp + K->m_pad);
-  LPGP_HIP(hipGetLastError());
   // mean, variance and the status word of the factorisation come back together: two asynchronous copies into pinned memory,
   // ONE wait (until round 5: two blocking copies into pageable memory here and a third in lpgp_mat_check, ~25 us each --
   // a tenth of a step of the reference's own problem sizes)
-  double* const hs = ctx->h_stage;
   int* const hinfo = ctx->h_info_pinned + 4;
-  LPGP_HIP(hipMemcpyAsync(hs, ctx->d_tmp, (size_t)(K->m_pad + m) * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
-  LPGP_HIP(hipMemcpyAsync(hinfo, mat->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->s_main));
-  LPGP_TRY(sync_stream(ctx, ctx->s_main));
+  LPGP_TRY(reduce_read_back(ctx, mat, K, zcol, true, prior_mean_host, kxx_host, mean_host, var_host, hinfo));
   if (mat->unchecked) {
     mat->status_value = *hinfo;
     mat->status_known = 1;
-  }
-  for (int64_t j = 0; j < m; ++j) {
-    mean_host[j] = (prior_mean_host ? prior_mean_host[j] : 0.0) + hs[j];
-    var_host[j] = kxx_host[j] - hs[K->m_pad + j];
   }
   return 0;
 }
@@ -1695,18 +1657,17 @@ int lpgp_rhs_inner(lpgp_ctx* ctx, lpgp_rhs* A, lpgp_rhs* B, double* out_host) {
   LPGP_DEVICE(ctx);
   LPGP_CHECK(A->ld == B->ld, "lpgp_rhs_inner: row mismatch");
   const int64_t ma = A->m_pad, mb = B->m_pad;
-  double* dc = nullptr;
-  LPGP_HIP(hipMalloc(&dc, (size_t)ma * mb * sizeof(double)));
+  std::vector<double> h((size_t)ma * mb);
+  DevBuf dc;
+  LPGP_TRY(DevBuf::raw(h.size() * sizeof(double), &dc));
+  StreamDrain drain{ctx->s_main};
   GemmArgs g;
-  g.A = A->v; g.B = B->v; g.C = dc; g.lda = A->ld; g.ldb = B->ld; g.ldc = ma;
+  g.A = A->v; g.B = B->v; g.C = dc.as(); g.lda = A->ld; g.ldb = B->ld; g.ldc = ma;
   g.mt = (int)(ma / TILE); g.nt = (int)(mb / TILE); g.k = (int)A->ld; g.alpha = 1.0; g.beta = 0.0;
   g.tri = 0;
-  int rc = launch_gemm(ctx, ctx->s_main, 1, 1, g, LPGP_K_GEMM);
-  std::vector<double> h((size_t)ma * mb);
-  if (rc == 0 && hipMemcpyAsync(h.data(), dc, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess) rc = -1;
-  if (rc == 0 && hipStreamSynchronize(ctx->s_main) != hipSuccess) rc = -1;
-  (void)hipFree(dc);
-  if (rc != 0) return rc;
+  LPGP_TRY(launch_gemm(ctx, ctx->s_main, 1, 1, g, LPGP_K_GEMM));
+  LPGP_HIP(hipMemcpyAsync(h.data(), dc.as(), h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
+  LPGP_TRY(drain.wait());
   for (int64_t i = 0; i < A->m; ++i)
     for (int64_t j = 0; j < B->m; ++j) out_host[i * B->m + j] = h[(size_t)(i + j * ma)];
   return 0;
@@ -1718,51 +1679,27 @@ int lpgp_rhs_matmul(lpgp_ctx* ctx, const lpgp_rhs* A, const double* B_host, int6
   LPGP_CHECK(!ctx->distributed(), "lpgp_rhs_matmul: single GPU only");
   // the result shares A's row layout whatever the matrix A was created for has become since (a posterior is a value: later
   // conditionings extend the shared matrix); every element of it is written by the product (beta = 0): no clearing
-  lpgp_rhs* out = new lpgp_rhs();
-  out->ctx = ctx;
-  out->ld = A->ld;
-  out->m = m;
-  out->m_pad = round_up(m + 1, TILE);
-  out->v = nullptr;
-  {
-    void* pv = nullptr;
-    if (pool_alloc(ctx, &pv, (size_t)out->ld * out->m_pad * sizeof(double), nullptr) != 0) {
-      delete out;
-      return -1;
-    }
-    out->v = (double*)pv;
-  }
+  std::unique_ptr<lpgp_rhs, Destroy> out;
+  LPGP_TRY(rhs_new(ctx, A->ld, m, &out));
   out->assembled.assign(A->assembled.size(), 1);
-  ++ctx->live_mats;
   const int64_t ka = A->m_pad, mp = out->m_pad;
   // B, zero-padded to (columns of A incl. its spare ones) x (columns of out incl. its spare ones), column-major: the spare
   // columns of A meet zero rows, the spare columns of out come out as zeros
   std::vector<double> hb((size_t)ka * mp, 0.0);
   for (int64_t kk = 0; kk < A->m; ++kk)
     for (int64_t j = 0; j < m; ++j) hb[(size_t)(kk + j * ka)] = B_host[kk * m + j];
-  void* pb = nullptr;
   const size_t bb = hb.size() * sizeof(double);
-  if (pool_alloc(ctx, &pb, bb, nullptr) != 0) {
-    (void)lpgp_rhs_destroy(out);
-    return -1;
-  }
-  int rc = 0;
-  if (hipMemcpyAsync(pb, hb.data(), bb, hipMemcpyHostToDevice, ctx->s_main) != hipSuccess) rc = -1;
-  if (rc == 0) {
-    GemmArgs g;
-    g.A = A->v; g.B = (const double*)pb; g.C = out->v; g.lda = A->ld; g.ldb = ka; g.ldc = out->ld;
-    g.mt = (int)(out->ld / TILE); g.nt = (int)(mp / TILE); g.k = (int)ka; g.alpha = 1.0; g.beta = 0.0;
-    g.tri = 0;
-    rc = launch_gemm(ctx, ctx->s_main, 0, 1, g, LPGP_K_GEMM);
-  }
-  if (rc == 0 && hipStreamSynchronize(ctx->s_main) != hipSuccess) rc = -1;      // (the staging vector is borrowed by the copy)
-  pool_free(ctx, pb, bb);
-  if (rc != 0) {
-    if (rc == -1) set_error("lpgp_rhs_matmul: HIP failure (%s)", hipGetErrorString(hipGetLastError()));
-    (void)lpgp_rhs_destroy(out);
-    return rc;
-  }
-  *out_new = out;
+  DevBuf b;
+  LPGP_TRY(DevBuf::pool(ctx, bb, &b));
+  StreamDrain drain{ctx->s_main};                // (the staging vector is borrowed by the copy)
+  LPGP_HIP(hipMemcpyAsync(b.as(), hb.data(), bb, hipMemcpyHostToDevice, ctx->s_main));
+  GemmArgs g;
+  g.A = A->v; g.B = b.as(); g.C = out->v; g.lda = A->ld; g.ldb = ka; g.ldc = out->ld;
+  g.mt = (int)(out->ld / TILE); g.nt = (int)(mp / TILE); g.k = (int)ka; g.alpha = 1.0; g.beta = 0.0;
+  g.tri = 0;
+  LPGP_TRY(launch_gemm(ctx, ctx->s_main, 0, 1, g, LPGP_K_GEMM));
+  LPGP_TRY(drain.wait());
+  *out_new = out.release();
   return 0;
 }
 
@@ -1819,36 +1756,31 @@ int lpgp_gemm_host(lpgp_ctx* ctx, int32_t transa, int32_t transb, int64_t m, int
   const int64_t a_src_ld = transb ? k : n, a_src_cols = transb ? n : k;   // the host array behind it, as column-major ld x cols
   const int64_t b_src_ld = transa ? m : k, b_src_cols = transa ? k : m;
   const size_t ab = (size_t)a_ld * a_cols * sizeof(double), bb = (size_t)b_ld * b_cols * sizeof(double), cb = (size_t)np_ * mp * sizeof(double);
-  void *pa = nullptr, *pb = nullptr, *pc = nullptr;
-  if (pool_alloc(ctx, &pa, ab, nullptr) != 0) return -1;
-  if (pool_alloc(ctx, &pb, bb, nullptr) != 0) { pool_free(ctx, pa, ab); return -1; }
-  if (pool_alloc(ctx, &pc, cb, nullptr) != 0) { pool_free(ctx, pa, ab); pool_free(ctx, pb, bb); return -1; }
+  DevBuf pc, pb, pa;                             // (declared in reverse: they go back into the pool in the order a, b, c)
+  LPGP_TRY(DevBuf::pool(ctx, ab, &pa));
+  LPGP_TRY(DevBuf::pool(ctx, bb, &pb));
+  LPGP_TRY(DevBuf::pool(ctx, cb, &pc));
   hipStream_t st = ctx->s_main;
-  int rc = 0;
-  auto ok = [&](hipError_t e) { if (e != hipSuccess && rc == 0) { rc = -1; set_error("lpgp_gemm_host: %s", hipGetErrorString(e)); } };
-  ok(hipMemsetAsync(pa, 0, ab, st));
-  ok(hipMemsetAsync(pb, 0, bb, st));
-  ok(hipMemcpy2DAsync(pa, (size_t)a_ld * sizeof(double), B_host, (size_t)a_src_ld * sizeof(double), (size_t)a_src_ld * sizeof(double), (size_t)a_src_cols,
-                      hipMemcpyHostToDevice, st));
-  ok(hipMemcpy2DAsync(pb, (size_t)b_ld * sizeof(double), A_host, (size_t)b_src_ld * sizeof(double), (size_t)b_src_ld * sizeof(double), (size_t)b_src_cols,
-                      hipMemcpyHostToDevice, st));
+  StreamDrain drain{st};                         // (the caller's arrays are borrowed by the copies)
+  LPGP_HIP(hipMemsetAsync(pa.as(), 0, ab, st));
+  LPGP_HIP(hipMemsetAsync(pb.as(), 0, bb, st));
+  LPGP_HIP(hipMemcpy2DAsync(pa.as(), (size_t)a_ld * sizeof(double), B_host, (size_t)a_src_ld * sizeof(double), (size_t)a_src_ld * sizeof(double),
+                            (size_t)a_src_cols, hipMemcpyHostToDevice, st));
+  LPGP_HIP(hipMemcpy2DAsync(pb.as(), (size_t)b_ld * sizeof(double), A_host, (size_t)b_src_ld * sizeof(double), (size_t)b_src_ld * sizeof(double),
+                            (size_t)b_src_cols, hipMemcpyHostToDevice, st));
   if (beta != 0.0) {
-    ok(hipMemsetAsync(pc, 0, cb, st));
-    ok(hipMemcpy2DAsync(pc, (size_t)np_ * sizeof(double), C_host, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
+    LPGP_HIP(hipMemsetAsync(pc.as(), 0, cb, st));
+    LPGP_HIP(hipMemcpy2DAsync(pc.as(), (size_t)np_ * sizeof(double), C_host, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)m,
+                              hipMemcpyHostToDevice, st));
   }
-  if (rc == 0) {
-    GemmArgs g;
-    g.A = (const double*)pa; g.B = (const double*)pb; g.C = (double*)pc; g.lda = a_ld; g.ldb = b_ld; g.ldc = np_;
-    g.mt = (int)(np_ / TILE); g.nt = (int)(mp / TILE); g.k = (int)kp; g.alpha = alpha; g.beta = beta;
-    g.tri = 0;
-    rc = launch_gemm(ctx, st, transb ? 1 : 0, transa ? 0 : 1, g, LPGP_K_GEMM);
-  }
-  if (rc == 0) ok(hipMemcpy2DAsync(C_host, (size_t)n * sizeof(double), pc, (size_t)np_ * sizeof(double), (size_t)n * sizeof(double), (size_t)m, hipMemcpyDeviceToHost, st));
-  if (hipStreamSynchronize(st) != hipSuccess && rc == 0) { rc = -1; set_error("lpgp_gemm_host: synchronisation failed"); }
-  pool_free(ctx, pa, ab);
-  pool_free(ctx, pb, bb);
-  pool_free(ctx, pc, cb);
-  return rc;
+  GemmArgs g;
+  g.A = pa.as(); g.B = pb.as(); g.C = pc.as(); g.lda = a_ld; g.ldb = b_ld; g.ldc = np_;
+  g.mt = (int)(np_ / TILE); g.nt = (int)(mp / TILE); g.k = (int)kp; g.alpha = alpha; g.beta = beta;
+  g.tri = 0;
+  LPGP_TRY(launch_gemm(ctx, st, transb ? 1 : 0, transa ? 0 : 1, g, LPGP_K_GEMM));
+  LPGP_HIP(hipMemcpy2DAsync(C_host, (size_t)n * sizeof(double), pc.as(), (size_t)np_ * sizeof(double), (size_t)n * sizeof(double), (size_t)m,
+                            hipMemcpyDeviceToHost, st));
+  return drain.wait();
 }
 
 int lpgp_rhs_to_host(lpgp_ctx* ctx, const lpgp_mat* mat, lpgp_rhs* rhs, double* out_host) {
@@ -1885,17 +1817,15 @@ int lpgp_kernel_matrix(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, con
   LPGP_CHECK(X0->d == X1->d && kd[0].d == X0->d, "lpgp_kernel_matrix: dimension mismatch");
   if (X0->n == 0 || X1->n == 0) return 0;
   DevDesc desc;
-  int rc = lower_kdesc(kd, ngroups, &desc);
-  if (rc != 0) return rc;
+  LPGP_TRY(lower_kdesc(kd, ngroups, &desc));
   const int64_t ld = round_up(X0->n, 2);
-  double* d = nullptr;
-  LPGP_HIP(hipMalloc(&d, (size_t)ld * X1->n * sizeof(double)));
-  rc = launch_assemble(ctx, ctx->s_main, desc, X0->x, X0->n, X0->n_pad, X1->x, X1->n, X1->n_pad, d, ld, 0, 0, 0);
   std::vector<double> h((size_t)ld * X1->n);
-  if (rc == 0 && hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess) rc = -1;
-  if (rc == 0 && hipStreamSynchronize(ctx->s_main) != hipSuccess) rc = -1;
-  (void)hipFree(d);
-  if (rc != 0) return rc;
+  DevBuf d;
+  LPGP_TRY(DevBuf::raw(h.size() * sizeof(double), &d));
+  StreamDrain drain{ctx->s_main};
+  LPGP_TRY(launch_assemble(ctx, ctx->s_main, desc, X0->x, X0->n, X0->n_pad, X1->x, X1->n, X1->n_pad, d.as(), ld, 0, 0, 0));
+  LPGP_HIP(hipMemcpyAsync(h.data(), d.as(), h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
+  LPGP_TRY(drain.wait());
   for (int64_t i = 0; i < X0->n; ++i)
     for (int64_t j = 0; j < X1->n; ++j) out_host[i * X1->n + j] = h[(size_t)(i + j * ld)];
   return 0;
@@ -1914,38 +1844,34 @@ int lpgp_kernel_matvec(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, con
     return 0;
   }
   DevDesc desc;
-  int rc = lower_kdesc(kd, ngroups, &desc);
-  if (rc != 0) return rc;
+  LPGP_TRY(lower_kdesc(kd, ngroups, &desc));
   // enough workgroups to fill the chip: row tiles x column splits >= ~4 per CU
   const int tiles_r = (int)((n0 + 63) / 64), tiles_c = (int)((n1 + 63) / 64);
   int splits = (4 * ctx->cus + tiles_r - 1) / tiles_r;
   if (splits > tiles_c) splits = tiles_c;
   if (splits < 1) splits = 1;
   const int64_t n0p = X0->n_pad, n1p = X1->n_pad;
-  double *dv = nullptr, *dpart = nullptr, *dout = nullptr;
-  void* p = nullptr;
   const size_t bv = (size_t)MV_RHS * n1p * sizeof(double), bp = (size_t)splits * MV_RHS * n0p * sizeof(double),
                bo = (size_t)MV_RHS * n0p * sizeof(double);
-  if (pool_alloc(ctx, &p, bv + bp + bo, nullptr) != 0) return -1;
-  dv = (double*)p;
-  dpart = dv + (size_t)MV_RHS * n1p;
-  dout = dpart + (size_t)splits * MV_RHS * n0p;
   std::vector<double> hv((size_t)MV_RHS * n1p), ho((size_t)MV_RHS * n0p);
-  for (int64_t r0 = 0; r0 < nrhs && rc == 0; r0 += MV_RHS) {
+  DevBuf buf;
+  LPGP_TRY(DevBuf::pool(ctx, bv + bp + bo, &buf));
+  double* const dv = buf.as();
+  double* const dpart = dv + (size_t)MV_RHS * n1p;
+  double* const dout = dpart + (size_t)splits * MV_RHS * n0p;
+  for (int64_t r0 = 0; r0 < nrhs; r0 += MV_RHS) {
     const int nr = (int)((nrhs - r0 < MV_RHS) ? nrhs - r0 : MV_RHS);
     for (int r = 0; r < nr; ++r)
       for (int64_t j = 0; j < n1; ++j) hv[(size_t)r * n1p + j] = v_host[j * nrhs + r0 + r];
-    if (hipMemcpyAsync(dv, hv.data(), (size_t)nr * n1p * sizeof(double), hipMemcpyHostToDevice, ctx->s_main) != hipSuccess) rc = -1;
-    if (rc == 0) rc = launch_matvec(ctx, ctx->s_main, desc, X0->x, n0, n0p, X1->x, n1, n1p, dv, nr, dpart, splits, dout);
-    if (rc == 0 && hipMemcpyAsync(ho.data(), dout, (size_t)nr * n0p * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess) rc = -1;
-    if (rc == 0 && hipStreamSynchronize(ctx->s_main) != hipSuccess) rc = -1;
-    if (rc == 0)
-      for (int r = 0; r < nr; ++r)
-        for (int64_t i = 0; i < n0; ++i) out_host[i * nrhs + r0 + r] = ho[(size_t)r * n0p + i];
+    StreamDrain drain{ctx->s_main};              // (the staging vectors are borrowed by the copies of this pass)
+    LPGP_HIP(hipMemcpyAsync(dv, hv.data(), (size_t)nr * n1p * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
+    LPGP_TRY(launch_matvec(ctx, ctx->s_main, desc, X0->x, n0, n0p, X1->x, n1, n1p, dv, nr, dpart, splits, dout));
+    LPGP_HIP(hipMemcpyAsync(ho.data(), dout, (size_t)nr * n0p * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
+    LPGP_TRY(drain.wait());
+    for (int r = 0; r < nr; ++r)
+      for (int64_t i = 0; i < n0; ++i) out_host[i * nrhs + r0 + r] = ho[(size_t)r * n0p + i];
   }
-  pool_free(ctx, p, bv + bp + bo);
-  if (rc == -1) set_error("lpgp_kernel_matvec: HIP error %s", hipGetErrorString(hipGetLastError()));
-  return rc;
+  return 0;
 }
 
 int lpgp_profile_enable(lpgp_ctx* ctx, int32_t mask) {

@@ -313,34 +313,30 @@ int dist_warm_up(lpgp_ctx* ctx) {
       ctx->nccl_comm_bulk = nullptr;
     }
   }
-  double* d = nullptr;
-  LPGP_HIP(hipMalloc(&d, (size_t)W * sizeof(double)));
   std::vector<double> h((size_t)W, -1.0);
   h[(size_t)ctx->rank] = 1000.0 + ctx->rank;
-  int rc = 0;
-  do {
-    if (hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) { rc = -1; break; }
-    std::vector<Piece> pieces;
-    for (int r = 0; r < W; ++r) pieces.push_back({r, d + r, 1});
-    if ((rc = bcast_pieces(ctx, st, pieces)) != 0) break;
-    if (ctx->nccl_comm_bulk && (rc = bcast_pieces(ctx, st, pieces, true)) != 0) break;
-    if (hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) { rc = -1; break; }
-    if ((rc = sync_stream(ctx, st)) != 0) break;
-    for (int r = 0; r < W; ++r)
-      if (h[(size_t)r] != 1000.0 + r) {
-        set_error("communicator warm-up: rank %d received %g from rank %d (expected %g)", ctx->rank, h[(size_t)r], r, 1000.0 + r);
-        rc = -3;
-      }
-    if (rc != 0) break;
-    int v = ctx->rank;
-    if ((rc = allreduce_max_int(ctx, st, &v)) != 0) break;
-    if (v != W - 1) {
-      set_error("communicator warm-up: all-reduce(max) of the ranks gave %d, expected %d", v, W - 1);
-      rc = -3;
+  DevBuf buf;                                    // (released by hipFree, which waits for the device: behind h, so in front of it on the way out)
+  LPGP_TRY(DevBuf::raw(h.size() * sizeof(double), &buf));
+  double* const d = buf.as();
+  LPGP_HIP(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  std::vector<Piece> pieces;
+  for (int r = 0; r < W; ++r) pieces.push_back({r, d + r, 1});
+  LPGP_TRY(bcast_pieces(ctx, st, pieces));
+  if (ctx->nccl_comm_bulk) LPGP_TRY(bcast_pieces(ctx, st, pieces, true));
+  LPGP_HIP(hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  LPGP_TRY(sync_stream(ctx, st));
+  for (int r = 0; r < W; ++r)
+    if (h[(size_t)r] != 1000.0 + r) {
+      set_error("communicator warm-up: rank %d received %g from rank %d (expected %g)", ctx->rank, h[(size_t)r], r, 1000.0 + r);
+      return -3;
     }
-  } while (0);
-  (void)hipFree(d);
-  return rc;
+  int v = ctx->rank;
+  LPGP_TRY(allreduce_max_int(ctx, st, &v));
+  if (v != W - 1) {
+    set_error("communicator warm-up: all-reduce(max) of the ranks gave %d, expected %d", v, W - 1);
+    return -3;
+  }
+  return 0;
 }
 
 // ---- link probe ---------------------------------------------------------------------------------------------------
@@ -360,18 +356,16 @@ int dist_link_probe(lpgp_ctx* ctx, int64_t bytes, int32_t reps, double* out) {
   size_t count = (size_t)bytes / sizeof(double);
   if (ctx->ipc()) count = std::min(count, ctx->ipc_window_doubles / 2 / (size_t)W);      // (lower half: the exchanges of the panel stream)
   out[W * W + W + 1] = (double)(count * sizeof(double));      // bytes per message actually moved (the IPC window may cap the request)
-  void *ps = nullptr, *pr = nullptr;
   const size_t sb = count * sizeof(double), rb = sb * (size_t)(W - 1);
-  if (pool_alloc(ctx, &ps, sb, nullptr) != 0) return -1;
-  if (pool_alloc(ctx, &pr, rb, nullptr) != 0) { pool_free(ctx, ps, sb); return -1; }
-  double* dsend = (double*)ps;
-  double* drecv = (double*)pr;
-  struct Release { lpgp_ctx* c; void *a, *b; size_t sa, sb_; ~Release() { pool_free(c, a, sa); pool_free(c, b, sb_); } } release{ctx, ps, pr, sb, rb};
+  DevBuf recv, send;                             // (declared in reverse: they go back into the pool send buffer first)
+  LPGP_TRY(DevBuf::pool(ctx, sb, &send));
+  LPGP_TRY(DevBuf::pool(ctx, rb, &recv));
+  double* dsend = send.as();
+  double* drecv = recv.as();
   LPGP_HIP(hipMemsetAsync(dsend, 0, sb, st));
-  hipEvent_t e0, e1;
-  LPGP_HIP(hipEventCreate(&e0));
-  LPGP_HIP(hipEventCreate(&e1));
-  struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evs{e0, e1};
+  EventPair evs;
+  LPGP_TRY(evs.create());
+  const hipEvent_t e0 = evs.e0, e1 = evs.e1;
   auto barrier = [&]() -> int {
     int v = 0;
     return allreduce_max_int(ctx, st, &v);
@@ -944,11 +938,9 @@ int trsm_lower_t_dist(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int6
   const int mtl = (int)(m_pad / TILE);
   const int64_t nb = (int64_t)G.nbt * TILE, tb = TILE;
   hipStream_t st = ctx->s_main;
-  void* sp = nullptr;
-  const size_t sbytes = (size_t)TILE * (size_t)m_pad * sizeof(double);
-  if (pool_alloc(ctx, &sp, sbytes, nullptr) != 0) return -1;
-  double* S = (double*)sp;
-  struct Release { lpgp_ctx* c; void* p; size_t b; ~Release() { pool_free(c, p, b); } } release{ctx, sp, sbytes};
+  DevBuf sbuf;
+  LPGP_TRY(DevBuf::pool(ctx, (size_t)TILE * (size_t)m_pad * sizeof(double), &sbuf));
+  double* S = sbuf.as();
   std::vector<int> starts;
   for (int c0 = 0; c0 < T; c0 = std::min(T, (c0 / G.nbt + 1) * G.nbt)) starts.push_back(c0);
   for (int pi = (int)starts.size() - 1; pi >= 0; --pi) {

@@ -285,6 +285,84 @@ int dist_link_probe(lpgp_ctx* ctx, int64_t bytes, int32_t reps, double* out);
 int pool_alloc(lpgp_ctx* ctx, void** out, size_t bytes, bool* fresh);
 void pool_free(lpgp_ctx* ctx, void* p, size_t bytes);
 
+// ---- scope guards of the entry points: the error macros return early, these release on the way out -------------------------
+#define LPGP_LOCAL __attribute__((visibility("hidden")))      // (their inline members are no exports of the library)
+// A temporary device buffer.  It goes back where it came from when it leaves its scope: into the pool (reuse of a pool buffer is
+// ordered on the panel stream, so the guard may go right after the last launch that uses the buffer was enqueued there), or to
+// hipFree (which waits for the device).
+class LPGP_LOCAL DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p_ && ctx_) pool_free(ctx_, p_, bytes_);
+    else if (p_) (void)hipFree(p_);
+  }
+  static int pool(lpgp_ctx* ctx, size_t bytes, DevBuf* out) {
+    LPGP_TRY(pool_alloc(ctx, &out->p_, bytes, nullptr));
+    out->ctx_ = ctx;
+    out->bytes_ = bytes;
+    return 0;
+  }
+  static int raw(size_t bytes, DevBuf* out) {
+    const hipError_t e = hipMalloc(&out->p_, bytes);
+    if (e != hipSuccess) {
+      out->p_ = nullptr;
+      set_error("device allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+      return -1;
+    }
+    return 0;
+  }
+  void adopt_raw(void* p) { p_ = p; }      // a pointer that came from hipMalloc earlier (the points-set recycler)
+  template <class T = double> T* as() const { return static_cast<T*>(p_); }
+  void* release() {                        // hand the pointer to a longer-lived owner (lpgp_rhs::v, lpgp_dvec::v, ...)
+    void* p = p_;
+    p_ = nullptr;
+    return p;
+  }
+
+ private:
+  void* p_ = nullptr;
+  size_t bytes_ = 0;
+  lpgp_ctx* ctx_ = nullptr;                // pool buffers only
+};
+
+// Borrowed host memory is drained before return: a function that enqueues a copy to or from a local vector or the caller's
+// pointer declares one of these BEHIND the vector and the device buffers, waits through wait() on its way to success, and is
+// waited for by the destructor on every early return (which keeps the error text of the step that failed).
+// `watched`: the context of a multi-GPU path, whose waits go through sync_stream.
+struct LPGP_LOCAL StreamDrain {
+  hipStream_t st;
+  lpgp_ctx* watched = nullptr;
+  bool armed = true;
+  int wait() {
+    armed = false;
+    if (watched) return sync_stream(watched, st);
+    LPGP_HIP(hipStreamSynchronize(st));
+    return 0;
+  }
+  ~StreamDrain() {
+    if (!armed) return;
+    const std::string msg = last_error();
+    if (wait() != 0) set_error("%s", msg.c_str());
+  }
+};
+
+// two timing events (micro-benchmarks of the test hooks, the link probe)
+struct LPGP_LOCAL EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int create() {
+    LPGP_HIP(hipEventCreate(&e0));
+    LPGP_HIP(hipEventCreate(&e1));
+    return 0;
+  }
+  ~EventPair() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
 // profiling helpers: bracket launches of `kernel` on `stream`
 void prof_begin(lpgp_ctx* ctx, hipStream_t stream, int kernel, double flops, double bytes);
 void prof_end(lpgp_ctx* ctx, hipStream_t stream);

@@ -16,6 +16,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "lpgp_internal.h"
@@ -169,19 +170,14 @@ extern "C" {
 int lpgp_dvec_create(lpgp_ctx* ctx, int64_t n, int64_t m, lpgp_dvec** out) {
   LPGP_CHECK(ctx && out && n >= 1 && m >= 1, "lpgp_dvec_create: bad argument");
   LPGP_DEVICE(ctx);
-  lpgp_dvec* d = new lpgp_dvec();
+  std::unique_ptr<lpgp_dvec> d(new lpgp_dvec());
   d->ctx = ctx; d->n = n; d->m = m; d->ld = (n + 63) / 64 * 64;
   d->bytes = (size_t)d->ld * m * sizeof(double);
-  void* p = nullptr;
-  if (pool_alloc(ctx, &p, d->bytes, nullptr) != 0) { delete d; return -1; }
-  d->v = (double*)p;
-  if (hipMemsetAsync(d->v, 0, d->bytes, ctx->s_main) != hipSuccess) {
-    (void)hipGetLastError();
-    pool_free(ctx, p, d->bytes);
-    delete d;
-    LPGP_CHECK(false, "lpgp_dvec_create: clearing %zu bytes failed", (size_t)((n + 63) / 64 * 64) * (size_t)m * sizeof(double));
-  }
-  *out = d;
+  DevBuf v;
+  LPGP_TRY(DevBuf::pool(ctx, d->bytes, &v));
+  LPGP_HIP(hipMemsetAsync(v.as(), 0, d->bytes, ctx->s_main));
+  d->v = (double*)v.release();
+  *out = d.release();
   return 0;
 }
 int lpgp_dvec_destroy(lpgp_dvec* d) {
@@ -225,19 +221,15 @@ int lpgp_dvec_scale_rows_add(lpgp_ctx* ctx, lpgp_dvec* Y, int64_t y_off, const l
   LPGP_CHECK(ctx && Y && V && d_host && n >= 1 && Y->m == V->m && Y->ld == V->ld && y_off == v_off && y_off >= 0 && y_off + n <= Y->n,
              "lpgp_dvec_scale_rows_add: bad argument (the two blocks must share their layout and row range)");
   LPGP_DEVICE(ctx);
-  void* p = nullptr;
   const size_t b = (size_t)n * sizeof(double);
-  if (pool_alloc(ctx, &p, b, nullptr) != 0) return -1;
-  hipError_t e = hipMemcpyAsync(p, d_host, b, hipMemcpyHostToDevice, ctx->s_main);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(dvec_scale_rows_add_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)Y->m), dim3(256), 0, ctx->s_main, Y->v + y_off, V->v + v_off,
-                       (const double*)p, n, Y->ld);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_main);          // (borrowed host vector)
-  pool_free(ctx, p, b);
-  LPGP_CHECK(e == hipSuccess, "lpgp_dvec_scale_rows_add: %s", hipGetErrorString(e));
-  return 0;
+  DevBuf d;
+  LPGP_TRY(DevBuf::pool(ctx, b, &d));
+  StreamDrain drain{ctx->s_main};                // (borrowed host vector)
+  LPGP_HIP(hipMemcpyAsync(d.as(), d_host, b, hipMemcpyHostToDevice, ctx->s_main));
+  hipLaunchKernelGGL(dvec_scale_rows_add_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)Y->m), dim3(256), 0, ctx->s_main, Y->v + y_off, V->v + v_off,
+                     (const double*)d.as(), n, Y->ld);
+  LPGP_HIP(hipGetLastError());
+  return drain.wait();
 }
 
 // Y[y_off : y_off + n0, :] (accumulate: +=) K(X0, X1) V[v_off : v_off + n1, :], every operand resident (replaces the KeOps lazy
@@ -251,23 +243,20 @@ int lpgp_kernel_matvec_dev(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups,
   LPGP_CHECK(V->m == Y->m && v_off >= 0 && v_off + n1 <= V->n && y_off >= 0 && y_off + n0 <= Y->n, "lpgp_kernel_matvec_dev: block out of range");
   if (n0 == 0 || n1 == 0) return 0;
   DevDesc desc;
-  int rc = lower_kdesc(kd, ngroups, &desc);
-  if (rc != 0) return rc;
+  LPGP_TRY(lower_kdesc(kd, ngroups, &desc));
   const int tiles_r = (int)((n0 + 63) / 64), tiles_c = (int)((n1 + 63) / 64);
   int splits = (4 * ctx->cus + tiles_r - 1) / tiles_r;
   if (splits > tiles_c) splits = tiles_c;
   if (splits < 1) splits = 1;
   const int64_t n0p = X0->n_pad;
-  void* p = nullptr;
-  const size_t bp = (size_t)splits * MV_RHS * n0p * sizeof(double);
-  if (pool_alloc(ctx, &p, bp, nullptr) != 0) return -1;
-  for (int64_t r0 = 0; r0 < V->m && rc == 0; r0 += MV_RHS) {
+  DevBuf part;                   // (reuse is stream-ordered: every user of the pool runs on the panel stream)
+  LPGP_TRY(DevBuf::pool(ctx, (size_t)splits * MV_RHS * n0p * sizeof(double), &part));
+  for (int64_t r0 = 0; r0 < V->m; r0 += MV_RHS) {
     const int nr = (int)((V->m - r0 < MV_RHS) ? V->m - r0 : MV_RHS);
-    rc = launch_matvec(ctx, ctx->s_main, desc, X0->x, n0, n0p, X1->x, n1, X1->n_pad, V->v + v_off + r0 * V->ld, nr, (double*)p, splits,
-                       Y->v + y_off + r0 * Y->ld, V->ld, Y->ld, accumulate);
+    LPGP_TRY(launch_matvec(ctx, ctx->s_main, desc, X0->x, n0, n0p, X1->x, n1, X1->n_pad, V->v + v_off + r0 * V->ld, nr, part.as(), splits,
+                           Y->v + y_off + r0 * Y->ld, V->ld, Y->ld, accumulate));
   }
-  pool_free(ctx, p, bp);         // (reuse is stream-ordered: every user of the pool runs on the panel stream)
-  return rc;
+  return 0;
 }
 
 // ---- preconditioned conjugate gradients, one iteration = launches only ------------------------------------------------
@@ -275,27 +264,24 @@ int lpgp_pcg_create(lpgp_ctx* ctx, int64_t n, int64_t m, int32_t rank, const dou
                     double delta, lpgp_pcg** out) {
   LPGP_CHECK(ctx && out && n >= 1 && m >= 1 && m <= 256 && rank >= 0 && delta > 0.0 && (rank == 0 || (L_host && Sinv_host)), "lpgp_pcg_create: bad argument");
   LPGP_DEVICE(ctx);
-  lpgp_pcg* p = new lpgp_pcg();
+  std::unique_ptr<lpgp_pcg> p(new lpgp_pcg());
   p->ctx = ctx; p->n = n; p->m = m; p->rank = rank; p->delta = delta; p->G = PCG_G;
   p->L_bytes = ((size_t)rank * n + (size_t)rank * rank + 8) * sizeof(double);
   p->work_bytes = ((size_t)3 * m * PCG_G + (size_t)8 * m + (size_t)2 * rank * m + 8) * sizeof(double);
-  void *pl = nullptr, *pw = nullptr;
-  if (pool_alloc(ctx, &pl, p->L_bytes, nullptr) != 0) { delete p; return -1; }
-  if (pool_alloc(ctx, &pw, p->work_bytes, nullptr) != 0) { pool_free(ctx, pl, p->L_bytes); delete p; return -1; }
-  p->L = (double*)pl;
-  p->Sinv = p->L + (size_t)rank * n;
-  p->work = (double*)pw;
-  hipError_t e = hipMemsetAsync(pw, 0, p->work_bytes, ctx->s_main);
-  if (e == hipSuccess && rank > 0) e = hipMemcpyAsync(p->L, L_host, (size_t)rank * n * sizeof(double), hipMemcpyHostToDevice, ctx->s_main);
-  if (e == hipSuccess && rank > 0) e = hipMemcpyAsync(p->Sinv, Sinv_host, (size_t)rank * rank * sizeof(double), hipMemcpyHostToDevice, ctx->s_main);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_main);
-  if (e != hipSuccess) {
-    set_error("lpgp_pcg_create: %s", hipGetErrorString(e));
-    pool_free(ctx, pl, p->L_bytes); pool_free(ctx, pw, p->work_bytes);
-    delete p;
-    return -1;
+  DevBuf L, work;
+  LPGP_TRY(DevBuf::pool(ctx, p->L_bytes, &L));
+  LPGP_TRY(DevBuf::pool(ctx, p->work_bytes, &work));
+  StreamDrain drain{ctx->s_main};                // (the caller's arrays are borrowed by the copies)
+  LPGP_HIP(hipMemsetAsync(work.as(), 0, p->work_bytes, ctx->s_main));
+  if (rank > 0) {
+    LPGP_HIP(hipMemcpyAsync(L.as(), L_host, (size_t)rank * n * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
+    LPGP_HIP(hipMemcpyAsync(L.as() + (size_t)rank * n, Sinv_host, (size_t)rank * rank * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
   }
-  *out = p;
+  LPGP_TRY(drain.wait());
+  p->L = (double*)L.release();
+  p->Sinv = p->L + (size_t)rank * n;
+  p->work = (double*)work.release();
+  *out = p.release();
   return 0;
 }
 int lpgp_pcg_destroy(lpgp_pcg* p) {

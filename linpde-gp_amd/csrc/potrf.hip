@@ -835,11 +835,9 @@ int trsm_lower_t_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, i
   const int nbt = (int)(ctx->nb / TILE);
   const double* a = mat->a;
   hipStream_t st = ctx->s_main;
-  void* sp = nullptr;
-  const size_t sbytes = (size_t)TILE * (size_t)m_pad * sizeof(double);
-  if (pool_alloc(ctx, &sp, sbytes, nullptr) != 0) return -1;
-  double* S = (double*)sp;
-  struct Release { lpgp_ctx* c; void* p; size_t b; ~Release() { pool_free(c, p, b); } } release{ctx, sp, sbytes};   // reuse is stream-ordered
+  DevBuf sbuf;                                   // (reuse is stream-ordered)
+  LPGP_TRY(DevBuf::pool(ctx, (size_t)TILE * (size_t)m_pad * sizeof(double), &sbuf));
+  double* S = sbuf.as();
   for (int p1 = T; p1 > 0;) {
     const int p0 = (p1 - nbt > 0) ? p1 - nbt : 0;
     for (int jt = p1 - 1; jt >= p0; --jt) {

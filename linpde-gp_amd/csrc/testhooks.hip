@@ -49,10 +49,11 @@ int lpgp_test_gemm(lpgp_ctx* ctx, int32_t ta, int32_t tb, int32_t lower_only, in
   LPGP_CHECK(m % TILE == 0 && n % TILE == 0 && k % 16 == 0, "lpgp_test_gemm: m,n multiples of 128 and k of 16 required");
   const int64_t a_elems = ta ? lda * m : lda * k;
   const int64_t b_elems = tb ? ldb * n : ldb * k;
-  double *dA = nullptr, *dB = nullptr, *dC = nullptr;
-  LPGP_HIP(hipMalloc(&dA, (size_t)a_elems * sizeof(double)));
-  LPGP_HIP(hipMalloc(&dB, (size_t)b_elems * sizeof(double)));
-  LPGP_HIP(hipMalloc(&dC, (size_t)ldc * n * sizeof(double)));
+  DevBuf bA, bB, bC;
+  LPGP_TRY(DevBuf::raw((size_t)a_elems * sizeof(double), &bA));
+  LPGP_TRY(DevBuf::raw((size_t)b_elems * sizeof(double), &bB));
+  LPGP_TRY(DevBuf::raw((size_t)ldc * n * sizeof(double), &bC));
+  double *const dA = bA.as(), *const dB = bB.as(), *const dC = bC.as();
   LPGP_HIP(hipMemcpy(dA, A, (size_t)a_elems * sizeof(double), hipMemcpyHostToDevice));
   LPGP_HIP(hipMemcpy(dB, B, (size_t)b_elems * sizeof(double), hipMemcpyHostToDevice));
   LPGP_HIP(hipMemcpy(dC, C, (size_t)ldc * n * sizeof(double), hipMemcpyHostToDevice));
@@ -60,27 +61,21 @@ int lpgp_test_gemm(lpgp_ctx* ctx, int32_t ta, int32_t tb, int32_t lower_only, in
   g.A = dA; g.B = dB; g.C = dC; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.mt = (int)(m / TILE); g.nt = (int)(n / TILE); g.k = (int)k; g.alpha = alpha; g.beta = beta;
   g.tri = lower_only;
-  int rc = launch_gemm(ctx, ts, ta, tb, g, -1);
-  if (rc == 0 && hipStreamSynchronize(ts) != hipSuccess) rc = -1;
-  if (rc == 0) LPGP_HIP(hipMemcpy(C, dC, (size_t)ldc * n * sizeof(double), hipMemcpyDeviceToHost));
-  if (rc == 0 && reps > 0 && ms_per_rep) {
-    hipEvent_t e0, e1;
-    LPGP_HIP(hipEventCreate(&e0));
-    LPGP_HIP(hipEventCreate(&e1));
-    LPGP_HIP(hipEventRecord(e0, ts));
-    for (int r = 0; r < reps && rc == 0; ++r) rc = launch_gemm(ctx, ts, ta, tb, g, -1);
-    LPGP_HIP(hipEventRecord(e1, ts));
-    LPGP_HIP(hipEventSynchronize(e1));
+  LPGP_TRY(launch_gemm(ctx, ts, ta, tb, g, -1));
+  LPGP_HIP(hipStreamSynchronize(ts));
+  LPGP_HIP(hipMemcpy(C, dC, (size_t)ldc * n * sizeof(double), hipMemcpyDeviceToHost));
+  if (reps > 0 && ms_per_rep) {
+    EventPair ev;
+    LPGP_TRY(ev.create());
+    LPGP_HIP(hipEventRecord(ev.e0, ts));
+    for (int r = 0; r < reps; ++r) LPGP_TRY(launch_gemm(ctx, ts, ta, tb, g, -1));
+    LPGP_HIP(hipEventRecord(ev.e1, ts));
+    LPGP_HIP(hipEventSynchronize(ev.e1));
     float ms = 0.f;
-    LPGP_HIP(hipEventElapsedTime(&ms, e0, e1));
+    LPGP_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
     *ms_per_rep = ms / reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
   }
-  (void)hipFree(dA);
-  (void)hipFree(dB);
-  (void)hipFree(dC);
-  return rc;
+  return 0;
 }
 
 int lpgp_test_stair_enumerate(int32_t pr, int32_t pc, int32_t my_r, int32_t my_c, int32_t nbt, int32_t T, int32_t row_lo,
@@ -106,88 +101,77 @@ int lpgp_test_stair_enumerate(int32_t pr, int32_t pc, int32_t my_r, int32_t my_c
 
 int lpgp_test_potrf_tile(lpgp_ctx* ctx, double* T, double* Linv, int32_t* info) {
   LPGP_DEVICE(ctx);
-  double *dT = nullptr, *dL = nullptr;
-  LPGP_HIP(hipMalloc(&dT, (size_t)TILE * TILE * sizeof(double)));
-  LPGP_HIP(hipMalloc(&dL, (size_t)TILE * TILE * sizeof(double)));
-  LPGP_HIP(hipMemcpy(dT, T, (size_t)TILE * TILE * sizeof(double), hipMemcpyHostToDevice));
-  LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), ctx->s_main));
-  int rc = launch_potrf_tile(ctx, ctx->s_main, dT, TILE, dL, ctx->d_info, 0);
+  const size_t tbytes = (size_t)TILE * TILE * sizeof(double);
   int h = 0;
-  if (rc == 0) {
-    LPGP_HIP(hipMemcpyAsync(&h, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->s_main));
-    LPGP_HIP(hipStreamSynchronize(ctx->s_main));
-    LPGP_HIP(hipMemcpy(T, dT, (size_t)TILE * TILE * sizeof(double), hipMemcpyDeviceToHost));
-    LPGP_HIP(hipMemcpy(Linv, dL, (size_t)TILE * TILE * sizeof(double), hipMemcpyDeviceToHost));
-  }
   if (info) *info = h;
-  (void)hipFree(dT);
-  (void)hipFree(dL);
-  return rc;
+  DevBuf bT, bL;                                 // (hipFree waits for the device: h, declared in front, outlives a copy in flight)
+  LPGP_TRY(DevBuf::raw(tbytes, &bT));
+  LPGP_TRY(DevBuf::raw(tbytes, &bL));
+  double *const dT = bT.as(), *const dL = bL.as();
+  LPGP_HIP(hipMemcpy(dT, T, tbytes, hipMemcpyHostToDevice));
+  LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), ctx->s_main));
+  LPGP_TRY(launch_potrf_tile(ctx, ctx->s_main, dT, TILE, dL, ctx->d_info, 0));
+  LPGP_HIP(hipMemcpyAsync(&h, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->s_main));
+  LPGP_HIP(hipStreamSynchronize(ctx->s_main));
+  LPGP_HIP(hipMemcpy(T, dT, tbytes, hipMemcpyDeviceToHost));
+  LPGP_HIP(hipMemcpy(Linv, dL, tbytes, hipMemcpyDeviceToHost));
+  if (info) *info = h;
+  return 0;
 }
 
 int lpgp_test_tile_step(lpgp_ctx* ctx, int32_t which, double* XV, int64_t n, const double* L, const double* Linv, double* ms) {
   LPGP_CHECK(ctx && XV && L && Linv && n > 0 && n % TILE == 0 && (which == 0 || which == 1), "lpgp_test_tile_step: bad argument");
   LPGP_DEVICE(ctx);
-  double *d = nullptr, *dl = nullptr, *dt = nullptr;
   const size_t bytes = (size_t)n * TILE * sizeof(double), tbytes = (size_t)TILE * TILE * sizeof(double);
-  LPGP_HIP(hipMalloc(&d, bytes));
-  LPGP_HIP(hipMalloc(&dl, tbytes));
-  LPGP_HIP(hipMalloc(&dt, tbytes));
+  DevBuf bd, bl, bt;
+  LPGP_TRY(DevBuf::raw(bytes, &bd));
+  LPGP_TRY(DevBuf::raw(tbytes, &bl));
+  LPGP_TRY(DevBuf::raw(tbytes, &bt));
+  double *const d = bd.as(), *const dl = bl.as(), *const dt = bt.as();
   LPGP_HIP(hipMemcpy(d, XV, bytes, hipMemcpyHostToDevice));
   LPGP_HIP(hipMemcpy(dl, Linv, tbytes, hipMemcpyHostToDevice));
   LPGP_HIP(hipMemcpy(dt, L, tbytes, hipMemcpyHostToDevice));
-  hipEvent_t e0, e1;
-  LPGP_HIP(hipEventCreate(&e0));
-  LPGP_HIP(hipEventCreate(&e1));
+  EventPair ev;
+  LPGP_TRY(ev.create());
   const int nt = (int)(n / TILE);
-  LPGP_HIP(hipEventRecord(e0, ctx->s_main));
-  int rc = which == 0 ? launch_trsm_tile(ctx, ctx->s_main, d, n, dl, dt, TILE, nt, -1)
-                      : launch_trsv_tile(ctx, ctx->s_main, d, TILE, dl, dt, TILE, nt, -1);
-  LPGP_HIP(hipEventRecord(e1, ctx->s_main));
-  LPGP_HIP(hipEventSynchronize(e1));
+  LPGP_HIP(hipEventRecord(ev.e0, ctx->s_main));
+  LPGP_TRY(which == 0 ? launch_trsm_tile(ctx, ctx->s_main, d, n, dl, dt, TILE, nt, -1)
+                      : launch_trsv_tile(ctx, ctx->s_main, d, TILE, dl, dt, TILE, nt, -1));
+  LPGP_HIP(hipEventRecord(ev.e1, ctx->s_main));
+  LPGP_HIP(hipEventSynchronize(ev.e1));
   float t = 0.f;
-  LPGP_HIP(hipEventElapsedTime(&t, e0, e1));
+  LPGP_HIP(hipEventElapsedTime(&t, ev.e0, ev.e1));
   if (ms) *ms = t;
-  if (rc == 0) LPGP_HIP(hipMemcpy(XV, d, bytes, hipMemcpyDeviceToHost));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(d);
-  (void)hipFree(dl);
-  (void)hipFree(dt);
-  return rc;
+  LPGP_HIP(hipMemcpy(XV, d, bytes, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int lpgp_test_panel_solve(lpgp_ctx* ctx, int32_t rows_form, double* V, int32_t nt, int64_t cols, const double* Lblk, const double* Linv, double* ms) {
   LPGP_CHECK(ctx && V && Lblk && Linv && nt >= 1 && nt <= 4 && cols > 0 && cols % TILE == 0, "lpgp_test_panel_solve: bad argument");
   LPGP_DEVICE(ctx);
   const int64_t rows = (int64_t)nt * TILE;
-  double *d = nullptr, *dl = nullptr, *di = nullptr;
   const size_t vb = (size_t)rows * cols * sizeof(double), lb = (size_t)rows * rows * sizeof(double), ib = (size_t)nt * TILE * TILE * sizeof(double);
-  LPGP_HIP(hipMalloc(&d, vb));
-  LPGP_HIP(hipMalloc(&dl, lb));
-  LPGP_HIP(hipMalloc(&di, ib));
+  DevBuf bd, bl, bi;
+  LPGP_TRY(DevBuf::raw(vb, &bd));
+  LPGP_TRY(DevBuf::raw(lb, &bl));
+  LPGP_TRY(DevBuf::raw(ib, &bi));
+  double *const d = bd.as(), *const dl = bl.as(), *const di = bi.as();
   LPGP_HIP(hipMemcpy(d, V, vb, hipMemcpyHostToDevice));
   LPGP_HIP(hipMemcpy(dl, Lblk, lb, hipMemcpyHostToDevice));
   LPGP_HIP(hipMemcpy(di, Linv, ib, hipMemcpyHostToDevice));
-  hipEvent_t e0, e1;
-  LPGP_HIP(hipEventCreate(&e0));
-  LPGP_HIP(hipEventCreate(&e1));
-  LPGP_HIP(hipEventRecord(e0, ctx->s_main));
+  EventPair ev;
+  LPGP_TRY(ev.create());
+  LPGP_HIP(hipEventRecord(ev.e0, ctx->s_main));
   // rows_form: V holds X (cols rows x nt * 128 columns, column-major ld = cols) and X <- X Lblk^{-T}
-  int rc = rows_form ? launch_trsm_panel(ctx, ctx->s_main, d, cols, di, dl, rows, nt, (int)(cols / TILE), -1)
-                     : launch_trsv_panel(ctx, ctx->s_main, d, rows, di, dl, rows, nt, (int)(cols / TILE), -1);
-  LPGP_HIP(hipEventRecord(e1, ctx->s_main));
-  LPGP_HIP(hipEventSynchronize(e1));
+  LPGP_TRY(rows_form ? launch_trsm_panel(ctx, ctx->s_main, d, cols, di, dl, rows, nt, (int)(cols / TILE), -1)
+                     : launch_trsv_panel(ctx, ctx->s_main, d, rows, di, dl, rows, nt, (int)(cols / TILE), -1));
+  LPGP_HIP(hipEventRecord(ev.e1, ctx->s_main));
+  LPGP_HIP(hipEventSynchronize(ev.e1));
   float t = 0.f;
-  LPGP_HIP(hipEventElapsedTime(&t, e0, e1));
+  LPGP_HIP(hipEventElapsedTime(&t, ev.e0, ev.e1));
   if (ms) *ms = t;
-  if (rc == 0) LPGP_HIP(hipMemcpy(V, d, vb, hipMemcpyDeviceToHost));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(d);
-  (void)hipFree(dl);
-  (void)hipFree(di);
-  return rc;
+  LPGP_HIP(hipMemcpy(V, d, vb, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int lpgp_debug_tile_xcc(lpgp_ctx* ctx, int32_t* out8, int32_t reset) {
@@ -200,47 +184,41 @@ int lpgp_debug_tile_xcc(lpgp_ctx* ctx, int32_t* out8, int32_t reset) {
 int lpgp_probe_mfma_f64(lpgp_ctx* ctx, double* tflops) {
   LPGP_DEVICE(ctx);
   const int blocks = ctx->cus * 4, iters = 4000;
-  double* d = nullptr;
-  LPGP_HIP(hipMalloc(&d, (size_t)blocks * 256 * sizeof(double)));
-  hipEvent_t e0, e1;
-  LPGP_HIP(hipEventCreate(&e0));
-  LPGP_HIP(hipEventCreate(&e1));
+  DevBuf buf;
+  LPGP_TRY(DevBuf::raw((size_t)blocks * 256 * sizeof(double), &buf));
+  double* const d = buf.as();
+  EventPair ev;
+  LPGP_TRY(ev.create());
   hipLaunchKernelGGL(mfma_probe_kernel, dim3(blocks), dim3(256), 0, ctx->s_main, d, 100);   // warm-up
-  LPGP_HIP(hipEventRecord(e0, ctx->s_main));
+  LPGP_HIP(hipEventRecord(ev.e0, ctx->s_main));
   hipLaunchKernelGGL(mfma_probe_kernel, dim3(blocks), dim3(256), 0, ctx->s_main, d, iters);
-  LPGP_HIP(hipEventRecord(e1, ctx->s_main));
-  LPGP_HIP(hipEventSynchronize(e1));
+  LPGP_HIP(hipEventRecord(ev.e1, ctx->s_main));
+  LPGP_HIP(hipEventSynchronize(ev.e1));
   float ms = 0.f;
-  LPGP_HIP(hipEventElapsedTime(&ms, e0, e1));
+  LPGP_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   const double flops = (double)blocks * 4.0 * iters * 8.0 * (2.0 * 16 * 16 * 4);
   if (tflops) *tflops = flops / (ms * 1e-3) / 1e12;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(d);
   return 0;
 }
 
 int lpgp_probe_hbm_write(lpgp_ctx* ctx, int64_t bytes, double* gbps) {
   LPGP_DEVICE(ctx);
-  double* d = nullptr;
   bytes = round_up(bytes, 16);
-  LPGP_HIP(hipMalloc(&d, (size_t)bytes));
-  hipEvent_t e0, e1;
-  LPGP_HIP(hipEventCreate(&e0));
-  LPGP_HIP(hipEventCreate(&e1));
+  DevBuf buf;
+  LPGP_TRY(DevBuf::raw((size_t)bytes, &buf));
+  double* const d = buf.as();
+  EventPair ev;
+  LPGP_TRY(ev.create());
   const int grid = ctx->cus * 8;
   hipLaunchKernelGGL(write_probe_kernel, dim3(grid), dim3(256), 0, ctx->s_main, d, bytes / 16);
-  LPGP_HIP(hipEventRecord(e0, ctx->s_main));
+  LPGP_HIP(hipEventRecord(ev.e0, ctx->s_main));
   for (int r = 0; r < 5; ++r)
     hipLaunchKernelGGL(write_probe_kernel, dim3(grid), dim3(256), 0, ctx->s_main, d, bytes / 16);
-  LPGP_HIP(hipEventRecord(e1, ctx->s_main));
-  LPGP_HIP(hipEventSynchronize(e1));
+  LPGP_HIP(hipEventRecord(ev.e1, ctx->s_main));
+  LPGP_HIP(hipEventSynchronize(ev.e1));
   float ms = 0.f;
-  LPGP_HIP(hipEventElapsedTime(&ms, e0, e1));
+  LPGP_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   if (gbps) *gbps = 5.0 * (double)bytes / (ms * 1e-3) / 1e9;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(d);
   return 0;
 }
 

@@ -151,37 +151,28 @@ int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s,
   if (shift_host) std::memcpy(hz.data() + zdoubles, shift_host, (size_t)n * sizeof(double));
   const size_t bz = hz.size() * sizeof(double), bt = tab.size() * sizeof(int32_t);
   const size_t bp = (size_t)nchunks * nct * TILE * TR_ST * sizeof(double), bo = (size_t)n * s * sizeof(double);
-  void *pz = nullptr, *pt = nullptr, *pp = nullptr, *po = nullptr;
-  int rc = pool_alloc(ctx, &pz, bz, nullptr);
-  if (rc == 0) rc = pool_alloc(ctx, &pt, bt, nullptr);
-  if (rc == 0) rc = pool_alloc(ctx, &pp, bp, nullptr);
-  if (rc == 0) rc = pool_alloc(ctx, &po, bo, nullptr);
+  DevBuf po, pp, pt, pz;                         // (declared in reverse: they go back into the pool in the order z, t, p, o)
+  LPGP_TRY(DevBuf::pool(ctx, bz, &pz));
+  LPGP_TRY(DevBuf::pool(ctx, bt, &pt));
+  LPGP_TRY(DevBuf::pool(ctx, bp, &pp));
+  LPGP_TRY(DevBuf::pool(ctx, bo, &po));
   hipStream_t st = ctx->s_main;
-  auto ok = [&](hipError_t e) { if (e != hipSuccess && rc == 0) { rc = -1; set_error("lpgp_mat_factor_matmul: %s", hipGetErrorString(e)); } };
-  if (rc == 0) {
-    ok(hipMemcpyAsync(pz, hz.data(), bz, hipMemcpyHostToDevice, st));
-    ok(hipMemcpyAsync(pt, tab.data(), bt, hipMemcpyHostToDevice, st));
-  }
-  if (rc == 0) {
-    const int32_t* d_tab = (const int32_t*)pt;
-    const double flops = (double)pn * (double)(pn + TILE) * (double)nct * TR_ST;
-    prof_begin(ctx, st, LPGP_K_TRMM, flops, 4.0 * (double)pn * (double)(pn + TILE) * nct);
-    hipLaunchKernelGGL(trmm_lower_kernel, dim3((unsigned)nchunks, (unsigned)nct), dim3(256), 0, st, (const double*)mat->a, mat->lr_cap,
-                       (const double*)pz, pn, d_tab + pn + T + 1, d_tab + pn + T + 1 + nchunks, kc, (double*)pp, nct);
-    ok(hipGetLastError());
-    const int64_t total = pn * nct * TR_ST;
-    hipLaunchKernelGGL(trmm_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)pp, d_tab, d_tab + pn, nct, s, pn,
-                       shift_host ? (const double*)pz + zdoubles : (const double*)nullptr, (double*)po);
-    ok(hipGetLastError());
-    prof_end(ctx, st);
-    ok(hipMemcpyAsync(out_host, po, bo, hipMemcpyDeviceToHost, st));
-  }
-  if (hipStreamSynchronize(st) != hipSuccess && rc == 0) { rc = -1; set_error("lpgp_mat_factor_matmul: synchronisation failed"); }
-  if (pz) pool_free(ctx, pz, bz);
-  if (pt) pool_free(ctx, pt, bt);
-  if (pp) pool_free(ctx, pp, bp);
-  if (po) pool_free(ctx, po, bo);
-  return rc;
+  StreamDrain drain{st};                         // (the staging vectors and the caller's array are borrowed by the copies)
+  LPGP_HIP(hipMemcpyAsync(pz.as(), hz.data(), bz, hipMemcpyHostToDevice, st));
+  LPGP_HIP(hipMemcpyAsync(pt.as(), tab.data(), bt, hipMemcpyHostToDevice, st));
+  const int32_t* d_tab = pt.as<int32_t>();
+  const double flops = (double)pn * (double)(pn + TILE) * (double)nct * TR_ST;
+  prof_begin(ctx, st, LPGP_K_TRMM, flops, 4.0 * (double)pn * (double)(pn + TILE) * nct);
+  hipLaunchKernelGGL(trmm_lower_kernel, dim3((unsigned)nchunks, (unsigned)nct), dim3(256), 0, st, (const double*)mat->a, mat->lr_cap,
+                     (const double*)pz.as(), pn, d_tab + pn + T + 1, d_tab + pn + T + 1 + nchunks, kc, pp.as(), nct);
+  LPGP_HIP(hipGetLastError());
+  const int64_t total = pn * nct * TR_ST;
+  hipLaunchKernelGGL(trmm_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)pp.as(), d_tab, d_tab + pn, nct, s, pn,
+                     shift_host ? (const double*)pz.as() + zdoubles : (const double*)nullptr, po.as());
+  LPGP_HIP(hipGetLastError());
+  prof_end(ctx, st);
+  LPGP_HIP(hipMemcpyAsync(out_host, po.as(), bo, hipMemcpyDeviceToHost, st));
+  return drain.wait();
 }
 
 }  // namespace lpgp
