@@ -84,7 +84,8 @@ int  lpgp_sync(lpgp_ctx* ctx);                       /* hipDeviceSynchronize */
 /* tuning options of the context, one row each in the table of csrc/options.cpp: its key, its environment variable
  * (read by lpgp_init), its default and the values it accepts.  get reads every row, and also the read-only state
  * "live_mats" and "route_*" (route counters of the forward substitution); set refuses the rows read at init only
- * (reserve_cus, reserve_narrow, single_stream).                                                                    */
+ * (reserve_cus, reserve_narrow, single_stream).  Beside the table: "inverse_diag_panel" (get / set; lpgp_mat_inverse_diag)
+ * and the read-only byte counters "evidence_h2d_bytes" / "evidence_d2h_bytes".                                     */
 int  lpgp_set_option(lpgp_ctx* ctx, const char* key, int64_t value);
 int  lpgp_get_option(lpgp_ctx* ctx, const char* key, int64_t* value);
 
@@ -362,6 +363,32 @@ int  lpgp_mat_sub_inner(lpgp_ctx* ctx, lpgp_mat* S, int32_t bi, lpgp_rhs* V);
  * csrc/trmm.hip; bound by reading the lower triangle of L once, 4 n^2 bytes, for s <= 16.                                    */
 int  lpgp_mat_factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host,
                             double* out_host);
+
+/* ---- model evidence and leave-one-out diagnostics from the resident factor (csrc/evidence.hip).  The reference's users take
+ *      them from probnum (`Normal.logpdf` on `L(prior)(X)`) or from `gram.inv().todense()`; here nothing of size n^2 leaves the
+ *      device.  All three: a fully factored matrix or view (the logical rows of the CURRENT view), single GPU; a matrix that is
+ *      not (fully) factored, unchecked (lpgp_mat_check) or poisoned fails as lpgp_mat_factor_matmul does.  The same bits on
+ *      every call (fixed order of summation, no atomics).  The bytes they copy are counted: lpgp_get_option
+ *      "evidence_h2d_bytes" / "evidence_d2h_bytes".                                                                          */
+/* out_host[0] = r^T G^{-1} r = || L^{-1} r ||^2,  out_host[1] = log det G = 2 sum_i log L_ii  -- the two data-dependent terms of
+ * log p(y) = -1/2 r^T G^{-1} r - 1/2 log det G - n/2 log 2 pi  (Rasmussen & Williams, GPML eq. 2.30), r = Y - L[m] - b.mean
+ * (_conditional.py:44).  One forward solve of r through the single-vector path (csrc/trsv.hip), one two-stage reduction over the
+ * solved vector and the factor's diagonal, one read-back of 16 bytes.  The padding rows add 0 and log 1 = 0; that they do is
+ * checked on the device (an error otherwise).                                                                              */
+int  lpgp_mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]);
+/* out_host[j] = (G^{-1})_jj = sum_{i >= j} (L^{-1})_ij^2,  j < n  (G^{-1} = L^{-T} L^{-1}): `np.diag(gram.inv().todense())` without
+ * the inverse.  Column panel by column panel (option "inverse_diag_panel": a multiple of 128, at most and by default 4 096
+ * columns) the identity is written on the device, solved by the blocked forward substitution of lpgp_trsm_lower against the
+ * TRAILING sub-factor L[j0:, j0:] -- (L^{-1} e_j)[j0:] = (L[j0:, j0:])^{-1} e_{j - j0}, the rows above are zeros -- and reduced to
+ * one sum of squares per column; the n numbers come down once.  n^3 / 3 flop.                                              */
+int  lpgp_mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host);
+/* Leave-one-out predictive distribution of every observation (GPML eqs. 5.10 - 5.12) from w = G^{-1} r (lpgp_solve_weights'
+ * solve; the resident weights of the matrix are not touched) and d = diag(G^{-1}) (lpgp_mat_inverse_diag), fused on the device:
+ *   mean_host[i] = y_i - w_i / d_i,   var_host[i] = 1 / d_i,   logp_host[i] = 1/2 log d_i - 1/2 w_i^2 / d_i - 1/2 log 2 pi
+ * (n doubles each, Gram order; the variance is that of the noisy observation y_i: G carries the noise), and
+ * logp_host[n] = sum_i logp_host[i] in a fixed order: logp_host has n + 1 doubles.  y_host: the observations Y.              */
+int  lpgp_mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host,
+                  double* logp_host);
 
 /* diag of sum_g (kd[g])(x, x): a constant for the stationary kernels supported here     */
 int  lpgp_kernel_diag(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, double* out_value);

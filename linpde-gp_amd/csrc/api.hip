@@ -507,6 +507,10 @@ static const struct { const char* key; int64_t lpgp_ctx::RouteCounts::*count; } 
     ROUTE(ride_done), ROUTE(ride_aug), ROUTE(ride_b2b), ROUTE(ride), ROUTE(ride_vchain), ROUTE(ride_two), ROUTE(ride_outer),
     ROUTE(solve_two_level), ROUTE(solve_ahead), ROUTE(solve_tiles)};
 #undef ROUTE
+// the context state of evidence.hip, beside the option table like the rows above: the panel width of the inverse diagonal (the
+// one key of these that lpgp_set_option takes) and the byte counters of its copies
+static const struct { const char* key; int64_t lpgp_ctx::*field; } kEvidence[] = {
+    {"inverse_diag_panel", &lpgp_ctx::inverse_diag_panel}, {"evidence_h2d_bytes", &lpgp_ctx::evidence_h2d_bytes}, {"evidence_d2h_bytes", &lpgp_ctx::evidence_d2h_bytes}};
 
 int lpgp_get_option(lpgp_ctx* ctx, const char* key, int64_t* value) {
   LPGP_CHECK(ctx && key && value, "lpgp_get_option: null argument");
@@ -521,11 +525,21 @@ int lpgp_get_option(lpgp_ctx* ctx, const char* key, int64_t* value) {
       *value = ctx->route.*r.count;
       return 0;
     }
+  for (const auto& r : kEvidence)
+    if (std::strcmp(key, r.key) == 0) {
+      *value = ctx->*r.field;
+      return 0;
+    }
   return rc;       // (unknown option <key>, set by option_get)
 }
 
 int lpgp_set_option(lpgp_ctx* ctx, const char* key, int64_t value) {
   LPGP_DEVICE(ctx);
+  if (key && std::strcmp(key, kEvidence[0].key) == 0) {
+    LPGP_CHECK(value >= TILE && value <= 4096 && value % TILE == 0, "inverse_diag_panel must be a multiple of %d in %d .. 4096", TILE, TILE);
+    ctx->inverse_diag_panel = value;
+    return 0;
+  }
   return option_set(*ctx, key, value);
 }
 
@@ -1740,6 +1754,33 @@ int lpgp_mat_factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, i
   LPGP_CHECK(!mat->unchecked, "lpgp_mat_factor_matmul: the status of an enqueued factorisation has not been read (lpgp_mat_check)");
   return factor_matmul(ctx, mat, Z_host, s, shift_host, out_host);
 }
+
+// the state every entry point of evidence.hip asks for: the checks of lpgp_mat_factor_matmul
+#define LPGP_EVIDENCE_READY(fn)                                                                                                             \
+  LPGP_DEVICE(ctx);                                                                                                                         \
+  LPGP_MAT_ALIVE(mat, fn);                                                                                                                  \
+  LPGP_CHECK(!ctx->distributed(), fn ": single GPU only");                                                                                  \
+  LPGP_CHECK(mat->pn > 0 && mat->pn_fact == mat->pn, fn ": matrix is not (fully) factored");                                                \
+  LPGP_CHECK(!mat->unchecked, fn ": the status of an enqueued factorisation has not been read (lpgp_mat_check)")
+
+int lpgp_mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]) {
+  LPGP_CHECK(ctx && mat && r_host && out_host, "lpgp_mat_evidence: null argument");
+  LPGP_EVIDENCE_READY("lpgp_mat_evidence");
+  return mat_evidence(ctx, mat, r_host, out_host);
+}
+
+int lpgp_mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host) {
+  LPGP_CHECK(ctx && mat && out_host, "lpgp_mat_inverse_diag: null argument");
+  LPGP_EVIDENCE_READY("lpgp_mat_inverse_diag");
+  return mat_inverse_diag(ctx, mat, out_host);
+}
+
+int lpgp_mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host, double* logp_host) {
+  LPGP_CHECK(ctx && mat && r_host && y_host && mean_host && var_host && logp_host, "lpgp_mat_loo: null argument");
+  LPGP_EVIDENCE_READY("lpgp_mat_loo");
+  return mat_loo(ctx, mat, r_host, y_host, mean_host, var_host, logp_host);
+}
+#undef LPGP_EVIDENCE_READY
 
 int lpgp_gemm_host(lpgp_ctx* ctx, int32_t transa, int32_t transb, int64_t m, int64_t n, int64_t k, double alpha,
                    const double* A_host, const double* B_host, double beta, double* C_host) {

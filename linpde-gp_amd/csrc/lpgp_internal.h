@@ -112,6 +112,11 @@ struct lpgp_ctx : lpgp::Options {     // tuning options: options.h
   } route;
   hipEvent_t ev_panel[2] = {nullptr, nullptr};
   hipEvent_t ev_upd[2] = {nullptr, nullptr};
+  // lpgp_mat_inverse_diag / lpgp_mat_loo (evidence.hip): columns of the identity solved at a time (a multiple of 128, at most 4 096: the
+  // right-hand side takes 8 n x this many bytes), and the bytes these entry points and lpgp_mat_evidence have copied up and down --
+  // option "inverse_diag_panel" and the read-only keys "evidence_h2d_bytes" / "evidence_d2h_bytes" of lpgp_get_option
+  int64_t inverse_diag_panel = 4096;
+  int64_t evidence_h2d_bytes = 0, evidence_d2h_bytes = 0;
   int panel_lds_extra = 0;         // bytes of LDS a fused panel launch asks for beyond its own 69 632 (set by the two-level forward substitution around its launches)
   // workspace
   // descriptor ring: an assembly launch copies its lowered descriptor into a pinned host slot,
@@ -447,6 +452,11 @@ int trsm_lower_t_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, int
 int solve_vec(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, double* tmp, int* info);
 int solve_vec_resident(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, double* tmp, int* info);      // trsv.hip
 int solve_vec_fwd(lpgp_ctx* ctx, hipStream_t st, lpgp_mat* mat, int64_t T, double* b, double* x);
+int solve_vec_fwd_resident(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, const double* b, double* x, int* info);   // trsv.hip: the forward half alone
+// evidence.hip: the quantities read off the factor of a fully factored single-GPU matrix (lpgp_mat_evidence, lpgp_mat_inverse_diag, lpgp_mat_loo)
+int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]);
+int mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host);
+int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host, double* logp_host);
 // trmm.hip: out (n x s, C-order, logical rows) = shift[:, None] + L Z for the lower factor of a fully factored single-GPU matrix
 int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host, double* out_host);
 

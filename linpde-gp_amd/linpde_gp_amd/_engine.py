@@ -457,6 +457,33 @@ class GramMatrix:
               "lpgp_mat_factor_matmul")
         return out
 
+    def evidence(self, r: np.ndarray) -> "tuple[float, float]":
+        """(r^T G^{-1} r, log det G) from the resident factor (`lpgp_mat_evidence`, csrc/evidence.hip): 16 bytes come back."""
+        r = np.ascontiguousarray(r, dtype=np.double)
+        if r.shape != (self.n,):
+            raise ValueError(f"residual must have shape ({self.n},), got {r.shape}")
+        out = np.empty(2)
+        check(lib.lpgp_mat_evidence(self.ctx._h, self._h, as_pd(r), as_pd(out)), "lpgp_mat_evidence")
+        return float(out[0]), float(out[1])
+
+    def inverse_diag(self) -> np.ndarray:
+        """diag(G^{-1}) without the inverse (`lpgp_mat_inverse_diag`): n numbers come back."""
+        out = np.empty(self.n)
+        check(lib.lpgp_mat_inverse_diag(self.ctx._h, self._h, as_pd(out)), "lpgp_mat_inverse_diag")
+        return out
+
+    def loo(self, r: np.ndarray, y: np.ndarray):
+        """Leave-one-out (mean, variance, log predictive density, sum of the densities) of every observation
+        (`lpgp_mat_loo`); `r` the residual the representer weights use, `y` the observations, both in Gram order."""
+        n = self.n
+        r = np.ascontiguousarray(r, dtype=np.double)
+        y = np.ascontiguousarray(y, dtype=np.double)
+        if r.shape != (n,) or y.shape != (n,):
+            raise ValueError(f"residual and observations must have shape ({n},), got {r.shape} and {y.shape}")
+        mean, var, logp = np.empty(n), np.empty(n), np.empty(n + 1)
+        check(lib.lpgp_mat_loo(self.ctx._h, self._h, as_pd(r), as_pd(y), as_pd(mean), as_pd(var), as_pd(logp)), "lpgp_mat_loo")
+        return mean, var, logp[:n].copy(), float(logp[n])
+
     def potrf_enqueue(self) -> None:
         """The factorisation enqueued, no host synchronisation (`lpgp_potrf_enqueue`): its status is read by `check`."""
         check(lib.lpgp_potrf_enqueue(self.ctx._h, self._h), "lpgp_potrf_enqueue")

@@ -313,6 +313,12 @@ class RemoteConditionalGaussianProcess:
     def sample(self, rng, x, size=(), *, damping=None):
         raise NotImplementedError("`sample` is not available through the `lp.spawn` multi-GPU front (single GPU only)")
 
+    def log_marginal_likelihood(self):
+        raise NotImplementedError("`log_marginal_likelihood` is not available through the `lp.spawn` multi-GPU front (single GPU only)")
+
+    def leave_one_out(self):
+        raise NotImplementedError("`leave_one_out` is not available through the `lp.spawn` multi-GPU front (single GPU only)")
+
     @property
     def cov(self):
         return _RemoteCov(self)

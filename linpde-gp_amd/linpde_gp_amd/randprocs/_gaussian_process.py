@@ -311,6 +311,15 @@ class _GramInverse:
     def todense(self):
         return self._gram.solve(np.eye(self.shape[0]))
 
+    def diagonal(self) -> np.ndarray:
+        """diag(G^{-1}) from the resident factor (`lpgp_mat_inverse_diag`): neither the identity nor the inverse visits the host."""
+        cgp = self._gram._cgp
+        if not cgp._blocks:
+            return np.zeros(0)
+        _evidence_context("gram.inv().diagonal")
+        cgp._check_current()
+        return cgp._state.mat.inverse_diag()
+
 
 class _DeviceState:
     """Device-resident state shared along a chain of conditionings: ONE matrix whose leading
@@ -390,6 +399,35 @@ class _DeviceState:
             self.view = nblocks
             self.weights_key = None
             self.residual_key = None
+
+
+def _evidence_context(what: str):
+    from .. import _spawn
+    if _spawn.active() is not None:
+        raise NotImplementedError(f"`{what}` is not available through the `lp.spawn` multi-GPU front (single GPU only)")
+    ctx = _engine.default_context()
+    if ctx.distributed:
+        raise NotImplementedError(f"`{what}` is not available in a multi-GPU job (single GPU only)")
+    return ctx
+
+
+class LeaveOneOut:
+    """Result of `ConditionalGaussianProcess.leave_one_out()`: per observation, in Gram order (conditioning order, each block
+    flattened in C order), the predictive distribution of the NOISY observation y_i given all the others -- `mean`, `var`
+    (the observation's own `b` variance included), `std` -- its log density at the observed value, `log_predictive_density`,
+    and `total`, the sum of the densities (the leave-one-out pseudo-likelihood)."""
+
+    __slots__ = ("mean", "var", "log_predictive_density", "total")
+
+    def __init__(self, mean, var, log_predictive_density, total):
+        self.mean, self.var, self.log_predictive_density, self.total = mean, var, log_predictive_density, float(total)
+
+    @property
+    def std(self) -> np.ndarray:
+        return np.sqrt(np.maximum(self.var, 0.0))
+
+    def __repr__(self):
+        return f"LeaveOneOut(n={self.mean.size}, total={self.total:.6g})"
 
 
 _ROWS_SEEN_MAX = 4096        # (a hint only, and only where re-allocation matters: 128 MB; beyond, a copy is noise against the O(n^3) work)
@@ -746,6 +784,31 @@ class ConditionalGaussianProcess(GaussianProcess):
 
     def var(self, x):
         return self.predict(x, return_var=True)[1]
+
+    def log_marginal_likelihood(self) -> float:
+        """log p(Y) = -1/2 r^T G^{-1} r - 1/2 log det G - n/2 log 2 pi of the observations this posterior was conditioned on,
+        r = Y - L[m] - b.mean over all its blocks (the residual of the representer weights), G the Gram matrix with the
+        noise.  Read off the resident factor (`lpgp_mat_evidence`): one forward solve and one reduction on the device, 16
+        bytes back.  An earlier posterior of a chain answers for its own blocks (through its view).  Lazy mode: deferred
+        factorisations are flushed and verified first, as `mean` does; a dropped block raises `LinAlgError`."""
+        if not self._blocks:
+            return 0.0
+        _evidence_context("log_marginal_likelihood")
+        self._check_current()
+        r = self._residual()
+        quad, logdet = self._state.mat.evidence(r)
+        return float(-0.5 * quad - 0.5 * logdet - 0.5 * r.size * np.log(2.0 * np.pi))
+
+    def leave_one_out(self) -> "LeaveOneOut":
+        """Leave-one-out predictive distribution of every observation (`LeaveOneOut`): mean_i = y_i - w_i / d_i, var_i = 1 / d_i,
+        log p_i = 1/2 log d_i - 1/2 w_i^2 / d_i - 1/2 log 2 pi with w = G^{-1} r and d = diag(G^{-1}), all formed on the device
+        (`lpgp_mat_loo`; O(n) numbers cross the bus).  Shows which collocation or boundary points the model explains badly.
+        Flushes, verifies and raises as `log_marginal_likelihood`."""
+        if not self._blocks:
+            return LeaveOneOut(np.zeros(0), np.zeros(0), np.zeros(0), 0.0)
+        _evidence_context("leave_one_out")
+        self._check_current()
+        return LeaveOneOut(*self._state.mat.loo(self._residual(), np.concatenate([ob.Y for ob in self._blocks])))
 
     def sample(self, rng, x, size=(), *, damping=None):
         """Joint draws of the posterior (of the read-out `D(u)` if this object is one) at the points `x`.

@@ -423,6 +423,12 @@ class MatrixFreeConditionalGaussianProcess:
     def sample(self, rng, x, size=(), *, damping=None):
         raise NotImplementedError("`sample` needs the dense factorisation: a matrix-free posterior has no Cholesky factor to draw with")
 
+    def log_marginal_likelihood(self):
+        raise NotImplementedError("`log_marginal_likelihood` needs the dense factorisation: a matrix-free posterior has no Cholesky factor to read the determinant off")
+
+    def leave_one_out(self):
+        raise NotImplementedError("`leave_one_out` needs the dense factorisation: a matrix-free posterior has no Cholesky factor to form diag(G^-1) with")
+
     @property
     def cov(self):
         return _MatrixFreeCovariance(self)

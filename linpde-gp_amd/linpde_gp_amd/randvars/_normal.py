@@ -105,6 +105,47 @@ class Normal:
             self._cov_cholesky = C
         return C
 
+    def logpdf(self, x):
+        """Log density at `x` (probnum `Normal.logpdf`): `x` of shape batch + self.shape, result of shape batch.
+        -1/2 (x - mean)^T cov^{-1} (x - mean) - 1/2 log det cov - n/2 log 2 pi.  Scalar and diagonal covariances in closed form
+        on the host (O(n), no device call); a dense covariance through its factored device matrix (`lpgp_mat_evidence`: one
+        forward solve and one reduction per point of the batch)."""
+        x = np.asarray(x, dtype=np.double)
+        shape = tuple(self._mean.shape)
+        nd = len(shape)
+        if x.shape[x.ndim - nd:] != shape:
+            raise ValueError(f"`x` has shape {x.shape}, expected batch + {shape}")
+        batch = x.shape[:x.ndim - nd]
+        n = self._mean.size
+        r = (x - self._mean).reshape(batch + (n,))
+        if nd == 0 or self._cov_diag is not None:
+            var = np.reshape(self._cov, (1,)) if nd == 0 else self._cov_diag
+            if np.any(var <= 0.0):
+                raise np.linalg.LinAlgError("the covariance is not positive definite")
+            return -0.5 * np.sum(r * r / var, axis=-1) - 0.5 * np.sum(np.log(var)) - 0.5 * n * np.log(2.0 * np.pi)
+        if n == 0:
+            return np.zeros(batch)
+        S = self._device_factor()
+        out = np.empty(batch)
+        for idx in np.ndindex(*batch):
+            quad, logdet = S.evidence(np.ascontiguousarray(r[idx]))
+            out[idx] = -0.5 * quad - 0.5 * logdet - 0.5 * n * np.log(2.0 * np.pi)
+        return out[()]
+
+    @property
+    def entropy(self) -> float:
+        """Differential entropy n/2 (1 + log 2 pi) + 1/2 log det cov (probnum `Normal.entropy`); the determinant of a dense
+        covariance from the diagonal of its device factor (`lpgp_mat_evidence`)."""
+        n = self._mean.size
+        if self._mean.ndim == 0 or self._cov_diag is not None:
+            var = np.reshape(self._cov, (1,)) if self._mean.ndim == 0 else self._cov_diag
+            if np.any(var <= 0.0):
+                raise np.linalg.LinAlgError("the covariance is not positive definite")
+            logdet = float(np.sum(np.log(var)))
+        else:
+            logdet = self._device_factor().evidence(np.zeros(n))[1] if n else 0.0
+        return float(0.5 * n * (1.0 + np.log(2.0 * np.pi)) + 0.5 * logdet)
+
     def sample(self, rng, size=()):
         """Draws of shape size + self.shape (probnum `Normal.sample(rng, size)`).  THE RANDOM STREAM IS PART OF THE CONTRACT:
         exactly one call `z = rng.standard_normal(size + self.shape)` and `draw[s] = mean + C z[s]` with the lower Cholesky
