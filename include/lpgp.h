@@ -61,6 +61,10 @@ typedef struct {
   double    scale;
   int32_t   nterms;
   lpgp_term terms[LPGP_MAXT];
+  /* 0: the kernel itself.  j + 1: its derivative with respect to log lengthscale[j] -- the form above is closed under it
+   * (csrc/lower.cpp), so every assembly / product entry point evaluates d G / d log l_j like any other block.  Product-form
+   * families only (LPGP_MATERN_ISO is refused).  A zero-initialised descriptor keeps its meaning.                        */
+  int32_t   dlog_lengthscale;
 } lpgp_kdesc;
 
 /* ---- context ------------------------------------------------------------------------
@@ -196,7 +200,8 @@ int  lpgp_gram_assemble_grid(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroup
                              const lpgp_pts* const* F0, const lpgp_pts* const* F1,
                              lpgp_mat* mat, int32_t bi, int32_t bj);
 /* 1 if lpgp_gram_assemble_grid holds this sum (its tables of terms and of distinct 1-D matrices are fixed-size kernel
- * arguments: 48 terms over all summands, 16 distinct 1-D matrices per dimension; product-form kernels only), 0 if the
+ * arguments: 48 terms over all summands, 16 distinct 1-D matrices per dimension; product-form kernels only, no summand with
+ * dlog_lengthscale != 0), 0 if the
  * caller must assemble the block entry-wise from the flattened grids (lpgp_gram_assemble).                              */
 int  lpgp_kron_fits(const lpgp_kdesc* kd, int32_t ngroups);
 /* diagonal of block bi += v_host[i] (v_host may be NULL) + scalar                       */
@@ -389,6 +394,29 @@ int  lpgp_mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host);
  * logp_host[n] = sum_i logp_host[i] in a fixed order: logp_host has n + 1 doubles.  y_host: the observations Y.              */
 int  lpgp_mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host,
                   double* logp_host);
+
+/* ---- gradient of the log marginal likelihood with respect to a hyperparameter theta (csrc/evidence_grad.hip):
+ *        d/d theta log p(y) = 1/2 w^T (dG/d theta) w - 1/2 tr(G^{-1} dG/d theta),   w = G^{-1} r      (GPML eq. 5.9).
+ *      dG/d theta is an ordinary assembled matrix: the block rows of the chain replayed into a scratch matrix with a derived
+ *      descriptor (one summand alone: d/d log scale; lpgp_kdesc.dlog_lengthscale: d/d log lengthscale) and no noise
+ *      (lpgp_mat_condition with lazy == 2 assembles without factoring).  All three: a fully factored matrix or view, single GPU,
+ *      the refusals of lpgp_mat_evidence; the same bits on every call.                                                      */
+/* *out = a NEW device matrix with the block layout of the blocks `mat` currently views whose lower triangle holds G^{-1} (GPML eq.
+ * 5.9 needs all of it, not only its diagonal; lpgp_mat_destroy).  From the resident factor: W = L^{-1} column panel by column panel
+ * (identity panels against the trailing sub-factors, option "inverse_diag_panel", as lpgp_mat_inverse_diag), then G^{-1} = W^T W on
+ * the fp64 MFMA kernel; 2 n^3 / 3 flop, one temporary of 8 n^2 bytes.  `mat` is unchanged.  The padding rows and columns of
+ * *out are the identity's; it is not a factor (lpgp_mat_to_host with what = 0 reads it).                                    */
+int  lpgp_mat_inverse(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat** out);
+/* out_host = ( w^T dG w,  tr(G^{-1} dG) ) of GPML eq. 5.9 with w = G^{-1} r solved on the device as lpgp_mat_evidence does; ginv from
+ * lpgp_mat_inverse(mat), dG an assembled, UNFACTORED matrix, both with mat's block layout.  One streaming pass over the two lower
+ * triangles (8 n^2 bytes, 16-byte loads, off-diagonal entries counted twice) and a second small kernel that adds the partial sums
+ * in a fixed order; the identity tails of the padding are masked by the logical row map.  16 bytes come back.              */
+int  lpgp_mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host, double out_host[2]);
+/* The same pair of GPML eq. 5.9 for dG = diag(v_host) + scalar I on block bi and zero elsewhere (v_host: n_bi doubles or NULL) -- the
+ * derivative by the log of a noise variance: sum v_i w_i^2 and sum v_i (G^{-1})_ii, no second n^2 matrix.  A dense noise covariance
+ * goes through lpgp_mat_add_dense into a scratch matrix and lpgp_mat_evidence_grad.                                         */
+int  lpgp_mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, int32_t bi, const double* v_host, double scalar,
+                                 const double* r_host, double out_host[2]);
 
 /* diag of sum_g (kd[g])(x, x): a constant for the stationary kernels supported here     */
 int  lpgp_kernel_diag(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, double* out_value);

@@ -959,6 +959,7 @@ int lpgp_gram_assemble_grid(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups
   LPGP_CHECK(sym == (bi == bj), "lpgp_gram_assemble_grid: F1 must be NULL exactly for diagonal blocks");
   const int D = kd[0].d;
   LPGP_CHECK(D >= 1 && D <= LPGP_MAXD, "lpgp_gram_assemble_grid: d=%d", D);
+  LPGP_CHECK(kron_fits(kd, ngroups), "lpgp_gram_assemble_grid: the Kronecker path does not hold this sum (lpgp_kron_fits tells beforehand)");
   const double *f0[LPGP_MAXD], *f1[LPGP_MAXD];
   int64_t n0d[LPGP_MAXD], n1d[LPGP_MAXD], n0 = 1, n1 = 1;
   for (int d = 0; d < D; ++d) {
@@ -1779,6 +1780,52 @@ int lpgp_mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const doubl
   LPGP_CHECK(ctx && mat && r_host && y_host && mean_host && var_host && logp_host, "lpgp_mat_loo: null argument");
   LPGP_EVIDENCE_READY("lpgp_mat_loo");
   return mat_loo(ctx, mat, r_host, y_host, mean_host, var_host, logp_host);
+}
+
+// `other` (the dense inverse, an assembled derivative) lies over the blocks `mat` views: same context, same block layout, not factored
+static int evidence_grad_layout(const lpgp_mat* mat, const lpgp_mat* other, const char* fn, const char* what) {
+  LPGP_CHECK(other->ctx == mat->ctx && !other->poisoned, "%s: %s belongs to another context or is undefined", fn, what);
+  LPGP_CHECK(other->pn == mat->pn && other->blocks.size() == mat->blocks.size() && other->hidden.empty(),
+             "%s: %s has another block layout than the matrix (%lld padded rows in %d blocks against %lld in %d)", fn, what, (long long)other->pn,
+             (int)other->blocks.size(), (long long)mat->pn, (int)mat->blocks.size());
+  for (size_t b = 0; b < mat->blocks.size(); ++b)
+    LPGP_CHECK(other->blocks[b].n == mat->blocks[b].n && other->blocks[b].poff == mat->blocks[b].poff,
+               "%s: block %d of %s has %lld rows, the matrix has %lld", fn, (int)b, what, (long long)other->blocks[b].n, (long long)mat->blocks[b].n);
+  LPGP_CHECK(other->pn_fact == 0, "%s: %s must not be factored", fn, what);
+  return 0;
+}
+
+int lpgp_mat_inverse(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat** out) {
+  LPGP_CHECK(ctx && mat && out, "lpgp_mat_inverse: null argument");
+  LPGP_EVIDENCE_READY("lpgp_mat_inverse");
+  lpgp_mat* created = nullptr;
+  LPGP_TRY(lpgp_mat_create(ctx, mat->pn, &created));
+  std::unique_ptr<lpgp_mat, Destroy> m(created);
+  m->blocks = mat->blocks;
+  m->n = mat->n;
+  m->pn = mat->pn;
+  m->pn_fact = 0;                                // (a plain symmetric matrix in the lower triangle, not a factor)
+  LPGP_TRY(mat_inverse_into(ctx, mat, m.get()));
+  LPGP_HIP(hipStreamSynchronize(ctx->s_main));   // (a failure of the device work is reported here, with the handle still owned)
+  *out = m.release();
+  return 0;
+}
+
+int lpgp_mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host, double out_host[2]) {
+  LPGP_CHECK(ctx && mat && ginv && dG && r_host && out_host, "lpgp_mat_evidence_grad: null argument");
+  LPGP_EVIDENCE_READY("lpgp_mat_evidence_grad");
+  LPGP_TRY(evidence_grad_layout(mat, ginv, "lpgp_mat_evidence_grad", "the inverse"));
+  LPGP_TRY(evidence_grad_layout(mat, dG, "lpgp_mat_evidence_grad", "the derivative"));
+  return mat_evidence_grad(ctx, mat, ginv, dG, r_host, out_host);
+}
+
+int lpgp_mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, int32_t bi, const double* v_host, double scalar,
+                                const double* r_host, double out_host[2]) {
+  LPGP_CHECK(ctx && mat && ginv && r_host && out_host, "lpgp_mat_evidence_grad_diag: null argument");
+  LPGP_EVIDENCE_READY("lpgp_mat_evidence_grad_diag");
+  LPGP_CHECK(bi >= 0 && bi < (int32_t)mat->blocks.size(), "lpgp_mat_evidence_grad_diag: bad block %d", bi);
+  LPGP_TRY(evidence_grad_layout(mat, ginv, "lpgp_mat_evidence_grad_diag", "the inverse"));
+  return mat_evidence_grad_diag(ctx, mat, ginv, bi, v_host, scalar, r_host, out_host);
 }
 #undef LPGP_EVIDENCE_READY
 

@@ -1111,6 +1111,7 @@ bool kron_fits(const lpgp_kdesc* kd, int ngroups) {
   for (int g = 0; g < ngroups; ++g) {
     const lpgp_kdesc& K = kd[g];
     if (K.d != D || K.family[0] == LPGP_MATERN_ISO || K.nterms < 0 || K.nterms > LPGP_MAXT) return false;
+    if (K.dlog_lengthscale != 0) return false;   // a lengthscale derivative (lower.cpp) is assembled entry-wise: the 1-D factor matrices are built from plain factors
     nterms += K.nterms;
     if (nterms > KR_MAXT) return false;
     for (int t = 0; t < K.nterms; ++t)

@@ -5,7 +5,9 @@
 // the CPU box (GPU AddressSanitizer is not available).  tests/test_host_asan.py drives it
 // over the descriptor zoo and compares with the oracle.  The option table of options.cpp is in it too
 // (tests/test_host_options.py).
+#include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "../eval_entries.h"
@@ -107,6 +109,32 @@ int lpgp_host_kernel_diag(const lpgp_kdesc* kd, int32_t ngroups, double* out_val
   if (rc != 0) return rc;
   *out_value = desc_diag(store[0]);
   return 0;
+}
+
+// sizeof(lpgp_kdesc) as the C compiler lays it out (the ctypes mirror `_lib.KDesc` must agree)
+int64_t lpgp_host_sizeof_kdesc(void) { return (int64_t)sizeof(lpgp_kdesc); }
+
+// The lowered descriptor as bytes: the header and the groups (everything in front of the coefficient table), then the coefficients
+// in use.  Returns the number of bytes (written only if they fit into cap), < 0 on a lowering error.
+int64_t lpgp_host_lower_bytes(const lpgp_kdesc* kd, int32_t ngroups, unsigned char* out, int64_t cap) {
+  std::vector<DevDesc> store(1);
+  int rc = lower_kdesc(kd, ngroups, &store[0]);
+  if (rc != 0) return rc;
+  const DevDesc& d = store[0];
+  int64_t used = 0;
+  for (int g = 0; g < d.ngroups; ++g) {
+    const DevGroup& G = d.g[g];
+    int64_t len = 1;
+    for (int j = 0; j < d.d; ++j) len *= G.deg[j] + 1;
+    if (G.iso) len = G.deg[0] + 1;
+    for (int c = 0; c < G.ncls; ++c) used = used > G.coef_off[c] + len ? used : G.coef_off[c] + len;
+  }
+  const int64_t head = (int64_t)offsetof(DevDesc, coef), total = head + used * (int64_t)sizeof(double);
+  if (total <= cap) {
+    std::memcpy(out, &d, (size_t)head);
+    std::memcpy(out + head, d.coef, (size_t)(used * (int64_t)sizeof(double)));
+  }
+  return total;
 }
 
 // out[i] = lpgp_exp_neg(s[i]): the per-entry exponential of the assembly kernels (eval_entries.h), host instantiation

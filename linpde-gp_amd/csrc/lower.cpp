@@ -72,6 +72,8 @@ static long double matern_poly_num(int p, int n, long double* num /* p+1 */) {
 //   d/dx_i d/dx'_j k = -[ a_i a_j u_i u_j (P_2 - P_1/s)/s^2 + a_i^2 delta_ij P_1/s ] e^{-s}
 // summed over the term list into  e^{-s} [Q0(s) + (w.u) Q1(s) + (u^T B u) Q2(s)].
 static int lower_iso_group(const lpgp_kdesc& K, int d, DevGroup& G, double* coef, int& coef_used) {
+  LPGP_CHECK(K.dlog_lengthscale == 0,
+             "lower_kdesc: the derivative with respect to a lengthscale is not implemented for the isotropic Matern (LPGP_MATERN_ISO)");
   const int p = K.p[0];
   LPGP_CHECK(p >= 0 && p <= 6, "lower_kdesc: Matern p=%d unsupported", p);
   long double a[LPGP_MAXD];
@@ -150,6 +152,21 @@ static int lower_iso_group(const lpgp_kdesc& K, int d, DevGroup& G, double* coef
   return 0;
 }
 
+// d / d log lengthscale of one Matern factor of total order n (lpgp_kdesc::dlog_lengthscale).  The factor a^n e^{-r} P_n(r),
+// r = a |x - x'|, depends on the lengthscale through a ~ 1 / lengthscale alone, and
+//   d/d log a [a^n e^{-r} P_n(r)] = a^n e^{-r} [n P_n(r) + r (P_n' - P_n)(r)] = a^n e^{-r} [n P_n(r) + r P_{n+1}(r)]:
+// the same form with one more degree.  out (p + 2 coefficients) = -(n P_n + r P_{n+1}), from the exact integer numerators,
+// rounded to double once per coefficient.
+static void matern_poly_dlog(int p, int n, long double* out /* p+2 */) {
+  long double a[16], b[16];
+  const long double D = matern_poly_num(p, n, a);
+  matern_poly_num(p, n + 1, b);
+  for (int k = 0; k <= p + 1; ++k) {
+    const long double num = (k <= p ? n * a[k] : 0.0L) + (k >= 1 ? b[k - 1] : 0.0L);
+    out[k] = (long double)(double)(-num / D);
+  }
+}
+
 // Probabilists' Hermite He_n, ascending coefficients, degree n.
 static void hermite_poly(int n, long double* out /* n+1 */) {
   long double a[16] = {1}, b[16];
@@ -162,6 +179,16 @@ static void hermite_poly(int n, long double* out /* n+1 */) {
     for (int k = 0; k <= deg; ++k) a[k] = b[k];
   }
   for (int k = 0; k <= n; ++k) out[k] = a[k];
+}
+
+// The same for an ExpQuad factor a^n e^{-u^2/2} He_n(u), u = a (x - x'):  d/du [e^{-u^2/2} He_n] = -e^{-u^2/2} He_{n+1}, so
+//   d/d log a [a^n e^{-u^2/2} He_n(u)] = a^n e^{-u^2/2} [n He_n(u) - u He_{n+1}(u)]  (parity n, degree n + 2).
+// out (n + 3 coefficients) = -(n He_n - u He_{n+1}); integers, exact.
+static void hermite_poly_dlog(int n, long double* out /* n+3 */) {
+  long double a[16], b[16];
+  hermite_poly(n, a);
+  hermite_poly(n + 1, b);
+  for (int k = 0; k <= n + 2; ++k) out[k] = (k >= 1 ? b[k - 1] : 0.0L) - (k <= n ? n * a[k] : 0.0L);
 }
 
 int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out) {
@@ -183,6 +210,9 @@ int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out) {
       if (rc != 0) return rc;
       continue;
     }
+    LPGP_CHECK(K.dlog_lengthscale >= 0 && K.dlog_lengthscale <= d, "lower_kdesc: dlog_lengthscale=%d out of range (0 .. d=%d)",
+               K.dlog_lengthscale, d);
+    const int jd = K.dlog_lengthscale - 1;       // the dimension whose factor is differentiated by its log lengthscale (-1: none)
     long double a[LPGP_MAXD];
     for (int j = 0; j < d; ++j) {
       LPGP_CHECK(K.lengthscale[j] > 0, "lower_kdesc: lengthscale must be positive");
@@ -208,6 +238,7 @@ int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out) {
         LPGP_CHECK(K.terms[t].n0[j] >= 0 && K.terms[t].n1[j] >= 0 && n <= 12,
                    "lower_kdesc: derivative order out of range");
         int dg = (K.family[j] == LPGP_MATERN_HALFINT) ? K.p[j] : n;
+        if (j == jd) dg += (K.family[j] == LPGP_MATERN_HALFINT) ? 1 : 2;
         if (dg > deg) deg = dg;
       }
       G.deg[j] = deg;
@@ -228,12 +259,14 @@ int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out) {
         pref *= std::pow(a[j], n);
         if (K.family[j] == LPGP_MATERN_HALFINT) {
           if (T.n1[j] & 1) pref = -pref;
-          matern_poly(K.p[j], n, q[j]);
-          qdeg[j] = K.p[j];
+          if (j == jd) matern_poly_dlog(K.p[j], n, q[j]);
+          else matern_poly(K.p[j], n, q[j]);
+          qdeg[j] = K.p[j] + (j == jd ? 1 : 0);
         } else {
           if (T.n0[j] & 1) pref = -pref;
-          hermite_poly(n, q[j]);
-          qdeg[j] = n;
+          if (j == jd) hermite_poly_dlog(n, q[j]);
+          else hermite_poly(n, q[j]);
+          qdeg[j] = n + (j == jd ? 2 : 0);
         }
       }
       auto& C = cls[parity];

@@ -457,6 +457,12 @@ int solve_vec_fwd_resident(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, const double
 int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]);
 int mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host);
 int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host, double* logp_host);
+// evidence_grad.hip: the dense inverse W^T W, W = L^{-1}, into the lower triangle of `out` (same block layout, not factored), and the
+// pair (w^T dG w, tr(G^{-1} dG)) of GPML eq. 5.9 for an assembled dG / for dG = diag(v) + scalar I on block bi
+int mat_inverse_into(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat* out);
+int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host, double out_host[2]);
+int mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, int32_t bi, const double* v_host, double scalar, const double* r_host,
+                           double out_host[2]);
 // trmm.hip: out (n x s, C-order, logical rows) = shift[:, None] + L Z for the lower factor of a fully factored single-GPU matrix
 int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host, double* out_host);
 

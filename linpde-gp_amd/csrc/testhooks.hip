@@ -233,4 +233,18 @@ int lpgp_test_force_status(lpgp_ctx* ctx, lpgp_mat* mat, int32_t value) {
   return 0;
 }
 
+// the raw storage of the view of `mat` -- pn x pn doubles, column-major, leading dimension pn, padding rows and the tiles above the
+// diagonal included -- read (set == 0) or overwritten (set != 0): what the padded layout holds, and operands with garbage in the padding.
+// Declared by its one caller (tests/test_gpu_evidence_grad.py binds it itself), not in include/lpgp_test.h.
+int lpgp_test_mat_raw(lpgp_ctx* ctx, lpgp_mat* mat, int32_t set, double* host) {
+  LPGP_CHECK(ctx && mat && host && mat->pn > 0, "lpgp_test_mat_raw: bad argument");
+  LPGP_DEVICE(ctx);
+  LPGP_CHECK(!ctx->distributed(), "lpgp_test_mat_raw: single GPU only");
+  LPGP_HIP(hipStreamSynchronize(ctx->s_main));
+  const size_t row = (size_t)mat->pn * sizeof(double), ld = (size_t)mat->lr_cap * sizeof(double);
+  if (set) LPGP_HIP(hipMemcpy2D(mat->a, ld, host, row, row, (size_t)mat->pn, hipMemcpyHostToDevice));
+  else LPGP_HIP(hipMemcpy2D(host, row, mat->a, ld, row, (size_t)mat->pn, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 }  // extern "C"

@@ -484,6 +484,37 @@ class GramMatrix:
         check(lib.lpgp_mat_loo(self.ctx._h, self._h, as_pd(r), as_pd(y), as_pd(mean), as_pd(var), as_pd(logp)), "lpgp_mat_loo")
         return mean, var, logp[:n].copy(), float(logp[n])
 
+    def inverse(self) -> "GramMatrix":
+        """G^{-1} of the blocks in view as a device matrix of its own with the same block layout, lower triangle (`lpgp_mat_inverse`:
+        W = L^{-1} panel by panel, then W^T W on the MFMA kernel); this matrix is unchanged.  `todense()` reads it."""
+        h = C.c_void_p()
+        check(lib.lpgp_mat_inverse(self.ctx._h, self._h, C.byref(h)), "lpgp_mat_inverse")
+        return GramMatrix(self.ctx, _handle=h, _block_sizes=self.block_sizes[:self.num_blocks])
+
+    def evidence_grad(self, ginv: "GramMatrix", dG: "GramMatrix", r: np.ndarray) -> "tuple[float, float]":
+        """(w^T dG w, tr(G^{-1} dG)), w = G^{-1} r: the two terms of GPML eq. 5.9 (`lpgp_mat_evidence_grad`, csrc/evidence_grad.hip).
+        `ginv` = `inverse()`, `dG` an assembled, unfactored matrix of the same block layout; 16 bytes come back."""
+        r = np.ascontiguousarray(r, dtype=np.double)
+        if r.shape != (self.n,):
+            raise ValueError(f"residual must have shape ({self.n},), got {r.shape}")
+        out = np.empty(2)
+        check(lib.lpgp_mat_evidence_grad(self.ctx._h, self._h, ginv._h, dG._h, as_pd(r), as_pd(out)), "lpgp_mat_evidence_grad")
+        return float(out[0]), float(out[1])
+
+    def evidence_grad_diag(self, ginv: "GramMatrix", bi: int, r: np.ndarray, v: "np.ndarray | None" = None, scalar: float = 0.0) -> "tuple[float, float]":
+        """The same pair for dG = diag(v) + scalar I on block `bi` (`lpgp_mat_evidence_grad_diag`): the derivative by a noise variance."""
+        r = np.ascontiguousarray(r, dtype=np.double)
+        if r.shape != (self.n,):
+            raise ValueError(f"residual must have shape ({self.n},), got {r.shape}")
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.double)
+            if v.shape != (self.block_sizes[bi],):
+                raise ValueError("diagonal has the wrong length")
+        out = np.empty(2)
+        check(lib.lpgp_mat_evidence_grad_diag(self.ctx._h, self._h, ginv._h, int(bi), as_pd(v) if v is not None else None, float(scalar),
+                                              as_pd(r), as_pd(out)), "lpgp_mat_evidence_grad_diag")
+        return float(out[0]), float(out[1])
+
     def potrf_enqueue(self) -> None:
         """The factorisation enqueued, no host synchronisation (`lpgp_potrf_enqueue`): its status is read by `check`."""
         check(lib.lpgp_potrf_enqueue(self.ctx._h, self._h), "lpgp_potrf_enqueue")

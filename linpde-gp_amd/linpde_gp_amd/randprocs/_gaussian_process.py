@@ -430,6 +430,43 @@ class LeaveOneOut:
         return f"LeaveOneOut(n={self.mean.size}, total={self.total:.6g})"
 
 
+class EvidenceGradient:
+    """Result of `ConditionalGaussianProcess.log_marginal_likelihood_gradient()`: `value`, the log marginal likelihood itself, and
+    its derivatives with respect to the LOGARITHMS of the hyperparameters (every entry 1/2 w^T dG w - 1/2 tr(G^{-1} dG), GPML eq. 5.9):
+    `log_output_scale` (G,), by the variance scale of summand g of the prior covariance (its factor in front of the product of
+    univariate kernels); `log_lengthscales` (G, d), by lengthscale j of summand g; `log_noise` (B,), by a factor tau_b in front of
+    the noise covariance `b.cov` of observation block b, at tau_b = 1 (0.0 for a block without noise).  G summands, d input
+    dimensions, B observation blocks in conditioning order."""
+
+    __slots__ = ("value", "log_output_scale", "log_lengthscales", "log_noise")
+
+    def __init__(self, value, log_output_scale, log_lengthscales, log_noise):
+        self.value = float(value)
+        self.log_output_scale, self.log_lengthscales, self.log_noise = log_output_scale, log_lengthscales, log_noise
+
+    def __repr__(self):
+        return (f"EvidenceGradient(value={self.value:.6g}, summands={self.log_output_scale.size}, "
+                f"dims={self.log_lengthscales.shape[1]}, blocks={self.log_noise.size})")
+
+
+def _block_noise(ob):
+    """(scalar, diag, dense) of the noise covariance of an observation block, as `_extend` hands it to the library."""
+    n = ob.points.n
+    scalar, diag, dense = 0.0, None, None
+    if ob.b is not None and isinstance(ob.b, randvars.Normal):
+        if ob.b.cov_diag is not None:
+            diag = np.ascontiguousarray(ob.b.cov_diag, dtype=np.double)
+        else:
+            cov = np.asarray(ob.b.cov).reshape(n, n)
+            if np.any(cov - np.diag(np.diag(cov)) != 0.0):
+                dense = np.ascontiguousarray(cov, dtype=np.double)
+            else:
+                diag = np.ascontiguousarray(np.diag(cov), dtype=np.double)
+        if diag is not None and diag.size and np.all(diag == diag.flat[0]):
+            scalar, diag = float(diag.flat[0]), None
+    return scalar, diag, dense
+
+
 _ROWS_SEEN_MAX = 4096        # (a hint only, and only where re-allocation matters: 128 MB; beyond, a copy is noise against the O(n^3) work)
 
 
@@ -809,6 +846,68 @@ class ConditionalGaussianProcess(GaussianProcess):
         _evidence_context("leave_one_out")
         self._check_current()
         return LeaveOneOut(*self._state.mat.loo(self._residual(), np.concatenate([ob.Y for ob in self._blocks])))
+
+    def log_marginal_likelihood_gradient(self) -> "EvidenceGradient":
+        """The log marginal likelihood and its gradient by the log hyperparameters of the prior covariance and of the noise
+        (`EvidenceGradient`): 1/2 w^T dG w - 1/2 tr(G^{-1} dG) per parameter (GPML eq. 5.9), analytic -- differencing
+        `log_marginal_likelihood()` over fresh conditionings loses most digits at the condition numbers of these Gram matrices.
+        G^{-1} is formed once on the device from the resident factor (`lpgp_mat_inverse`) and released at the end; every dG is
+        assembled into ONE scratch matrix by replaying the chain's block rows with a derived descriptor and no noise -- one summand
+        alone (output scale), one summand with `dlog_lengthscale` set (lengthscale) -- and contracted in one streaming pass
+        (`lpgp_mat_evidence_grad`); a diagonal noise needs no matrix (`lpgp_mat_evidence_grad_diag`).  Three n x n matrices are
+        alive at most.  An earlier posterior of a chain answers for its own blocks; flushes, verifies and raises as
+        `log_marginal_likelihood`.  An isotropic multivariate Matern prior raises `NotImplementedError` (no closed form of its
+        lengthscale derivative here; use a `TensorProduct` prior)."""
+        base = self._prior.cov
+        base_groups = covfuncs._base(base)._base_groups()
+        G, d = len(base_groups), max(int(np.prod(self._prior.input_shape, dtype=int)), 1)
+        if not self._blocks:
+            return EvidenceGradient(0.0, np.zeros(G), np.zeros((G, d)), np.zeros(0))
+        ctx = _evidence_context("log_marginal_likelihood_gradient")
+        if any(f[0][0] == covfuncs.MATERN_ISO for _, f in base_groups):
+            raise NotImplementedError("`log_marginal_likelihood_gradient` is not available for the isotropic multivariate Matérn kernel "
+                                      "(its lengthscale derivative has no closed form here); use a `TensorProduct` prior")
+        self._check_current()
+        mat = self._state.mat
+        r = self._residual()
+        quad, logdet = mat.evidence(r)
+        value = float(-0.5 * quad - 0.5 * logdet - 0.5 * r.size * np.log(2.0 * np.pi))
+        blocks = self._blocks
+        # descriptor groups of every block pair (i, j <= i), once: the derived descriptors pick from them
+        pair = [[covfuncs.DifferentiatedCovarianceFunction(covfuncs._base(base), *_combine(base, bi.coeffs, bj.coeffs)).lower()
+                 for bj in blocks[:i + 1]] for i, bi in enumerate(blocks)]
+        ginv = mat.inverse()
+        scratch = _engine.GramMatrix(ctx, capacity_hint=mat.padded_n)
+
+        def contract(derive, dense_block=None, dense=None) -> float:
+            """1/2 w^T dG w - 1/2 tr(G^{-1} dG) for dG = the chain's block rows under `derive(groups)` (+ `dense` on one block)."""
+            try:
+                for i, bi in enumerate(blocks):
+                    row = [(derive(pair[i][j]), bj.points) for j, bj in enumerate(blocks[:i])]
+                    row.append((derive(pair[i][i]), None))
+                    info = scratch.condition(bi.points.n, bi.points, row, noise_dense=dense if i == dense_block else None, lazy=2)
+                    assert info == 0
+                q, t = mat.evidence_grad(ginv, scratch, r)
+            finally:
+                scratch.truncate(0)
+            return 0.5 * q - 0.5 * t
+
+        try:
+            d_scale, d_ls, d_noise = np.zeros(G), np.zeros((G, d)), np.zeros(len(blocks))
+            for g in range(G):
+                d_scale[g] = contract(lambda groups, g=g: [groups[g]])
+                for j in range(d):
+                    d_ls[g, j] = contract(lambda groups, g=g, j=j: [dict(groups[g], dlog_lengthscale=j + 1)])
+            for b, ob in enumerate(blocks):
+                scalar, diag, dense = _block_noise(ob)
+                if dense is not None:
+                    d_noise[b] = contract(lambda groups: [dict(groups[0], scale=0.0)], b, dense)
+                elif diag is not None or scalar != 0.0:
+                    q, t = mat.evidence_grad_diag(ginv, b, r, v=diag, scalar=scalar)
+                    d_noise[b] = 0.5 * q - 0.5 * t
+        finally:
+            del scratch, ginv
+        return EvidenceGradient(value, d_scale, d_ls, d_noise)
 
     def sample(self, rng, x, size=(), *, damping=None):
         """Joint draws of the posterior (of the read-out `D(u)` if this object is one) at the points `x`.

@@ -429,6 +429,9 @@ class MatrixFreeConditionalGaussianProcess:
     def leave_one_out(self):
         raise NotImplementedError("`leave_one_out` needs the dense factorisation: a matrix-free posterior has no Cholesky factor to form diag(G^-1) with")
 
+    def log_marginal_likelihood_gradient(self):
+        raise NotImplementedError("`log_marginal_likelihood_gradient` needs the dense factorisation: a matrix-free posterior has no Cholesky factor to form G^-1 with")
+
     @property
     def cov(self):
         return _MatrixFreeCovariance(self)
