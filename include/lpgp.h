@@ -190,6 +190,28 @@ int64_t lpgp_mat_padded_size(const lpgp_mat* mat);    /* internal padded size   
 int  lpgp_gram_assemble(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups,
                         const lpgp_pts* X0, const lpgp_pts* X1,
                         lpgp_mat* mat, int32_t bi, int32_t bj);
+/* ---- variable-coefficient operators  L = sum_a f_a(x) D_a  with constant-coefficient parts D_a (at most LPGP_MAXW of them):
+ *      G[i, j] = sum_p  w0[a_p][i] * (kd_p)(x_i, x'_j) * w1[b_p][j],   kd_p = D_{a_p} k D_{b_p}'^*  an ordinary descriptor sum,
+ *      w0[a][i] = f_a(x_i), w1[b][j] = g_b(x'_j) evaluated by the caller.  One fused launch: the pairs are evaluated one after
+ *      another per entry and accumulated in registers in pair order (no atomics: the same bits on every call); with one pair
+ *      and all weights 1.0 the block is bit-identical to lpgp_gram_assemble's generic kernel.  Cost: npairs x the generic
+ *      evaluation.  The reference has no counterpart (its `WeightedLaplacian` weights are constants).  Single GPU.          */
+#define LPGP_MAXW 4                     /* coefficient functions per operator */
+typedef struct { const lpgp_kdesc* kd; int32_t ngroups; int32_t a, b; } lpgp_wpair;
+/* block (bi, bj), bi >= bj  <-  sum_p  diag(w0[a_p]) (kd_p)(X0, X1) diag(w1[b_p]),  1 <= npairs <= 16.
+ * w0_host: A0 x n_bi, C-order; w1_host: A1 x n_bj.
+ * bi == bj: X1 == NULL and w1_host == NULL (A1 is ignored); the row weights serve both sides, and the pair list must be
+ * symmetric so that only the lower triangle is needed ((a, b) and (b, a) carry transposed descriptors): as many pairs
+ * (a, b) as (b, a) -- only the indices are checked.  Host pointers are borrowed for the call.
+ * Refused, with the matrix untouched: npairs outside 1..16, A0 / A1 outside 1..LPGP_MAXW, a pair index out of range, a NULL
+ * weight pointer where one is needed, pairs of different input dimension, a block that is already factored, a strict-prefix
+ * view (lpgp_mat_set_view), a context inside a multi-GPU job.  Conditioning on such a block goes through the separate calls:
+ * lpgp_mat_add_block, one weighted or plain assembly per block of the row, lpgp_mat_add_diag / lpgp_mat_add_dense, lpgp_potrf. */
+int  lpgp_gram_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_t npairs,
+                                 const double* w0_host, int32_t A0,
+                                 const double* w1_host, int32_t A1,
+                                 const lpgp_pts* X0, const lpgp_pts* X1,
+                                 lpgp_mat* mat, int32_t bi, int32_t bj);
 /* The same block when its point sets are TENSOR GRIDS: rows = grid F0[0] x ... x F0[d-1] and
  * columns = grid F1[0] x ... x F1[d-1] of 1-D point sets (C order, last factor fastest; F1 ==
  * NULL for bi == bj).  The block is then a sum of Kronecker products of 1-D kernel matrices:
@@ -294,6 +316,12 @@ int  lpgp_rhs_destroy(lpgp_rhs* rhs);
 int  lpgp_cross_assemble(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups,
                          const lpgp_pts* X_obs, const lpgp_pts* X_test,
                          lpgp_rhs* rhs, const lpgp_mat* mat, int32_t bi);
+/* rows of block bi of K_Xx  <-  sum_p diag(w[a_p]) (kd_p)(X_obs, X_test): the cross-covariance of a variable-coefficient
+ * observation block (see lpgp_gram_assemble_weighted).  The test side is unweighted; b_p must be 0.  w_host: A x n_bi, C-order. */
+int  lpgp_cross_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_t npairs,
+                                  const double* w_host, int32_t A,
+                                  const lpgp_pts* X_obs, const lpgp_pts* X_test,
+                                  lpgp_rhs* rhs, const lpgp_mat* mat, int32_t bi);
 /* The same for ALL observation blocks in one call (round 5): blocks[bi] = {descriptor, observation points} of block bi (kd == NULL:
  * the block has no cross-covariance with the prediction points, its rows stay zero).  Consecutive blocks that share a descriptor
  * -- value observations on several boundary pieces -- are assembled by ONE launch (a table of point sets in the kernel

@@ -944,6 +944,30 @@ int lpgp_gram_assemble(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, con
   return rc;       // asynchronous: consumers are ordered behind it on the main stream
 }
 
+int lpgp_gram_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_t npairs, const double* w0_host, int32_t A0,
+                                const double* w1_host, int32_t A1, const lpgp_pts* X0, const lpgp_pts* X1, lpgp_mat* mat, int32_t bi,
+                                int32_t bj) {
+  static const char* fn = "lpgp_gram_assemble_weighted";
+  LPGP_CHECK(ctx && X0 && mat, "%s: null argument", fn);
+  LPGP_DEVICE(ctx);
+  LPGP_CHECK(!ctx->distributed(), "%s: single GPU only (this context has joined a multi-GPU job)", fn);
+  LPGP_MAT_ALIVE(mat, "lpgp_gram_assemble_weighted");
+  LPGP_CHECK(mat->hidden.empty(), "%s: a strict prefix of the blocks is in view (lpgp_mat_set_view)", fn);
+  LPGP_CHECK(bi >= 0 && bi < (int)mat->blocks.size() && bj >= 0 && bj <= bi, "%s: bad block (%d,%d)", fn, bi, bj);
+  const lpgp_block& Bi = mat->blocks[bi];
+  const lpgp_block& Bj = mat->blocks[bj];
+  LPGP_CHECK(Bi.poff >= mat->pn_fact, "%s: block %d is already factored", fn, bi);
+  const bool sym = (bi == bj);
+  LPGP_CHECK(sym == (X1 == nullptr), "%s: X1 must be NULL exactly for diagonal blocks", fn);
+  LPGP_CHECK(w0_host != nullptr, "%s: null row weights", fn);
+  LPGP_CHECK(sym ? w1_host == nullptr : w1_host != nullptr, "%s: the column weights must be NULL exactly for diagonal blocks", fn);
+  LPGP_TRY_RC(check_wpairs(pairs, npairs, A0, A1, sym ? WP_SYM : WP_RECT, fn));
+  const lpgp_pts* Xc = sym ? X0 : X1;
+  LPGP_CHECK(X0->n == Bi.n && Xc->n == Bj.n && Xc->d == X0->d && pairs[0].kd[0].d == X0->d, "%s: shape mismatch", fn);
+  return assemble_weighted(ctx, ctx->s_main, pairs, npairs, w0_host, A0, w1_host, sym ? A0 : A1, X0, Xc, sym, mat->a, mat->lr_cap, Bi.poff,
+                           Bj.poff, mat_layout(ctx));
+}
+
 int lpgp_kron_fits(const lpgp_kdesc* kd, int32_t ngroups) { return kron_fits(kd, ngroups) ? 1 : 0; }
 
 int lpgp_gram_assemble_grid(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, const lpgp_pts* const* F0,
@@ -1525,6 +1549,27 @@ int lpgp_cross_assemble(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, co
                        X_test->n_pad, rhs->v, rhs->ld, B.poff, 0, 0);
   if (rc == 0 && bi < (int)rhs->assembled.size()) rhs->assembled[bi] = 1;
   return rc;       // asynchronous (see lpgp_gram_assemble)
+}
+
+int lpgp_cross_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_t npairs, const double* w_host, int32_t A,
+                                 const lpgp_pts* X_obs, const lpgp_pts* X_test, lpgp_rhs* rhs, const lpgp_mat* mat, int32_t bi) {
+  static const char* fn = "lpgp_cross_assemble_weighted";
+  LPGP_CHECK(ctx && X_obs && X_test && rhs && mat, "%s: null argument", fn);
+  LPGP_DEVICE(ctx);
+  LPGP_CHECK(!ctx->distributed(), "%s: single GPU only (this context has joined a multi-GPU job)", fn);
+  LPGP_CHECK(bi >= 0 && bi < (int)mat->blocks.size(), "%s: bad block %d", fn, bi);
+  const lpgp_block& B = mat->blocks[bi];
+  LPGP_CHECK(w_host != nullptr, "%s: null weights", fn);
+  LPGP_TRY_RC(check_wpairs(pairs, npairs, A, 1, WP_CROSS, fn));
+  LPGP_CHECK(X_obs->n == B.n && X_test->n == rhs->m && X_obs->d == X_test->d && pairs[0].kd[0].d == X_obs->d, "%s: shape mismatch", fn);
+  LPGP_CHECK(rhs->ld == mat->pn, "%s: rhs was created for a different matrix size", fn);
+  int rc = 0;
+  if (X_test->n > 0 && X_obs->n > 0) {
+    const std::vector<double> ones((size_t)X_test->n, 1.0);
+    rc = assemble_weighted(ctx, ctx->s_main, pairs, npairs, w_host, A, ones.data(), 1, X_obs, X_test, false, rhs->v, rhs->ld, B.poff, 0, Layout2D());
+  }
+  if (rc == 0 && bi < (int)rhs->assembled.size()) rhs->assembled[bi] = 1;
+  return rc;
 }
 
 int lpgp_cross_assemble_row(lpgp_ctx* ctx, const lpgp_cross_block* blocks, int32_t nblocks, const lpgp_pts* X_test, lpgp_rhs* rhs,

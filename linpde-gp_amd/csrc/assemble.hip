@@ -16,6 +16,7 @@
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 #include "lpgp_internal.h"
 #include "eval_entries.h"
@@ -177,6 +178,90 @@ __global__ __launch_bounds__(256) void assemble_kernel(const DevDesc* __restrict
     }
   }
   if ((a.flags & 4) && sink == 0.12345 && row < a.n0) a.out[lrow0 + lane + lcol0 * a.ld] = sink;
+}
+
+// ---------------------------------------------------------------------------------------
+// Variable-coefficient operators  L_row = sum_a f_a(x) D_a,  L_col = sum_b g_b(x') D_b  (DESIGN.md section 5c):
+//   G[i, j] = sum_p  w0[a_p][i] * (D_{a_p} k D_{b_p}'^*)(x_i, x'_j) * w1[b_p][j]
+// with one lowered descriptor per pair p = (a_p, b_p).  The tile code is assemble_kernel's (64 x 64 tile, lane = row, wave =
+// 16-column slab, AEK entries per pass, the LDS exponential table); per pass the pairs are evaluated one after another by the
+// SAME eval_entries and accumulated in registers, one store per entry at the end: the pairs never meet in memory, so there are
+// no atomics and a call gives the same bits every time.  The lane's row weights live in registers, the tile's column
+// weights in LDS beside the column coordinates.  The first pair starts the sum as a product, so with one pair and weights 1.0 an
+// entry is (1.0 * 1.0) * v == v, the sign of a zero included: the
+// block assemble_kernel writes for that descriptor (tests/test_gpu_varcoef.py).  Cost: npairs x the generic evaluation.
+// ---------------------------------------------------------------------------------------
+constexpr int WT_MAXP = 16;       // pairs per launch (LPGP_MAXW^2)
+struct WeightArgs {
+  const DevDesc* desc[WT_MAXP];   // device copies of the lowered pair descriptors
+  int32_t npairs, A0, A1;
+  uint8_t pa[WT_MAXP], pb[WT_MAXP];   // pair p multiplies by row weight pa[p] and column weight pb[p]
+  const double* w0;               // [A0][w0_stride] row weights
+  const double* w1;               // [A1][w1_stride] column weights
+  int64_t w0_stride, w1_stride;
+};
+
+template <int D>
+__global__ __launch_bounds__(256) void assemble_weighted_kernel(WeightArgs wa, AsmArgs a) {
+  __shared__ double sx1[D][AT];
+  __shared__ double sw1[LPGP_MAXW][AT];
+  __shared__ __attribute__((aligned(16))) double s_exp[2 * EXP_TAB_N];
+  const int tr = blockIdx.x % a.tiles_r;
+  const int tc = blockIdx.x / a.tiles_r;
+  const int64_t r0 = (int64_t)tr * AT, c0 = (int64_t)tc * AT;
+  if (a.lower_only && c0 > r0 + AT - 1) return;
+  const int64_t lrow0 = cyc_local(a.lay.rows, a.row_off + r0), lcol0 = cyc_local(a.lay.cols, a.col_off + c0);
+  if (lrow0 < 0 || lcol0 < 0) return;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t row = r0 + lane;
+  double xr[D], wr[LPGP_MAXW];
+#pragma unroll
+  for (int j = 0; j < D; ++j) xr[j] = (row < a.n0) ? a.x0[j * a.n0_pad + row] : 0.0;
+#pragma unroll
+  for (int q = 0; q < LPGP_MAXW; ++q) wr[q] = (q < wa.A0 && row < a.n0) ? wa.w0[q * wa.w0_stride + row] : 0.0;
+  if (threadIdx.x < AT) {
+    const int64_t col = c0 + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < D; ++j) sx1[j][threadIdx.x] = (col < a.n1) ? a.x1[j * a.n1_pad + col] : 0.0;
+#pragma unroll
+    for (int q = 0; q < LPGP_MAXW; ++q) sw1[q][threadIdx.x] = (q < wa.A1 && col < a.n1) ? wa.w1[q * wa.w1_stride + col] : 0.0;
+  }
+  s_exp[threadIdx.x] = g_exp_table[threadIdx.x], s_exp[threadIdx.x + 256] = g_exp_table[threadIdx.x + 256];
+  const ExpTab etab{s_exp};
+  __syncthreads();
+#pragma unroll 1
+  for (int pass = 0; pass < 16 / AEK; ++pass) {
+    const int cb = w * 16 + pass * AEK;
+    double dx[D][AEK], acc[AEK];
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+#pragma unroll
+      for (int e = 0; e < AEK; ++e) dx[j][e] = xr[j] - sx1[j][cb + e];
+#pragma unroll
+    for (int e = 0; e < AEK; ++e) acc[e] = 0.0;
+#pragma unroll 1
+    for (int p = 0; p < wa.npairs; ++p) {
+      const int qa = wa.pa[p], qb = wa.pb[p];                // (uniform: scalar loads from the kernel arguments)
+      double res[AEK];
+      eval_entries<D, AEK>(wa.desc[p], dx, res, etab);
+      const double wrow = qa == 0 ? wr[0] : (qa == 1 ? wr[1] : (qa == 2 ? wr[2] : wr[3]));      // (selects: no indexed register file)
+      if (p == 0) {                                            // (a product, not fma(w, v, +0.0): keeps the sign of a zero entry)
+#pragma unroll
+        for (int e = 0; e < AEK; ++e) acc[e] = (wrow * sw1[qb][cb + e]) * res[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < AEK; ++e) acc[e] = fma(wrow * sw1[qb][cb + e], res[e], acc[e]);
+      }
+    }
+    if (row < a.n0) {
+#pragma unroll
+      for (int e = 0; e < AEK; ++e) {
+        const int64_t c = c0 + cb + e;
+        if (c < a.n1) a.out[(lrow0 + lane) + (lcol0 + cb + e) * a.ld] = acc[e];
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -499,13 +584,8 @@ __global__ void add_dense_lower_kernel(double* a, int64_t ld, int64_t off, int64
   if (lr >= 0 && lc >= 0) a[lr + lc * ld] += b[i * n + j];
 }
 
-// Copy a lowered descriptor into the next slot of the context's ring (pinned host -> device,
-// asynchronous); the caller records slot.done behind the kernel that reads it.
-static int stage_desc(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, lpgp_ctx::DescSlot** out) {
-  lpgp_ctx::DescSlot& slot = ctx->desc_ring[ctx->desc_next];
-  ctx->desc_next = (ctx->desc_next + 1) % lpgp_ctx::DESC_RING;
-  if (slot.used) LPGP_HIP(hipEventSynchronize(slot.done));
-  // only the used prefix of the coefficient table travels
+// bytes of a lowered descriptor that travel to the device: only the used prefix of the coefficient table
+static size_t desc_used_bytes(const DevDesc& host_desc) {
   int ncoef = 0;
   for (int gi = 0; gi < host_desc.ngroups; ++gi) {
     const DevGroup& G = host_desc.g[gi];
@@ -515,7 +595,16 @@ static int stage_desc(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_des
       if (G.coef_off[c] + len > ncoef) ncoef = G.coef_off[c] + len;
     }
   }
-  const size_t bytes = offsetof(DevDesc, coef) + (size_t)ncoef * sizeof(double);
+  return offsetof(DevDesc, coef) + (size_t)ncoef * sizeof(double);
+}
+
+// Copy a lowered descriptor into the next slot of the context's ring (pinned host -> device,
+// asynchronous); the caller records slot.done behind the kernel that reads it.
+static int stage_desc(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, lpgp_ctx::DescSlot** out) {
+  lpgp_ctx::DescSlot& slot = ctx->desc_ring[ctx->desc_next];
+  ctx->desc_next = (ctx->desc_next + 1) % lpgp_ctx::DESC_RING;
+  if (slot.used) LPGP_HIP(hipEventSynchronize(slot.done));
+  const size_t bytes = desc_used_bytes(host_desc);
   std::memcpy(slot.h, &host_desc, bytes);
   LPGP_HIP(hipMemcpyAsync(slot.d, slot.h, bytes, hipMemcpyHostToDevice, stream));
   *out = &slot;
@@ -576,6 +665,80 @@ int launch_assemble(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc,
   LPGP_HIP(hipEventRecord(slot.done, stream));
   slot.used = true;
   return 0;
+}
+
+// One block of a variable-coefficient operator pair (assemble_weighted_kernel): lowers every pair, stages the descriptors
+// and the weights in ONE temporary device buffer (a ring slot per descriptor would not do: the ring has DESC_RING slots,
+// a launch up to WT_MAXP descriptors), launches, and waits -- the host weights are borrowed.  Everything that can refuse
+// (the lowering) happens before the launch: on an error the output is untouched.  sym: X1 == X0, the row weights serve both
+// sides, only tiles on or below the diagonal are written.
+int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs, int npairs, const double* w0_host, int A0,
+                      const double* w1_host, int A1, const lpgp_pts* X0, const lpgp_pts* X1, bool sym, double* out, int64_t ld,
+                      int64_t row_off, int64_t col_off, const Layout2D& lay) {
+  static_assert(LPGP_MAXW == 4 && WT_MAXP == LPGP_MAXW * LPGP_MAXW, "assemble_weighted_kernel selects among four row weights");
+  LPGP_CHECK(npairs >= 1 && npairs <= WT_MAXP && A0 >= 1 && A0 <= LPGP_MAXW && A1 >= 1 && A1 <= LPGP_MAXW, "assemble_weighted: bad sizes");
+  const int64_t n0 = X0->n, n1 = X1->n;
+  const int d = X0->d;
+  if (n0 <= 0 || n1 <= 0) return 0;                // an empty block: nothing to stage, nothing to write
+  std::vector<char> h;
+  size_t off_desc[WT_MAXP];
+  {
+    std::unique_ptr<DevDesc> desc(new DevDesc);
+    for (int p = 0; p < npairs; ++p) {
+      LPGP_TRY_RC(lower_kdesc(pairs[p].kd, pairs[p].ngroups, desc.get()));
+      LPGP_CHECK(desc->d == d, "assemble_weighted: pair %d lowers to d=%d, the points have d=%d", p, desc->d, d);
+      const size_t bytes = desc_used_bytes(*desc);
+      off_desc[p] = h.size();
+      h.resize(h.size() + (bytes + 15) / 16 * 16);
+      std::memcpy(h.data() + off_desc[p], desc.get(), bytes);
+    }
+  }
+  const size_t off_w0 = h.size(), w0_bytes = (size_t)A0 * (size_t)n0 * sizeof(double);
+  h.resize(off_w0 + w0_bytes);
+  std::memcpy(h.data() + off_w0, w0_host, w0_bytes);
+  size_t off_w1 = off_w0;
+  if (!sym) {
+    const size_t w1_bytes = (size_t)A1 * (size_t)n1 * sizeof(double);
+    off_w1 = h.size();
+    h.resize(off_w1 + w1_bytes);
+    std::memcpy(h.data() + off_w1, w1_host, w1_bytes);
+  }
+  AsmArgs a;
+  a.x0 = X0->x; a.x1 = X1->x; a.n0 = n0; a.n1 = n1; a.n0_pad = X0->n_pad; a.n1_pad = X1->n_pad;
+  a.out = out; a.ld = ld; a.row_off = row_off; a.col_off = col_off; a.lower_only = sym ? 1 : 0;
+  a.lay = lay;
+  a.tiles_r = (int)((n0 + AT - 1) / AT);
+  a.tiles_c = (int)((n1 + AT - 1) / AT);
+  if (a.tiles_r == 0 || a.tiles_c == 0) return 0;
+  DevBuf buf;
+  LPGP_TRY(DevBuf::pool(ctx, h.size(), &buf));
+  StreamDrain drain{stream};                       // (behind `h` and `buf`: the copy out of `h` has landed before either goes)
+  LPGP_HIP(hipMemcpyAsync(buf.as<char>(), h.data(), h.size(), hipMemcpyHostToDevice, stream));
+  WeightArgs wa;
+  std::memset(&wa, 0, sizeof(wa));
+  wa.npairs = npairs; wa.A0 = A0; wa.A1 = sym ? A0 : A1;
+  for (int p = 0; p < npairs; ++p) {
+    wa.desc[p] = reinterpret_cast<const DevDesc*>(buf.as<char>() + off_desc[p]);
+    wa.pa[p] = (uint8_t)pairs[p].a;
+    wa.pb[p] = (uint8_t)pairs[p].b;
+  }
+  wa.w0 = reinterpret_cast<const double*>(buf.as<char>() + off_w0);
+  wa.w1 = reinterpret_cast<const double*>(buf.as<char>() + off_w1);
+  wa.w0_stride = n0;
+  wa.w1_stride = n1;
+  const dim3 grid((unsigned)((int64_t)a.tiles_r * a.tiles_c));
+  const double entries = sym ? 0.5 * (double)n0 * ((double)n0 + 1.0) : (double)n0 * (double)n1;
+  prof_begin(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * entries);
+  switch (d) {
+    case 1: hipLaunchKernelGGL((assemble_weighted_kernel<1>), grid, dim3(256), 0, stream, wa, a); break;
+    case 2: hipLaunchKernelGGL((assemble_weighted_kernel<2>), grid, dim3(256), 0, stream, wa, a); break;
+    case 3: hipLaunchKernelGGL((assemble_weighted_kernel<3>), grid, dim3(256), 0, stream, wa, a); break;
+    case 4: hipLaunchKernelGGL((assemble_weighted_kernel<4>), grid, dim3(256), 0, stream, wa, a); break;
+    default: prof_end(ctx, stream); LPGP_CHECK(false, "assemble_weighted: d=%d", d);
+  }
+  prof_end(ctx, stream);
+  LPGP_HIP(hipGetLastError());
+  return drain.wait();
 }
 
 // column tiles per workgroup of a rectangular block (see launch_assemble)

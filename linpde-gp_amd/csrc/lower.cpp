@@ -315,4 +315,33 @@ double desc_diag(const DevDesc& desc) {
   return v;
 }
 
+// ---------------------------------------------------------------------------------------
+// pair list of a variable-coefficient block (lpgp_gram_assemble_weighted / lpgp_cross_assemble_weighted)
+// ---------------------------------------------------------------------------------------
+int check_wpairs(const lpgp_wpair* pairs, int npairs, int A0, int A1, WpairForm form, const char* fn) {
+  constexpr int MAXP = LPGP_MAXW * LPGP_MAXW;
+  LPGP_CHECK(pairs != nullptr, "%s: null pair list", fn);
+  LPGP_CHECK(npairs >= 1 && npairs <= MAXP, "%s: %d pairs (1 .. %d)", fn, npairs, MAXP);
+  LPGP_CHECK(A0 >= 1 && A0 <= LPGP_MAXW, "%s: %d row weight functions (1 .. %d)", fn, A0, LPGP_MAXW);
+  const bool sym = form == WP_SYM;
+  const int nb = form == WP_CROSS ? 1 : (sym ? A0 : A1);
+  LPGP_CHECK(nb >= 1 && nb <= LPGP_MAXW, "%s: %d column weight functions (1 .. %d)", fn, nb, LPGP_MAXW);
+  int count[LPGP_MAXW][LPGP_MAXW] = {};
+  for (int p = 0; p < npairs; ++p) {
+    const lpgp_wpair& P = pairs[p];
+    LPGP_CHECK(P.kd != nullptr && P.ngroups >= 1 && P.ngroups <= LPGP_MAXG, "%s: pair %d has no descriptor (or ngroups = %d)", fn, p, P.ngroups);
+    LPGP_CHECK(P.a >= 0 && P.a < A0, "%s: pair %d: row weight index %d outside 0 .. %d", fn, p, P.a, A0 - 1);
+    LPGP_CHECK(P.b >= 0 && P.b < nb, "%s: pair %d: column weight index %d outside 0 .. %d", fn, p, P.b, nb - 1);
+    for (int g = 0; g < P.ngroups; ++g)
+      LPGP_CHECK(P.kd[g].d == pairs[0].kd[0].d, "%s: pair %d has input dimension %d, pair 0 has %d", fn, p, P.kd[g].d, pairs[0].kd[0].d);
+    ++count[P.a][P.b];
+  }
+  if (sym)
+    for (int a = 0; a < A0; ++a)
+      for (int b = 0; b < a; ++b)
+        LPGP_CHECK(count[a][b] == count[b][a], "%s: the pair list of a diagonal block must be symmetric: %d pair(s) (%d, %d), %d pair(s) (%d, %d)",
+                   fn, count[a][b], a, b, count[b][a], b, a);
+  return 0;
+}
+
 }  // namespace lpgp

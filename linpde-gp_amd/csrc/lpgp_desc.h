@@ -56,6 +56,12 @@ struct DevDesc {
 };
 
 int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out);
+// The pair list and the weight counts of lpgp_gram_assemble_weighted / lpgp_cross_assemble_weighted (`fn`: the name in the
+// message).  WP_RECT: an off-diagonal block, a < A0 and b < A1.  WP_SYM: a diagonal block, b indexes the row weights (A1 is
+// ignored) and the list must hold as many pairs (a, b) as (b, a).  WP_CROSS: every b must be 0 (A1 is ignored).  Also: one
+// input dimension for all pairs.  0, or an error with its message set.
+enum WpairForm { WP_RECT = 0, WP_SYM = 1, WP_CROSS = 2 };
+int check_wpairs(const lpgp_wpair* pairs, int npairs, int A0, int A1, WpairForm form, const char* fn);
 // value of sum_g (kd[g])(x, x): only the constant coefficient of the all-even parity classes survives
 double desc_diag(const DevDesc& desc);
 

@@ -480,6 +480,10 @@ struct AsmJob {
   int64_t row_off, col_off;
   int lower_only;
 };
+// one block  sum_p diag(w0[a_p]) (kd_p)(X0, X1) diag(w1[b_p])  of a variable-coefficient operator pair; waits for the stream
+int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs, int npairs, const double* w0_host, int A0,
+                      const double* w1_host, int A1, const lpgp_pts* X0, const lpgp_pts* X1, bool sym, double* out, int64_t ld,
+                      int64_t row_off, int64_t col_off, const Layout2D& lay);
 bool assemble_same_fast(const DevDesc& p, const DevDesc& q);
 int launch_assemble_batch(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, const AsmJob* jobs, int njobs, double* out, int64_t ld,
                           const Layout2D& lay);

@@ -366,6 +366,22 @@ class GramMatrix:
         check(lib.lpgp_gram_assemble(self.ctx._h, arr, len(arr), X0._h, X1._h if X1 is not None else None,
                                      self._h, bi, bj), "lpgp_gram_assemble")
 
+    def assemble_weighted(self, pairs, w0: np.ndarray, w1: "np.ndarray | None", X0: Points, X1: "Points | None", bi: int, bj: int):
+        """Block (bi, bj) <- sum_p diag(w0[a_p]) K_p(X0, X1) diag(w1[b_p]) (`lpgp_gram_assemble_weighted`): `pairs` =
+        [(kdesc, a, b)], `w0` (A0, n_bi), `w1` (A1, n_bj); for a diagonal block `X1` and `w1` are None.  Always entry-wise from
+        the flattened points: a weighted block of two tensor grids is not a Kronecker product."""
+        arr, keep = _wpair_array(pairs)
+        w0 = np.ascontiguousarray(w0, dtype=np.double)
+        if w0.ndim != 2 or w0.shape[1] != X0.n:
+            raise ValueError(f"row weights must have shape (A0, {X0.n}), got {w0.shape}")
+        if w1 is not None:
+            w1 = np.ascontiguousarray(w1, dtype=np.double)
+            if X1 is None or w1.ndim != 2 or w1.shape[1] != X1.n:
+                raise ValueError("column weights must have shape (A1, number of column points)")
+        check(lib.lpgp_gram_assemble_weighted(self.ctx._h, arr, len(arr), as_pd(w0), w0.shape[0], as_pd(w1) if w1 is not None else None,
+                                              w1.shape[0] if w1 is not None else 0, X0._h, X1._h if X1 is not None else None, self._h, bi, bj),
+              "lpgp_gram_assemble_weighted")
+
     def add_diag(self, bi: int, v: np.ndarray | None = None, scalar: float = 0.0):
         if v is not None:
             v = np.ascontiguousarray(v, dtype=np.double)
@@ -576,6 +592,15 @@ class Rhs:
         check(lib.lpgp_cross_assemble(self.ctx._h, arr, len(arr), X_obs._h, X_test._h, self._h, self.mat._h, bi),
               "lpgp_cross_assemble")
 
+    def cross_assemble_weighted(self, pairs, w: np.ndarray, X_obs: Points, X_test: Points, bi: int):
+        """Rows of block `bi` <- sum_p diag(w[a_p]) K_p(X_obs, X_test) (`lpgp_cross_assemble_weighted`): `pairs` = [(kdesc, a, 0)]."""
+        arr, keep = _wpair_array(pairs)
+        w = np.ascontiguousarray(w, dtype=np.double)
+        if w.ndim != 2 or w.shape[1] != X_obs.n:
+            raise ValueError(f"weights must have shape (A, {X_obs.n}), got {w.shape}")
+        check(lib.lpgp_cross_assemble_weighted(self.ctx._h, arr, len(arr), as_pd(w), w.shape[0], X_obs._h, X_test._h, self._h, self.mat._h, bi),
+              "lpgp_cross_assemble_weighted")
+
     def cross_assemble_row(self, entries, X_test: Points):
         """All observation blocks in one call (`lpgp_cross_assemble_row`): entries = [(kdesc, X_obs)] per block, in block order."""
         arr = (_lib.CrossBlock * len(entries))()
@@ -636,6 +661,17 @@ class Rhs:
 def _kdesc_array(kdesc):
     """ctypes descriptor array of a lowered kernel; an array built earlier (`lowered_array`) passes through."""
     return kdesc if isinstance(kdesc, C.Array) else _lib.make_kdesc_array(kdesc)
+
+
+def _wpair_array(pairs):
+    """ctypes `lpgp_wpair` array of [(kdesc, a, b)] and the descriptor arrays it points into (keep them alive for the call)."""
+    arr = (_lib.WPair * len(pairs))()
+    keep = []
+    for e, (kdesc, a, b) in zip(arr, pairs):
+        kd = _kdesc_array(kdesc)
+        keep.append(kd)
+        e.kd, e.ngroups, e.a, e.b = C.cast(kd, C.POINTER(_lib.KDesc)), len(kd), int(a), int(b)
+    return arr, keep
 
 
 def lowered_array(kdesc):

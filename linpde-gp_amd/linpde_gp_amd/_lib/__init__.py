@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LPGP_LIB", os.path.join(_HERE, "liblpgp.so"))     # $LPGP_LIB: a diagnostic build of the same library
 
 MAXD, MAXT, MAXG = 4, 256, 16
+MAXW = 4            # LPGP_MAXW: coefficient functions per variable-coefficient operator
 MATERN_HALFINT, EXPQUAD, MATERN_ISO = 1, 2, 3
 K_ASSEMBLE, K_SYRK, K_GEMM, K_POTRF_TILE, K_TRSM, K_COUNT = 0, 1, 2, 3, 4, 5
 KERNEL_NAMES = ("assemble", "syrk_trailing", "gemm", "potrf_tile", "trsm_gemm", "syrk_panel", "gemm_small", "matvec", "syrk_lookahead",
@@ -42,6 +43,11 @@ class KDesc(C.Structure):
 class CondBlock(C.Structure):
     """`lpgp_cond_block` (include/lpgp.h): one entry of the block row a conditioning assembles."""
     _fields_ = [("kd", C.POINTER(KDesc)), ("ngroups", C.c_int32), ("X1", C.c_void_p), ("F0", C.POINTER(C.c_void_p)), ("F1", C.POINTER(C.c_void_p))]
+
+
+class WPair(C.Structure):
+    """`lpgp_wpair` (include/lpgp.h): one pair (a, b) of a variable-coefficient block with its descriptor sum."""
+    _fields_ = [("kd", C.POINTER(KDesc)), ("ngroups", C.c_int32), ("a", C.c_int32), ("b", C.c_int32)]
 
 
 # int fn(void* user, int32 op, void* buf, int64 bytes, int32 root)   (lpgp_host_exchange_fn)
@@ -103,6 +109,8 @@ def _load() -> C.CDLL:
     sig("lpgp_mat_size", i64, vp)
     sig("lpgp_mat_padded_size", i64, vp)
     sig("lpgp_gram_assemble", C.c_int, vp, pk, i32, vp, vp, vp, i32, i32)
+    sig("lpgp_gram_assemble_weighted", C.c_int, vp, C.POINTER(WPair), i32, pd, i32, pd, i32, vp, vp, vp, i32, i32)
+    sig("lpgp_cross_assemble_weighted", C.c_int, vp, C.POINTER(WPair), i32, pd, i32, vp, vp, vp, vp, i32)
     sig("lpgp_mat_add_diag", C.c_int, vp, vp, i32, pd, dbl)
     sig("lpgp_mat_add_dense", C.c_int, vp, vp, i32, pd)
     sig("lpgp_mat_to_host", C.c_int, vp, vp, i32, pd)
@@ -165,7 +173,7 @@ EXPORTED = [
     "lpgp_dist_grid", "lpgp_dist_stats", "lpgp_dist_link_probe", "lpgp_pts_create", "lpgp_pts_destroy", "lpgp_mat_create",
     "lpgp_mat_destroy", "lpgp_mat_add_block", "lpgp_mat_pop_block", "lpgp_mat_set_view", "lpgp_mat_num_blocks",
     "lpgp_mat_num_blocks_total", "lpgp_mat_clone", "lpgp_mat_size", "lpgp_mat_padded_size",
-    "lpgp_gram_assemble", "lpgp_mat_add_diag", "lpgp_mat_add_dense", "lpgp_mat_to_host", "lpgp_mat_factor_diag",
+    "lpgp_gram_assemble", "lpgp_gram_assemble_weighted", "lpgp_cross_assemble_weighted", "lpgp_mat_add_diag", "lpgp_mat_add_dense", "lpgp_mat_to_host", "lpgp_mat_factor_diag",
     "lpgp_potrf", "lpgp_potrf_enqueue", "lpgp_mat_condition", "lpgp_mat_check", "lpgp_mat_truncate", "lpgp_potrs", "lpgp_solve_weights", "lpgp_mat_set_residual", "lpgp_rhs_create", "lpgp_rhs_destroy",
     "lpgp_cross_assemble", "lpgp_cross_assemble_row", "lpgp_predict", "lpgp_potrf_predict", "lpgp_trsm_lower", "lpgp_rhs_inner", "lpgp_rhs_matmul", "lpgp_gemm_host", "lpgp_mat_sub_inner", "lpgp_mat_factor_matmul",
     "lpgp_mat_evidence", "lpgp_mat_inverse_diag", "lpgp_mat_loo", "lpgp_mat_inverse", "lpgp_mat_evidence_grad", "lpgp_mat_evidence_grad_diag",

@@ -376,6 +376,9 @@ def condition(prior, Y, X, *, L, b, parent=None):
     """Forwarded `condition_on_observations`: same validation errors as the local call (raised by the workers and
     re-raised here), returns the proxy of the new posterior."""
     group = _active
+    if getattr(L, "_variable_coefficients", False) or (hasattr(L, "variable_terms") and L.variable_terms() is not None):
+        raise NotImplementedError("variable-coefficient operators (`VariableCoefficientOperator`) are not supported through the "
+                                  "`lp.spawn` multi-GPU front (single GPU only)")
     X = np.asarray(X) if (X is not None and type(X).__name__ == "DeviceArray") else X
     new_id = group.new_id()
     group.request("condition", new_id, None if parent is None else parent._oid, prior if parent is None else None, Y, X, L, b)

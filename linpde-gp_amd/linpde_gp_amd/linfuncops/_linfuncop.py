@@ -98,11 +98,15 @@ class LinearFunctionOperator:
         return -1.0 * self
 
     def __add__(self, other):
+        if getattr(other, "_variable_coefficients", False):
+            return NotImplemented        # `VariableCoefficientOperator.__radd__` flattens the sum into its term list
         if isinstance(other, LinearFunctionOperator):
             return SumLinearFunctionOperator(self, other)
         return NotImplemented
 
     def __sub__(self, other):
+        if getattr(other, "_variable_coefficients", False):
+            return NotImplemented
         if isinstance(other, LinearFunctionOperator):
             return SumLinearFunctionOperator(self, -other)
         return NotImplemented

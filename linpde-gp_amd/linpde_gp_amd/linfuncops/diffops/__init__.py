@@ -11,10 +11,11 @@ from ._operators import (
     TimeDerivative,
     WeightedLaplacian,
 )
+from ._variable import VariableCoefficientOperator
 
 __all__ = [
     "MultiIndex", "PartialDerivativeCoefficients", "LinearDifferentialOperator",
     "PartialDerivative", "TimeDerivative", "Derivative", "DirectionalDerivative",
     "WeightedLaplacian", "Laplacian", "SpatialLaplacian", "HeatOperator",
-    "ScaledLinearDifferentialOperator",
+    "ScaledLinearDifferentialOperator", "VariableCoefficientOperator",
 ]

@@ -68,10 +68,21 @@ class LinearFunctional:
 
         return _engine.Points(ctx, self.points())
 
+    # A functional built on a `diffops.VariableCoefficientOperator` has no coefficient map; its canonical form is
+    # "point evaluation of  sum_a f_a(x) (D_a f)(x)  at X":  `variable_terms()` = (weights f_a(X) as an (A, n) array,
+    # [coefficient map of D_a]), None for every constant-coefficient functional.
+    def variable_terms(self):
+        return None
+
     def __call__(self, f, /, *, argnum: int = 0):
         from ..functions import Function
         from ..randprocs import _gaussian_process as gps
         from ..randprocs import covfuncs
+
+        if not isinstance(f, Function) and self.variable_terms() is not None:
+            raise NotImplementedError(
+                "a functional of a variable-coefficient operator (`VariableCoefficientOperator`) can be conditioned on and applied "
+                f"to a `Function`; as a read-out of a {type(f).__name__} it is not supported yet")
 
         if isinstance(f, gps.ConditionalGaussianProcess):
             return gps.apply_linfunctl_to_conditional_gp(self, f)
@@ -210,6 +221,10 @@ class ScaledLinearFunctional(LinearFunctional):
     def coefficients_dict(self):
         return {mi: self._scalar * c for mi, c in self._linfunctl.coefficients_dict().items()}
 
+    def variable_terms(self):
+        vt = self._linfunctl.variable_terms()
+        return None if vt is None else (self._scalar * vt[0], vt[1])
+
     def _apply_to_function(self, f):
         return self._scalar * self._linfunctl(f)
 
@@ -259,6 +274,12 @@ class SumLinearFunctional(LinearFunctional):
                 out[mi] = out.get(mi, 0.0) + c
         return out
 
+    def variable_terms(self):
+        if any(s.variable_terms() is not None for s in self._summands):
+            raise NotImplementedError("a sum of functionals with a variable-coefficient operator (`VariableCoefficientOperator`) among them "
+                                      "is not supported: add the operators and evaluate the sum at the points")
+        return None
+
     def _apply_to_function(self, f):
         res = self._summands[0](f)
         for s in self._summands[1:]:
@@ -299,6 +320,19 @@ class CompositeLinearFunctional(LinearFunctional):
             raise NotImplementedError("only point evaluation may be composed with an operator")
         c0 = inner[(0,) * d]
         return {mi: c0 * c for mi, c in self._linfuncop.coefficients_dict().items()}
+
+    def variable_terms(self):
+        if not getattr(self._linfuncop, "_variable_coefficients", False):
+            if self._linfunctl.variable_terms() is not None:
+                raise NotImplementedError("a functional of a variable-coefficient operator may not be composed with a further operator")
+            return None
+        inner = self._linfunctl.coefficients_dict()
+        d = len(next(iter(inner)))
+        if set(inner) != {(0,) * d}:
+            raise NotImplementedError("only point evaluation may be composed with an operator")
+        X = self.points()
+        W = self._linfuncop.weights(X if self._input_domain_shape else X[:, 0])
+        return inner[(0,) * d] * W, [dict(c) for _, c in self._linfuncop.terms]
 
     def _apply_to_function(self, f):
         return self._linfunctl(self._linfuncop(f))

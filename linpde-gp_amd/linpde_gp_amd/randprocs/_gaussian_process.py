@@ -187,14 +187,59 @@ def _draws(S: "_engine.GramMatrix", mean: np.ndarray, z: np.ndarray, size: tuple
     return np.ascontiguousarray(out.T).reshape(size + batch)
 
 
+class _VariableCoeffs:
+    """Canonical form of a functional built on a `diffops.VariableCoefficientOperator`, in the place of the coefficient map
+    (`_preprocess_observations`): `weights[a, i] = f_a(x_i)`, evaluated on the host once per block, and the coefficient maps of
+    the constant-coefficient parts `D_a`."""
+    __slots__ = ("weights", "terms")
+
+    def __init__(self, weights, terms):
+        self.weights = np.ascontiguousarray(weights, dtype=np.double)
+        self.terms = [dict(t) for t in terms]
+
+
+_VARIABLE = "variable-coefficient operators (`VariableCoefficientOperator`)"
+
+
 class _ObservationBlock:
-    __slots__ = ("Y", "L", "b", "X", "coeffs", "points", "pred_mean")
+    __slots__ = ("Y", "L", "b", "X", "coeffs", "points", "pred_mean", "vterms", "weights")
 
     def __init__(self, Y, L, b, X, coeffs, points, pred_mean):
         self.Y, self.L, self.b, self.X = Y, L, b, X
+        self.vterms = self.weights = None
+        if isinstance(coeffs, _VariableCoeffs):
+            # L = sum_a f_a D_a: the coefficient maps of the D_a and the weights f_a(X), (A, n); no single coefficient map
+            self.vterms, self.weights, coeffs = coeffs.terms, coeffs.weights, None
         self.coeffs = coeffs          # coefficient map of the functional's operator part
         self.points = points          # device point set
         self.pred_mean = pred_mean    # L[m] + b.mean, flattened
+
+
+def _block_terms(ob):
+    """(weights (A, n), [coefficient map of D_a]) of an observation block  sum_a f_a D_a;  a constant-coefficient block is ONE
+    term of weight 1."""
+    if ob.vterms is not None:
+        return ob.weights, ob.vterms
+    return np.ones((1, ob.points.n)), [ob.coeffs]
+
+
+def _has_variable(blocks) -> bool:
+    return any(ob.vterms is not None for ob in blocks)
+
+
+def _assemble_block(mat, base, bi, bj, row_block, col_block):
+    """Block (bi, bj) of the Gram matrix, `col_block is row_block` for the diagonal block: the existing call for two
+    constant-coefficient blocks, `lpgp_gram_assemble_weighted` (entry-wise from the flattened points, also for tensor grids: a
+    weighted block is not a Kronecker product) as soon as either side has variable coefficients -- one pair (a, b) per pair
+    of terms, weight 1 / A = 1 for a constant-coefficient side."""
+    sym = col_block is row_block
+    if row_block.vterms is None and col_block.vterms is None:
+        mat.assemble(_lowered(base, row_block.coeffs, col_block.coeffs), row_block.points, None if sym else col_block.points, bi, bj)
+        return
+    w0, t0 = _block_terms(row_block)
+    w1, t1 = _block_terms(col_block)
+    pairs = [(_lowered(base, ca, cb), a, b) for a, ca in enumerate(t0) for b, cb in enumerate(t1)]
+    mat.assemble_weighted(pairs, w0, None if sym else w1, row_block.points, None if sym else col_block.points, bi, bj)
 
 
 class _GramOperator:
@@ -250,6 +295,13 @@ class _GramOperator:
         base = cgp._prior.cov
         tr = 0.0
         for ob in cgp._blocks:
+            if ob.vterms is not None:
+                # sum_i sum_ab f_a(x_i) f_b(x_i) (D_a k D_b'^*)(x_i, x_i)
+                for a, ca in enumerate(ob.vterms):
+                    for b, cb in enumerate(ob.vterms):
+                        tr += float(ob.weights[a] @ ob.weights[b]) * _engine.kernel_diag(cgp._state.ctx, _lowered(base, ca, cb))
+                tr += float(np.sum(_noise_diag(ob)))
+                continue
             k = covfuncs.DifferentiatedCovarianceFunction(covfuncs._base(base), *_combine(base, ob.coeffs, ob.coeffs))
             tr += ob.points.n * _engine.kernel_diag(cgp._state.ctx, k.lower())
             tr += float(np.sum(_noise_diag(ob)))
@@ -268,6 +320,15 @@ class _GramOperator:
         for i, bi in enumerate(cgp._blocks):
             for j, bj in enumerate(cgp._blocks):
                 if bi.points.n == 0 or bj.points.n == 0:
+                    continue
+                if bi.vterms is not None or bj.vterms is not None:
+                    # diag(f_a) K_ab diag(g_b) V, pair by pair, the scalings on the host
+                    (w0, t0), (w1, t1) = _block_terms(bi), _block_terms(bj)
+                    Vj = V2[offs[j]:offs[j + 1]]
+                    for a, ca in enumerate(t0):
+                        for b, cb in enumerate(t1):
+                            out[offs[i]:offs[i + 1]] += w0[a][:, None] * _engine.kernel_matvec(
+                                cgp._state.ctx, _lowered(base, ca, cb), bi.points, bj.points, np.ascontiguousarray(w1[b][:, None] * Vj))
                     continue
                 k = covfuncs.DifferentiatedCovarianceFunction(covfuncs._base(base), *_combine(base, bi.coeffs, bj.coeffs))
                 out[offs[i]:offs[i + 1]] += _engine.kernel_matvec(cgp._state.ctx, k.lower(), bi.points, bj.points,
@@ -467,6 +528,13 @@ def _block_noise(ob):
     return scalar, diag, dense
 
 
+def _refuse_variable_off_path(coeffs, ctx=None) -> None:
+    """Variable-coefficient observations exist on the dense single-GPU path only: refuse a multi-GPU context before any
+    device work (the `lp.spawn` front and the matrix-free posteriors refuse on their own)."""
+    if isinstance(coeffs, _VariableCoeffs) and (ctx if ctx is not None else _engine.default_context()).distributed:
+        raise NotImplementedError(f"{_VARIABLE} are not supported in a multi-GPU job (single GPU only)")
+
+
 _ROWS_SEEN_MAX = 4096        # (a hint only, and only where re-allocation matters: 128 MB; beyond, a copy is noise against the O(n^3) work)
 
 
@@ -477,12 +545,20 @@ class ConditionalGaussianProcess(GaussianProcess):
         # (room for the longest chain this prior has been conditioned into so far: the same model is typically conditioned again
         #  and again -- new data, new hyperparameters' worth of right-hand sides -- and a matrix that outgrows its allocation in the
         #  middle of a chain is re-allocated and copied: eight launches of a 1 152-row problem's sixty)
+        _refuse_variable_off_path(coeffs)
         state = _DeviceState(_engine.default_context(), capacity_hint=getattr(prior, "_rows_seen", 0))
         block = _ObservationBlock(Yf, Lf, bf, Xpts, coeffs, Lf.device_points(state.ctx), pred_mean)
         return cls._extend(prior, state, (), block)
 
     @classmethod
     def _extend(cls, prior, state, old_blocks, new_block):
+        """Append `new_block` to the chain `old_blocks` of `state` and return the new posterior.
+
+        A chain that contains a block with VARIABLE coefficients (`diffops.VariableCoefficientOperator`) -- the new block or
+        an earlier one -- takes the eager separate-call path whatever `config.lazy_factorization` says: factorisations still
+        deferred are flushed and verified first, then `lpgp_mat_add_block`, one `lpgp_gram_assemble_weighted` per block of
+        the row where either side is variable (the existing assembly otherwise), the noise, `lpgp_potrf`; a Gram matrix
+        that is not positive definite pops the block and raises exactly as the one-call path does."""
         from .. import config
 
         if new_block.points.n == 0:
@@ -504,7 +580,16 @@ class ConditionalGaussianProcess(GaussianProcess):
                 raise np.linalg.LinAlgError(state.failure)
             if len(state.blocks) != len(old_blocks):
                 state = _DeviceState(state.ctx, state.mat.clone(len(old_blocks)), old_blocks)
+        variable = new_block.vterms is not None or _has_variable(old_blocks)
+        if variable:
+            if state.ctx.distributed:
+                raise NotImplementedError(f"{_VARIABLE} are not supported in a multi-GPU job (single GPU only)")
+            state.verify()
+            if not state.owns(old_blocks):
+                raise np.linalg.LinAlgError(state.failure or "the Gram matrix of this posterior is not positive definite")
         state.use(len(old_blocks))
+        if variable:
+            return cls._extend_eager(prior, state, old_blocks, new_block)
         # lazy: a LARGE block that an earlier conditioning only assembled STAYS deferred when further blocks follow -- they are
         # factored together at the first use, with the prediction riding inside all of it (c5: the 32 768-row collocation block
         # is followed by a small block of interior values: 297 -> 290 ms).  Small deferred blocks are factored now: their tiny
@@ -551,6 +636,34 @@ class ConditionalGaussianProcess(GaussianProcess):
         # the representer weights are solved on first use (`representer_weights`, `mean`, ...):
         # in a chain of conditionings only the last object's weights are ever needed
         return cls(prior=prior, blocks=blocks, state=state, representer_weights=None)
+
+    @classmethod
+    def _extend_eager(cls, prior, state, old_blocks, new_block):
+        """The separate-call conditioning of a chain with a variable-coefficient block (see `_extend`)."""
+        mat, base = state.mat, prior.cov
+        state.invalidate()
+        scalar, diag, dense = _block_noise(new_block)
+        bi = mat.add_block(new_block.points.n)
+        try:
+            for j, ob in enumerate(tuple(old_blocks) + (new_block,)):
+                _assemble_block(mat, base, bi, j, new_block, ob)
+            if dense is not None:
+                mat.add_dense(bi, dense)
+            elif diag is not None or scalar != 0.0:
+                mat.add_diag(bi, diag, scalar)
+            info = mat.potrf()
+        except BaseException:
+            mat.pop_block()
+            raise
+        if info != 0:
+            mat.pop_block()
+            raise np.linalg.LinAlgError(
+                f"{info}-th leading minor of the (padded) Gram matrix is not positive definite")
+        state.blocks.append(new_block)
+        rows = sum(-(-k // 128) * 128 for k in mat.block_sizes)
+        if getattr(prior, "_rows_seen", 0) < rows <= _ROWS_SEEN_MAX:
+            prior._rows_seen = rows          # (the capacity hint of the next chain from this prior, as in `_extend`)
+        return cls(prior=prior, blocks=tuple(old_blocks) + (new_block,), state=state, representer_weights=None)
 
     def __init__(self, *, prior, blocks, state, representer_weights, test_coeffs=None):
         self._prior = prior
@@ -658,10 +771,14 @@ class ConditionalGaussianProcess(GaussianProcess):
             raise NotImplementedError("conditioning a transformed posterior is not supported")
         Yf, Lf, bf, Xpts, coeffs, pred_mean = self._preprocess_observations(
             prior=self._prior, Y=Y, X=X, L=L, b=b)
+        _refuse_variable_off_path(coeffs, self._state.ctx)
         block = _ObservationBlock(Yf, Lf, bf, Xpts, coeffs, Lf.device_points(self._state.ctx), pred_mean)
         from .. import config
         if config.matrix_free_above and not self._state.ctx.distributed and \
                 sum(ob.points.n for ob in self._blocks) + block.points.n > int(config.matrix_free_above):
+            if block.vterms is not None or _has_variable(self._blocks):
+                raise NotImplementedError(f"{_VARIABLE} are not supported on matrix-free posteriors (this chain has outgrown "
+                                          "`config.matrix_free_above`)")
             # (the threshold used to be consulted at the FIRST conditioning only -- a dense posterior re-conditioned past it
             #  stayed dense and could run out of memory.)  The chain continues matrix-free on the same observation blocks; the weights
             #  of this posterior, if they exist, warm-start the solve.
@@ -700,8 +817,9 @@ class ConditionalGaussianProcess(GaussianProcess):
                 raise TypeError(f"`b` must be a `Normal` or a `Constant` `RandomVariable` ({type(b)=})")
             if tuple(b.shape) != tuple(L.output_shape):
                 raise ValueError(f"{b.shape=} must be equal to {L.output_shape}")
-        coeffs = L.coefficients_dict()
+        vt = L.variable_terms()
         Xpts = L.points()
+        coeffs = L.coefficients_dict() if vt is None else _VariableCoeffs(*vt)
         # predictive mean  L[m] (+ b.mean)
         pred_mean = np.asarray(L(prior.mean), dtype=np.double).reshape(-1, order="C")
         Y = np.asarray(Y, dtype=np.double)
@@ -718,6 +836,16 @@ class ConditionalGaussianProcess(GaussianProcess):
         st = self._state
         rhs = _engine.Rhs(st.ctx, st.mat, Xtest_pts.n)
         base = self._prior.cov
+        if _has_variable(self._blocks):
+            # block by block: sum_a diag(f_a(X_obs)) (D_a k Ltest'^*)(X_obs, x) for a variable-coefficient block
+            # (`lpgp_cross_assemble_weighted`), the plain call for the others
+            for bi, ob in enumerate(self._blocks):
+                if ob.vterms is None:
+                    rhs.cross_assemble(_lowered(base, ob.coeffs, self._test_coeffs), ob.points, Xtest_pts, bi)
+                else:
+                    rhs.cross_assemble_weighted([(_lowered(base, c, self._test_coeffs), a, 0) for a, c in enumerate(ob.vterms)],
+                                                ob.weights, ob.points, Xtest_pts, bi)
+            return rhs
         # (L_obs k Ltest'^*)(X_obs, x)  == (Ltest k L_obs'^*)(x, X_obs) for the symmetric priors here; one call for the whole row
         # (blocks that share a descriptor share a launch)
         rhs.cross_assemble_row([(_lowered(base, ob.coeffs, self._test_coeffs), ob.points) for ob in self._blocks], Xtest_pts)
@@ -858,6 +986,8 @@ class ConditionalGaussianProcess(GaussianProcess):
         alive at most.  An earlier posterior of a chain answers for its own blocks; flushes, verifies and raises as
         `log_marginal_likelihood`.  An isotropic multivariate Matern prior raises `NotImplementedError` (no closed form of its
         lengthscale derivative here; use a `TensorProduct` prior)."""
+        if _has_variable(self._blocks):
+            raise NotImplementedError(f"`log_marginal_likelihood_gradient` is not available on a chain with {_VARIABLE} yet")
         base = self._prior.cov
         base_groups = covfuncs._base(base)._base_groups()
         G, d = len(base_groups), max(int(np.prod(self._prior.input_shape, dtype=int)), 1)

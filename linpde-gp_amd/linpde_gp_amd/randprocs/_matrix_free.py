@@ -278,7 +278,11 @@ class MatrixFreeConditionalGaussianProcess:
     @classmethod
     def from_observations(cls, prior, Y, X=None, *, L=None, b=None, previous=None):
         from ._gaussian_process import ConditionalGaussianProcess, _ObservationBlock
+        from ._gaussian_process import _VARIABLE, _VariableCoeffs
         Yf, Lf, bf, Xpts, coeffs, pred_mean = ConditionalGaussianProcess._preprocess_observations(prior=prior, Y=Y, X=X, L=L, b=b)
+        if isinstance(coeffs, _VariableCoeffs):
+            raise NotImplementedError(f"{_VARIABLE} are not supported on matrix-free posteriors (`config.matrix_free`, "
+                                      "`config.matrix_free_above`); condition on the dense path")
         ctx = _engine.default_context()
         block = _ObservationBlock(Yf, Lf, bf, Xpts, coeffs, Lf.device_points(ctx), pred_mean)
         old = () if previous is None else previous._blocks
