@@ -29,8 +29,17 @@ extern "C" {
  * It is not a product over dimensions: closed forms exist for at most ONE derivative per
  * argument (sum of the orders of n0 <= 1, of n1 <= 1), i.e. identity and directional derivatives:
  * `HalfIntegerMatern_Identity_DirectionalDerivative` (diffops/_matern.py:17-86) and
- * `HalfIntegerMatern_DirectionalDerivative_DirectionalDerivative` (:138-203).                */
-enum lpgp_family { LPGP_MATERN_HALFINT = 1, LPGP_EXPQUAD = 2, LPGP_MATERN_ISO = 3 };
+ * `HalfIntegerMatern_DirectionalDerivative_DirectionalDerivative` (:138-203).
+ * LPGP_MATERN_RADIAL: the SAME kernel (all d dimensions carry this family and one p, p >= 2 as soon as a term
+ * differentiates), with up to TWO derivatives per argument and term (sum of n0 <= 2, of n1 <= 2; mixed orders allowed):
+ * Laplacians, second partial derivatives and their sums on the isotropic kernel, where the reference falls back to JAX
+ * autodiff (linfuncops/diffops/_laplacian.py:57-68, _lindiffop.py:104-129).  With u = a .* (x - x'), s = |u|, psi(s^2 / 2) =
+ * kappa(s) every term is a finite sum of psi^(m)(t) times a monomial in u (csrc/lower.cpp: lower_radial_group), evaluated
+ * by kernels of their own (one sqrt, one exponential per entry).  Refused: p < 2 with a derivative on both arguments or two
+ * on one, more than two derivatives per argument, dlog_lengthscale != 0, p > 6.  Family 3 keeps its own lowering and bits.  Both isotropic families check the orders of EVERY
+ * term before they drop the terms with coef == 0, so a zero-coefficient term of too high an order is refused, not ignored
+ * (the Python layer never sends one: it drops zero terms before it lowers). */
+enum lpgp_family { LPGP_MATERN_HALFINT = 1, LPGP_EXPQUAD = 2, LPGP_MATERN_ISO = 3, LPGP_MATERN_RADIAL = 4 };
 
 typedef struct lpgp_ctx lpgp_ctx;   /* one per process / per GPU                          */
 typedef struct lpgp_pts lpgp_pts;   /* device-resident point set (n x d)                  */
@@ -63,7 +72,7 @@ typedef struct {
   lpgp_term terms[LPGP_MAXT];
   /* 0: the kernel itself.  j + 1: its derivative with respect to log lengthscale[j] -- the form above is closed under it
    * (csrc/lower.cpp), so every assembly / product entry point evaluates d G / d log l_j like any other block.  Product-form
-   * families only (LPGP_MATERN_ISO is refused).  A zero-initialised descriptor keeps its meaning.                        */
+   * families only (LPGP_MATERN_ISO and LPGP_MATERN_RADIAL are refused).  A zero-initialised descriptor keeps its meaning.                        */
   int32_t   dlog_lengthscale;
 } lpgp_kdesc;
 
@@ -222,7 +231,7 @@ int  lpgp_gram_assemble_grid(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroup
                              const lpgp_pts* const* F0, const lpgp_pts* const* F1,
                              lpgp_mat* mat, int32_t bi, int32_t bj);
 /* 1 if lpgp_gram_assemble_grid holds this sum (its tables of terms and of distinct 1-D matrices are fixed-size kernel
- * arguments: 48 terms over all summands, 16 distinct 1-D matrices per dimension; product-form kernels only, no summand with
+ * arguments: 48 terms over all summands, 16 distinct 1-D matrices per dimension; product-form kernels only (no isotropic family), no summand with
  * dlog_lengthscale != 0), 0 if the
  * caller must assemble the block entry-wise from the flattened grids (lpgp_gram_assemble).                              */
 int  lpgp_kron_fits(const lpgp_kdesc* kd, int32_t ngroups);

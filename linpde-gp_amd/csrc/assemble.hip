@@ -108,7 +108,9 @@ __device__ __forceinline__ void stage_factors(const DevDesc* __restrict__ desc, 
 // FACTORS: the per-point exponential factors (`asm_factors`, off by default) need 2 x FACT_MAXG * D * 2 * 64 doubles of LDS (32 KB
 // at D = 4); the default instantiation carries the 4-KB exponential table only (the generic kernel is the one that
 // takes everything the specialised kernels reject -- D >= 3, several groups, isotropic -- and ran at 4 / 3 workgroups per CU)
-template <int D, bool FACTORS>
+// RADIAL (never with FACTORS): the descriptor holds a radial Matern group (eval_entries.h: eval_radial_group); kernels of their
+// own, picked on the host, so that the instantiations above the radial family are what they were
+template <int D, bool FACTORS, bool RADIAL = false>
 __global__ __launch_bounds__(256) void assemble_kernel(const DevDesc* __restrict__ desc, AsmArgs a) {
   __shared__ double sx1[D][AT];
   __shared__ double sfr[FACTORS ? FACT_MAXG * D * 2 * AT : 1], sfc[FACTORS ? FACT_MAXG * D * 2 * AT : 1];
@@ -163,6 +165,8 @@ __global__ __launch_bounds__(256) void assemble_kernel(const DevDesc* __restrict
     } else if (fast) {
       LdsFactors<D> fac{sfr + lane, sfc + cb};
       eval_entries<D, AEK, LdsFactors<D>>(desc, dx, res, etab, fac);
+    } else if constexpr (RADIAL) {
+      eval_entries_radial<D, AEK>(desc, dx, res, etab);
     } else {
       eval_entries<D, AEK>(desc, dx, res, etab);
     }
@@ -201,7 +205,7 @@ struct WeightArgs {
   int64_t w0_stride, w1_stride;
 };
 
-template <int D>
+template <int D, bool RADIAL = false>       // RADIAL: some pair's descriptor holds a radial Matern group
 __global__ __launch_bounds__(256) void assemble_weighted_kernel(WeightArgs wa, AsmArgs a) {
   __shared__ double sx1[D][AT];
   __shared__ double sw1[LPGP_MAXW][AT];
@@ -244,7 +248,8 @@ __global__ __launch_bounds__(256) void assemble_weighted_kernel(WeightArgs wa, A
     for (int p = 0; p < wa.npairs; ++p) {
       const int qa = wa.pa[p], qb = wa.pb[p];                // (uniform: scalar loads from the kernel arguments)
       double res[AEK];
-      eval_entries<D, AEK>(wa.desc[p], dx, res, etab);
+      if constexpr (RADIAL) eval_entries_radial<D, AEK>(wa.desc[p], dx, res, etab);
+      else eval_entries<D, AEK>(wa.desc[p], dx, res, etab);
       const double wrow = qa == 0 ? wr[0] : (qa == 1 ? wr[1] : (qa == 2 ? wr[2] : wr[3]));      // (selects: no indexed register file)
       if (p == 0) {                                            // (a product, not fma(w, v, +0.0): keeps the sign of a zero entry)
 #pragma unroll
@@ -586,16 +591,7 @@ __global__ void add_dense_lower_kernel(double* a, int64_t ld, int64_t off, int64
 
 // bytes of a lowered descriptor that travel to the device: only the used prefix of the coefficient table
 static size_t desc_used_bytes(const DevDesc& host_desc) {
-  int ncoef = 0;
-  for (int gi = 0; gi < host_desc.ngroups; ++gi) {
-    const DevGroup& G = host_desc.g[gi];
-    for (int c = 0; c < G.ncls; ++c) {
-      int len = 1;
-      for (int dd = 0; dd < host_desc.d; ++dd) len *= G.deg[dd] + 1;
-      if (G.coef_off[c] + len > ncoef) ncoef = G.coef_off[c] + len;
-    }
-  }
-  return offsetof(DevDesc, coef) + (size_t)ncoef * sizeof(double);
+  return offsetof(DevDesc, coef) + (size_t)desc_coef_used(host_desc) * sizeof(double);
 }
 
 // Copy a lowered descriptor into the next slot of the context's ring (pinned host -> device,
@@ -623,7 +619,8 @@ int launch_assemble(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc,
   a.tiles_c = (int)((n1 + AT - 1) / AT);
   if (a.tiles_r == 0 || a.tiles_c == 0) return 0;
   static const int diag = [] { const char* e = std::getenv("LPGP_ASM_DIAG"); return e ? std::atoi(e) : 0; }();
-  a.flags = ((ctx->asm_factors && host_desc.ngroups <= FACT_MAXG) ? 1 : 0) | ((diag & 3) << 1);
+  const bool radial = desc_has_radial(host_desc);      // (radial groups take no per-point factors: their exponent is not a sum over dimensions)
+  a.flags = ((ctx->asm_factors && host_desc.ngroups <= FACT_MAXG && !radial) ? 1 : 0) | ((diag & 3) << 1);
   dim3 grid((unsigned)((int64_t)a.tiles_r * a.tiles_c));
   double entries = lower_only ? 0.5 * (double)n0 * ((double)n0 + 1.0) : (double)n0 * (double)n1;
   {
@@ -653,6 +650,15 @@ int launch_assemble(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc,
   lpgp_ctx::DescSlot& slot = *slotp;
   const DevDesc* d_desc = slot.d;
   prof_begin(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * entries);
+  if (radial) {
+    switch (host_desc.d) {
+      case 1: hipLaunchKernelGGL((assemble_kernel<1, false, true>), grid, dim3(256), 0, stream, d_desc, a); break;
+      case 2: hipLaunchKernelGGL((assemble_kernel<2, false, true>), grid, dim3(256), 0, stream, d_desc, a); break;
+      case 3: hipLaunchKernelGGL((assemble_kernel<3, false, true>), grid, dim3(256), 0, stream, d_desc, a); break;
+      case 4: hipLaunchKernelGGL((assemble_kernel<4, false, true>), grid, dim3(256), 0, stream, d_desc, a); break;
+      default: prof_end(ctx, stream); LPGP_CHECK(false, "assemble: d=%d", host_desc.d);
+    }
+  } else
   switch (host_desc.d) {
     case 1: if (a.flags & 1) hipLaunchKernelGGL((assemble_kernel<1, true>), grid, dim3(256), 0, stream, d_desc, a); else hipLaunchKernelGGL((assemble_kernel<1, false>), grid, dim3(256), 0, stream, d_desc, a); break;
     case 2: if (a.flags & 1) hipLaunchKernelGGL((assemble_kernel<2, true>), grid, dim3(256), 0, stream, d_desc, a); else hipLaunchKernelGGL((assemble_kernel<2, false>), grid, dim3(256), 0, stream, d_desc, a); break;
@@ -682,11 +688,13 @@ int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs
   if (n0 <= 0 || n1 <= 0) return 0;                // an empty block: nothing to stage, nothing to write
   std::vector<char> h;
   size_t off_desc[WT_MAXP];
+  bool radial = false;
   {
     std::unique_ptr<DevDesc> desc(new DevDesc);
     for (int p = 0; p < npairs; ++p) {
       LPGP_TRY_RC(lower_kdesc(pairs[p].kd, pairs[p].ngroups, desc.get()));
       LPGP_CHECK(desc->d == d, "assemble_weighted: pair %d lowers to d=%d, the points have d=%d", p, desc->d, d);
+      radial = radial || desc_has_radial(*desc);
       const size_t bytes = desc_used_bytes(*desc);
       off_desc[p] = h.size();
       h.resize(h.size() + (bytes + 15) / 16 * 16);
@@ -729,6 +737,15 @@ int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs
   const dim3 grid((unsigned)((int64_t)a.tiles_r * a.tiles_c));
   const double entries = sym ? 0.5 * (double)n0 * ((double)n0 + 1.0) : (double)n0 * (double)n1;
   prof_begin(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * entries);
+  if (radial) {
+    switch (d) {
+      case 1: hipLaunchKernelGGL((assemble_weighted_kernel<1, true>), grid, dim3(256), 0, stream, wa, a); break;
+      case 2: hipLaunchKernelGGL((assemble_weighted_kernel<2, true>), grid, dim3(256), 0, stream, wa, a); break;
+      case 3: hipLaunchKernelGGL((assemble_weighted_kernel<3, true>), grid, dim3(256), 0, stream, wa, a); break;
+      case 4: hipLaunchKernelGGL((assemble_weighted_kernel<4, true>), grid, dim3(256), 0, stream, wa, a); break;
+      default: prof_end(ctx, stream); LPGP_CHECK(false, "assemble_weighted: d=%d", d);
+    }
+  } else
   switch (d) {
     case 1: hipLaunchKernelGGL((assemble_weighted_kernel<1>), grid, dim3(256), 0, stream, wa, a); break;
     case 2: hipLaunchKernelGGL((assemble_weighted_kernel<2>), grid, dim3(256), 0, stream, wa, a); break;
@@ -816,7 +833,7 @@ int launch_assemble_batch(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host
 // slab of each 64-column tile, up to MV_R right-hand sides ride along per evaluation.
 // Partial sums per split go to `part`; mv_reduce_kernel adds them in a fixed order.
 // ---------------------------------------------------------------------------------------
-template <int D, bool FACTORS>
+template <int D, bool FACTORS, bool RADIAL = false>
 __global__ __launch_bounds__(256) void matvec_kernel(const DevDesc* __restrict__ desc, MvArgs a) {
   __shared__ double sx1[D][AT];
   __shared__ double sv[MV_R][AT];
@@ -873,6 +890,8 @@ __global__ __launch_bounds__(256) void matvec_kernel(const DevDesc* __restrict__
       if (fast) {
         LdsFactors<D> fac{sfr + lane, sfc + cb};
         eval_entries<D, AEK, LdsFactors<D>>(desc, dx, res, etab, fac);
+      } else if constexpr (RADIAL) {
+        eval_entries_radial<D, AEK>(desc, dx, res, etab);
       } else {
         eval_entries<D, AEK>(desc, dx, res, etab);
       }
@@ -916,7 +935,8 @@ int launch_matvec(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, c
   MvArgs a;
   a.x0 = x0; a.x1 = x1; a.n0 = n0; a.n1 = n1; a.n0_pad = n0_pad; a.n1_pad = n1_pad;
   a.v = v; a.v_stride = v_stride; a.part = part; a.nr = nr;
-  a.factors = (ctx->asm_factors && host_desc.ngroups <= FACT_MAXG) ? 1 : 0;
+  const bool radial = desc_has_radial(host_desc);
+  a.factors = (ctx->asm_factors && host_desc.ngroups <= FACT_MAXG && !radial) ? 1 : 0;
   a.tiles_r = (int)((n0 + AT - 1) / AT);
   a.tiles_c = (int)((n1 + AT - 1) / AT);
   a.splits = splits;
@@ -940,6 +960,15 @@ int launch_matvec(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, c
   int rc = stage_desc(ctx, stream, host_desc, &slot);
   if (rc != 0) return rc;
   prof_begin(ctx, stream, LPGP_K_MATVEC, 2.0 * (double)n0 * (double)n1 * nr, 0.0);
+  if (radial) {
+    switch (host_desc.d) {
+      case 1: hipLaunchKernelGGL((matvec_kernel<1, false, true>), grid, dim3(256), 0, stream, slot->d, a); break;
+      case 2: hipLaunchKernelGGL((matvec_kernel<2, false, true>), grid, dim3(256), 0, stream, slot->d, a); break;
+      case 3: hipLaunchKernelGGL((matvec_kernel<3, false, true>), grid, dim3(256), 0, stream, slot->d, a); break;
+      case 4: hipLaunchKernelGGL((matvec_kernel<4, false, true>), grid, dim3(256), 0, stream, slot->d, a); break;
+      default: prof_end(ctx, stream); LPGP_CHECK(false, "matvec: d=%d", host_desc.d);
+    }
+  } else
   switch (host_desc.d) {
     case 1: if (a.factors) hipLaunchKernelGGL((matvec_kernel<1, true>), grid, dim3(256), 0, stream, slot->d, a); else hipLaunchKernelGGL((matvec_kernel<1, false>), grid, dim3(256), 0, stream, slot->d, a); break;
     case 2: if (a.factors) hipLaunchKernelGGL((matvec_kernel<2, true>), grid, dim3(256), 0, stream, slot->d, a); else hipLaunchKernelGGL((matvec_kernel<2, false>), grid, dim3(256), 0, stream, slot->d, a); break;
@@ -1273,7 +1302,7 @@ bool kron_fits(const lpgp_kdesc* kd, int ngroups) {
   int nterms = 0;
   for (int g = 0; g < ngroups; ++g) {
     const lpgp_kdesc& K = kd[g];
-    if (K.d != D || K.family[0] == LPGP_MATERN_ISO || K.nterms < 0 || K.nterms > LPGP_MAXT) return false;
+    if (K.d != D || K.family[0] == LPGP_MATERN_ISO || K.family[0] == LPGP_MATERN_RADIAL || K.nterms < 0 || K.nterms > LPGP_MAXT) return false;
     if (K.dlog_lengthscale != 0) return false;   // a lengthscale derivative (lower.cpp) is assembled entry-wise: the 1-D factor matrices are built from plain factors
     nterms += K.nterms;
     if (nterms > KR_MAXT) return false;
@@ -1320,7 +1349,7 @@ int launch_assemble_kron(lpgp_ctx* ctx, hipStream_t stream, const lpgp_kdesc* kd
   for (int g = 0; g < ngroups; ++g) {
     const lpgp_kdesc& K = kd[g];
     LPGP_CHECK(K.d == D, "kron assembly: group %d has d=%d != %d", g, K.d, D);
-    LPGP_CHECK(K.family[0] != LPGP_MATERN_ISO, "kron assembly: an isotropic Matern is not a product over dimensions");
+    LPGP_CHECK(K.family[0] != LPGP_MATERN_ISO && K.family[0] != LPGP_MATERN_RADIAL, "kron assembly: an isotropic Matern is not a product over dimensions");
     for (int t = 0; t < K.nterms; ++t) {
       LPGP_CHECK(a.nterms < KR_MAXT, "kron assembly: more than %d terms (lpgp_kron_fits tells beforehand)", KR_MAXT);
       const int ti = a.nterms++;

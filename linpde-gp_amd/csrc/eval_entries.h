@@ -123,7 +123,94 @@ struct MemCoef {
   LPGP_HD double operator()(int idx) const { return base[idx]; }
 };
 
-template <int D, int NE, class Fac, class Coef>
+// One radial Matern group (LPGP_MATERN_RADIAL, DevGroup::iso == 2; layout: lpgp_desc.h, derivation: lower.cpp) added into res:
+//   scale * e^{-s} * sum_m Theta_m(s) Pi_m(u),   u = a .* dx,  s = |u|,
+// one sqrt, one reciprocal and one lpgp_exp_neg per entry.  Pi_m is a sparse list of monomials (the exponents are uniform: scalar
+// loops of at most four multiplies), Theta_m a Horner chain in s plus, for m >= 3, a Horner chain in 1 / s that starts FROM Pi_m, so
+// that every partial product stays bounded (a monomial of Pi_m has a higher degree than the most negative power it meets).  At
+// s = 0 the reciprocal is replaced by 0 through a select: the negative powers then contribute h = 0 exactly (no 0 * inf), a
+// non-constant monomial c * 0, and what remains is the diagonal value as lower.cpp stores it for desc_diag, operation for operation.
+template <int D, int NE>
+LPGP_HD void eval_radial_group(const DevDesc* __restrict__ desc, const DevGroup& G, const double (&dx)[D][NE], double (&res)[NE],
+                               const ExpTab& tab) {
+  double u[D][NE], s2[NE];
+#pragma unroll
+  for (int e = 0; e < NE; ++e) s2[e] = 0.0;
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    const double a = G.a[j];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+      u[j][e] = a * dx[j][e];
+      s2[e] = fma(u[j][e], u[j][e], s2[e]);
+    }
+  }
+  double sv[NE], inv[NE], tot[NE];
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    sv[e] = sqrt(s2[e]);
+    inv[e] = sv[e] > 0.0 ? 1.0 / sv[e] : 0.0;
+    tot[e] = 0.0;
+  }
+  const int p = G.deg[0];
+  const int TL = rad_theta_len(p);
+  const double* th = desc->coef + G.coef_off[0] + 1;
+  const double* mono = desc->coef + G.coef_off[1];
+#pragma unroll 1
+  for (int m = 0; m < RAD_M; ++m, th += TL) {
+    const int nm = G.parity[1 + m];
+    if (nm == 0) continue;
+    double pim[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) pim[e] = 0.0;
+#pragma unroll 1
+    for (int q = 0; q < nm; ++q, mono += 2) {
+      const double c = mono[0];
+      unsigned long long raw;
+      __builtin_memcpy(&raw, mono + 1, 8);
+      const unsigned bits = (unsigned)raw;
+      double pr[NE];
+#pragma unroll
+      for (int e = 0; e < NE; ++e) pr[e] = 1.0;
+#pragma unroll
+      for (int j = 0; j < D; ++j)
+        for (int k = (int)((bits >> (3 * j)) & 7u); k > 0; --k) {
+#pragma unroll
+          for (int e = 0; e < NE; ++e) pr[e] *= u[j][e];
+        }
+#pragma unroll
+      for (int e = 0; e < NE; ++e) pim[e] = fma(c, pr[e], pim[e]);
+    }
+    double thv[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) thv[e] = 0.0;
+    for (int k = p; k >= 0; --k) {
+      const double c = th[k];
+#pragma unroll
+      for (int e = 0; e < NE; ++e) thv[e] = fma(thv[e], sv[e], c);
+    }
+    if (m >= 3) {
+      const double n1 = th[p + 1], n2 = th[p + 2], n3 = th[p + 3];
+#pragma unroll
+      for (int e = 0; e < NE; ++e) {
+        double h = pim[e] * n3;
+        h = fma(h, inv[e], pim[e] * n2);
+        h = fma(h, inv[e], pim[e] * n1);
+        h *= inv[e];
+        tot[e] = fma(thv[e], pim[e], tot[e]) + h;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < NE; ++e) tot[e] = fma(thv[e], pim[e], tot[e]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < NE; ++e) res[e] = fma(G.scale * lpgp_exp_neg(sv[e], tab), tot[e], res[e]);
+}
+
+// RADIAL: the descriptor may hold radial Matern groups (iso == 2).  The launch sites pick the RADIAL instantiations on the host
+// (desc_has_radial); the others never meet such a group and carry none of its code.
+template <int D, int NE, class Fac, class Coef, bool RADIAL = false>
 LPGP_HD void eval_entries(const DevDesc* __restrict__ desc,
                                              const double (&dx)[D][NE], double (&res)[NE], const Fac& fac, const Coef& coef,
                                              const ExpTab& tab) {
@@ -132,6 +219,12 @@ LPGP_HD void eval_entries(const DevDesc* __restrict__ desc,
   for (int e = 0; e < AE; ++e) res[e] = 0.0;
   for (int g = 0; g < desc->ngroups; ++g) {
     const DevGroup& G = desc->g[g];
+    if constexpr (RADIAL) {
+      if (G.iso == 2) {
+        eval_radial_group<D, NE>(desc, G, dx, res, tab);
+        continue;
+      }
+    }
     if (G.iso) {
       // isotropic Matern: e^{-s} [Q0(s) + (w.u) Q1(s) + (u^T B u) Q2(s)],  u = a .* dx, s = |u|
       double s2[AE], lin[AE], quad[AE];
@@ -287,6 +380,12 @@ template <int D, int NE = AE, class Fac = NoFactors>
 LPGP_HD void eval_entries(const DevDesc* __restrict__ desc, const double (&dx)[D][NE], double (&res)[NE], const ExpTab& tab,
                           const Fac& fac = Fac()) {
   eval_entries<D, NE, Fac, MemCoef>(desc, dx, res, fac, MemCoef{desc->coef}, tab);
+}
+
+// the same for a descriptor that may hold radial Matern groups
+template <int D, int NE = AE>
+LPGP_HD void eval_entries_radial(const DevDesc* __restrict__ desc, const double (&dx)[D][NE], double (&res)[NE], const ExpTab& tab) {
+  eval_entries<D, NE, NoFactors, MemCoef, true>(desc, dx, res, NoFactors(), MemCoef{desc->coef}, tab);
 }
 
 }  // namespace lpgp

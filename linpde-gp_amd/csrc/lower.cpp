@@ -10,6 +10,8 @@
 #include <cstdio>
 #include <cstddef>
 #include <cstring>
+#include <map>
+#include <utility>
 #include <vector>
 
 #include "lpgp_desc.h"
@@ -152,6 +154,140 @@ static int lower_iso_group(const lpgp_kdesc& K, int d, DevGroup& G, double* coef
   return 0;
 }
 
+// Isotropic Matern with up to TWO derivatives per argument (LPGP_MATERN_RADIAL).  With u = a .* (x - x'), s = |u|, t = s^2 / 2 and
+// psi(t) = kappa(s) the only non-zero derivatives of t are d_i t = u_i and d_i^2 t = 1, so (Faa di Bruno)
+//   d_u^alpha psi = sum_{j <= alpha / 2} psi^(|alpha| - |j|)(t) prod_d alpha_d! / (j_d! (alpha_d - 2 j_d)! 2^{j_d}) u_d^{alpha_d - 2 j_d},
+//   d/dx_i = a_i d/du_i,  d/dx'_i = -a_i d/du_i,
+// and the term list sums into  e^{-s} sum_{m = 0..4} Theta_m(s) Pi_m(u):  e^{-s} Theta_m = psi^(m),  Theta_0 = P_p,
+// Theta_{m+1} = (Theta_m' - Theta_m) / s -- a polynomial for m <= p, a finite Laurent polynomial beyond (p = 2: Theta_3 = -1/(3 s),
+// Theta_4 = (1 + s)/(3 s^3)); a monomial of Pi_m has degree 2 m - |alpha| >= 2 m - 4, above the most negative power 2 (m - p) - 1
+// of Theta_m, so every singular product vanishes at s = 0 and only the constant monomials (m = |alpha| / 2 <= 2 <= p) survive there.
+// The Theta_m come from the exact integer numerators over D_p, the monomial coefficients are summed in long double; each is
+// rounded to double once.  Layout: lpgp_desc.h.
+static int lower_radial_group(const lpgp_kdesc& K, int d, DevGroup& G, double* coef, int& coef_used) {
+  LPGP_CHECK(K.dlog_lengthscale == 0,
+             "lower_kdesc: the derivative with respect to a lengthscale is not implemented for the isotropic Matern (LPGP_MATERN_RADIAL)");
+  const int p = K.p[0];
+  LPGP_CHECK(p >= 0 && p <= 6, "lower_kdesc: Matern p=%d unsupported", p);
+  long double a[LPGP_MAXD];
+  for (int j = 0; j < d; ++j) {
+    LPGP_CHECK(K.family[j] == LPGP_MATERN_RADIAL && K.p[j] == p,
+               "lower_kdesc: an isotropic Matern spans all dimensions with one nu");
+    LPGP_CHECK(K.lengthscale[j] > 0, "lower_kdesc: lengthscale must be positive");
+    const double as = std::sqrt(2.0 * (p + 0.5)) / K.lengthscale[j];
+    a[j] = as;
+    G.a[j] = as;
+    G.expkind[j] = 1;
+    G.deg[j] = 0;
+  }
+  G.deg[0] = p;
+  G.iso = 2;
+  std::map<std::pair<int, int>, long double> mono;          // (m, packed exponents of u) -> coefficient of Pi_m
+  bool any = false, high = false;
+  for (int t = 0; t < K.nterms; ++t) {
+    const lpgp_term& T = K.terms[t];
+    int o0 = 0, o1 = 0, al[LPGP_MAXD] = {0, 0, 0, 0};
+    for (int j = 0; j < d; ++j) {
+      LPGP_CHECK(T.n0[j] >= 0 && T.n1[j] >= 0, "lower_kdesc: derivative order out of range");
+      o0 += T.n0[j];
+      o1 += T.n1[j];
+      al[j] = T.n0[j] + T.n1[j];
+    }
+    LPGP_CHECK(o0 <= 2 && o1 <= 2,
+               "lower_kdesc: the isotropic Matern (LPGP_MATERN_RADIAL) takes at most two derivatives per argument");
+    if (T.coef == 0.0) continue;
+    any = any || o0 + o1 > 0;
+    high = high || o0 == 2 || o1 == 2 || (o0 && o1);
+    long double pref = (o1 & 1) ? -(long double)T.coef : (long double)T.coef;
+    for (int j = 0; j < d; ++j) pref *= std::pow(a[j], al[j]);
+    int jj[LPGP_MAXD] = {0, 0, 0, 0};
+    for (;;) {
+      long double w = pref;
+      int m = o0 + o1, bits = 0;
+      for (int j = 0; j < d; ++j) {
+        w *= ifact(al[j]) / (ifact(jj[j]) * ifact(al[j] - 2 * jj[j]) * std::pow(2.0L, jj[j]));
+        m -= jj[j];
+        bits |= (al[j] - 2 * jj[j]) << (3 * j);
+      }
+      mono[std::make_pair(m, bits)] += w;
+      int j = d - 1;
+      while (j >= 0) {
+        if (2 * (++jj[j]) <= al[j]) break;
+        jj[j] = 0;
+        --j;
+      }
+      if (j < 0) break;
+    }
+  }
+  LPGP_CHECK(!any || p >= 1, "lower_kdesc: Matern-1/2 is not differentiable");
+  LPGP_CHECK(!high || p >= 2,
+             "lower_kdesc: a multivariate Matern needs nu >= 5/2 for two derivatives on one argument or a derivative on both");
+  // Theta_m as Laurent polynomials: th[m][OFF + k] = numerator of the coefficient of s^k over D_p
+  constexpr int OFF = 12;
+  long double th[RAD_M][OFF + 16] = {};
+  long double P0[16];
+  const long double D = matern_poly_num(p, 0, P0);
+  for (int k = 0; k <= p; ++k) th[0][OFF + k] = P0[k];
+  for (int m = 0; m + 1 < RAD_M; ++m)
+    for (int k = -OFF; k < p; ++k) th[m + 1][OFF + k] = (k + 2) * th[m][OFF + k + 2] - th[m][OFF + k + 1];
+  const int TL = rad_theta_len(p);
+  int nmono = 0;
+  bool used[RAD_M] = {false, false, false, false, false};
+  for (auto& kv : mono)
+    if (kv.second != 0.0L) {
+      ++nmono;
+      LPGP_CHECK(kv.first.first >= 0 && kv.first.first < RAD_M, "lower_kdesc: radial order %d out of range", kv.first.first);
+      used[kv.first.first] = true;
+    }
+  const int need = 1 + RAD_M * TL + 2 * nmono;
+  LPGP_CHECK(coef_used + need <= MAXCOEF, "lower_kdesc: coefficient table overflow");
+  double* base = coef + coef_used;
+  double* tab = base + 1;
+  for (int m = 0; m < RAD_M; ++m) {
+    for (int k = 0; k < TL; ++k) tab[m * TL + k] = 0.0;
+    if (!used[m]) continue;                                // (Theta_m of a p below 2 is more singular; nothing reads it)
+    for (int k = -OFF; k < -RAD_NEG; ++k)
+      LPGP_CHECK(th[m][OFF + k] == 0.0L, "lower_kdesc: the radial Matern table has a power below s^-%d (p=%d)", RAD_NEG, p);
+    for (int k = 0; k <= p; ++k) tab[m * TL + k] = (double)(th[m][OFF + k] / D);
+    for (int k = 1; k <= RAD_NEG; ++k) tab[m * TL + p + k] = (double)(th[m][OFF - k] / D);
+  }
+  double* ml = tab + RAD_M * TL;
+  int cnt[RAD_M] = {0, 0, 0, 0, 0};
+  for (auto& kv : mono) {                                  // (ordered by m, then by the packed exponents)
+    if (kv.second == 0.0L) continue;
+    const int m = kv.first.first;
+    LPGP_CHECK(m <= p || kv.first.second != 0, "lower_kdesc: a singular radial term without a vanishing monomial (p=%d)", p);
+    ml[0] = (double)kv.second;
+    const unsigned long long bits = (unsigned long long)(unsigned)kv.first.second;
+    std::memcpy(ml + 1, &bits, 8);
+    ml += 2;
+    ++cnt[m];
+  }
+  // the diagonal value, operation for operation what the evaluation (eval_entries.h: eval_radial_group) computes at u = 0: a
+  // constant monomial contributes its coefficient, every other one c * 0; Theta_m(0) is its constant coefficient, the negative
+  // powers are switched off
+  double tot = 0.0;
+  const double* q = tab + RAD_M * TL;
+  for (int m = 0; m < RAD_M; ++m) {
+    if (cnt[m] == 0) continue;
+    double pim = 0.0;
+    for (int i = 0; i < cnt[m]; ++i, q += 2) {
+      unsigned long long bits;
+      std::memcpy(&bits, q + 1, 8);
+      pim = std::fma(q[0], bits == 0 ? 1.0 : 0.0, pim);
+    }
+    tot = std::fma(tab[m * TL], pim, tot);
+  }
+  base[0] = tot;
+  G.ncls = 1;
+  G.parity[0] = 0;
+  for (int m = 0; m < RAD_M; ++m) G.parity[1 + m] = cnt[m];
+  G.coef_off[0] = coef_used;
+  G.coef_off[1] = coef_used + 1 + RAD_M * TL;
+  coef_used += need;
+  return 0;
+}
+
 // d / d log lengthscale of one Matern factor of total order n (lpgp_kdesc::dlog_lengthscale).  The factor a^n e^{-r} P_n(r),
 // r = a |x - x'|, depends on the lengthscale through a ~ 1 / lengthscale alone, and
 //   d/d log a [a^n e^{-r} P_n(r)] = a^n e^{-r} [n P_n(r) + r (P_n' - P_n)(r)] = a^n e^{-r} [n P_n(r) + r P_{n+1}(r)]:
@@ -207,6 +343,11 @@ int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out) {
     G.scale = K.scale;
     if (K.family[0] == LPGP_MATERN_ISO) {
       int rc = lower_iso_group(K, d, G, out->coef, coef_used);
+      if (rc != 0) return rc;
+      continue;
+    }
+    if (K.family[0] == LPGP_MATERN_RADIAL) {
+      int rc = lower_radial_group(K, d, G, out->coef, coef_used);
       if (rc != 0) return rc;
       continue;
     }
@@ -313,6 +454,31 @@ double desc_diag(const DevDesc& desc) {
     for (int c = 0; c < desc.g[g].ncls; ++c)
       if (desc.g[g].parity[c] == 0) v += desc.g[g].scale * desc.coef[desc.g[g].coef_off[c]];
   return v;
+}
+
+bool desc_has_radial(const DevDesc& desc) {
+  for (int g = 0; g < desc.ngroups; ++g)
+    if (desc.g[g].iso == 2) return true;
+  return false;
+}
+
+int desc_coef_used(const DevDesc& desc) {
+  int ncoef = 0;
+  for (int gi = 0; gi < desc.ngroups; ++gi) {
+    const DevGroup& G = desc.g[gi];
+    if (G.iso == 2) {
+      int end = G.coef_off[1];
+      for (int m = 0; m < RAD_M; ++m) end += 2 * G.parity[1 + m];
+      if (end > ncoef) ncoef = end;
+      continue;
+    }
+    for (int c = 0; c < G.ncls; ++c) {
+      int len = 1;
+      for (int dd = 0; dd < desc.d; ++dd) len *= G.deg[dd] + 1;
+      if (G.coef_off[c] + len > ncoef) ncoef = G.coef_off[c] + len;
+    }
+  }
+  return ncoef;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -29,6 +29,8 @@ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 // r_d = |a_d (x_d - x'_d)|, E = r (Matern) or r^2/2 (ExpQuad); Poly_c dense nested-Horner
 // coefficient tensor.  Built on the host by lower_kdesc (lower.cpp).
 constexpr int MAXCLS = 16;         // parity classes (2^d, d <= 4)
+constexpr int RAD_M = 5;           // radial Matern group: psi^(0) .. psi^(4)
+constexpr int RAD_NEG = 3;         // ... negative powers of s a Theta_m may carry (p >= 2, m <= 4: at most s^-3)
 constexpr int MAXCOEF = 8192;      // coefficient doubles over all groups (only the used part is staged to the device)
 
 struct DevGroup {
@@ -43,6 +45,14 @@ struct DevGroup {
   //   entry = scale * exp(-s) * [ Q0(s) + (w . u) Q1(s) + (u^T B u) Q2(s) ],
   // Q0, Q1, Q2 of degree deg[0] at coef_off[0..2] (ncls = 3; parity[0] = 0 so that the constant
   // coefficient of Q0 is the diagonal value, as for the product form)
+  // radial Matern group (LPGP_MATERN_RADIAL, iso == 2): up to two derivatives per argument,
+  //   entry = scale * exp(-s) * sum_{m=0..4} Theta_m(s) Pi_m(u),   exp(-s) Theta_m(s) = psi^(m)(s^2 / 2),  psi(s^2 / 2) = kappa(s).
+  // coef_off[0]: one double, the diagonal value before the scale (ncls = 1, parity[0] = 0: desc_diag reads it like a
+  //   product-form class), then Theta_0..Theta_4, rad_theta_len(p) doubles each: the coefficients of s^0..s^p (p = deg[0]), then
+  //   those of s^-1, s^-2, s^-3 (zero while m <= p).
+  // coef_off[1]: the monomials of Pi_0, Pi_1, .., Pi_4 one after another, parity[1 + m] of them for Pi_m, two doubles each: the
+  //   coefficient, and a double whose low 32 bits hold the exponents of u_0..u_3, three bits each (a sparse list: 6 monomials
+  //   for a pair of Laplacians in 2-D, 15 in 4-D, against 5^d coefficients per m of a dense tensor).
   int32_t iso, has_lin, has_quad;
   double w[LPGP_MAXD];
   double B[LPGP_MAXD * LPGP_MAXD];
@@ -55,7 +65,13 @@ struct DevDesc {
   double coef[MAXCOEF];
 };
 
+// doubles of one Theta_m of a radial Matern group (host and device: the lowering writes, eval_entries.h reads by this stride)
+constexpr int rad_theta_len(int p) { return p + 1 + RAD_NEG; }
 int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out);
+// does the lowered descriptor hold a radial Matern group (iso == 2)?  Those are evaluated by the RADIAL instantiations only.
+bool desc_has_radial(const DevDesc& desc);
+// doubles of the coefficient table the descriptor uses (what travels to the device)
+int desc_coef_used(const DevDesc& desc);
 // The pair list and the weight counts of lpgp_gram_assemble_weighted / lpgp_cross_assemble_weighted (`fn`: the name in the
 // message).  WP_RECT: an off-diagonal block, a < A0 and b < A1.  WP_SYM: a diagonal block, b indexes the row weights (A1 is
 // ignored) and the list must hold as many pairs (a, b) as (b, a).  WP_CROSS: every b must be 0 (A1 is ignored).  Also: one

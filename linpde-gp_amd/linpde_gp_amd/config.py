@@ -66,3 +66,13 @@ defer_min_rows: int = 4096
 # of the largest one, so a covariance that is singular in exact arithmetic (noise-free observations) has computed eigenvalues of
 # either sign at that level; two decades above it inflates a standard deviation that was zero by 1e-3 of the prior's.
 sample_damping: float = 1e-6
+
+# Isotropic multivariate Matérn priors (`covfuncs.Matern((d,), ...)`, d > 1) under operators of SECOND order -- `Laplacian`,
+# `WeightedLaplacian`, second `PartialDerivative`s, their sums and `VariableCoefficientOperator`s over them -- on either argument.
+# True: such a kernel lowers to the radial family (`LPGP_MATERN_RADIAL`, include/lpgp.h: psi^(m)(s^2 / 2) times a monomial of
+# a .* (x - x') in closed form, kernels of their own); it needs nu >= 5/2 (`ValueError` below), more than two derivatives per
+# argument still raise `NotImplementedError`.  Kernels with at most one derivative per argument keep the family they have today,
+# bit for bit, whatever the flag says.  False (the default): everything above first order raises `NotImplementedError`, as it
+# always has -- the default stays off because two existing tests (tests/test_host_api.py, tests/test_gpu_matern_iso.py) pin that
+# refusal as the behaviour of an unconfigured package.
+isotropic_matern_higher_order: bool = False

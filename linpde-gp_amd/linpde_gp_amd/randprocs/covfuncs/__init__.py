@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..._lib import EXPQUAD, MATERN_HALFINT, MATERN_ISO, MAXD, MAXG, MAXT
+from ..._lib import EXPQUAD, MATERN_HALFINT, MATERN_ISO, MATERN_RADIAL, MAXD, MAXG, MAXT
 
 
 def _as_shape(shape):
@@ -149,7 +149,11 @@ class Matern(CovarianceFunction):
     ISOTROPIC kernel (scalar or per-dimension lengthscales); closed forms exist for identity and
     directional derivatives on either argument (`HalfIntegerMatern_Identity_DirectionalDerivative`,
     `HalfIntegerMatern_DirectionalDerivative_DirectionalDerivative`, `_matern.py:17-264`), anything
-    of higher order raises NotImplementedError (the reference falls back to JAX autodiff there)."""
+    of higher order raises NotImplementedError (the reference falls back to JAX autodiff there) --
+    unless `config.isotropic_matern_higher_order` is set: then up to two derivatives per argument
+    (`Laplacian`, `WeightedLaplacian`, second `PartialDerivative`s, sums, scalings and
+    `VariableCoefficientOperator`s of these) lower to the radial closed form `LPGP_MATERN_RADIAL`
+    (needs nu >= 5/2; three or more derivatives on one argument still raise NotImplementedError)."""
 
     def __init__(self, input_shape=(), nu=1.5, lengthscales=1.0):
         super().__init__(input_shape)
@@ -424,16 +428,31 @@ def lower_groups(base_groups, L0: dict, L1: dict):
         d = len(factors)
         if d > MAXD:
             raise NotImplementedError(f"at most {MAXD} input dimensions are supported")
+        radial = False
         for c, a, b in term_list:
             if len(a) != d or len(b) != d:
                 raise ValueError("operator and kernel dimensions do not match")
             if factors[0][0] == MATERN_ISO:
                 p = factors[0][1]
                 if (sum(a) > 1 or sum(b) > 1) and c != 0.0:
-                    raise NotImplementedError(
-                        "the isotropic multivariate Matérn kernel has closed forms for identity and "
-                        "directional derivatives only (no JAX autodiff fallback on the MI355X path); "
-                        "use a `TensorProduct` prior for higher-order operators")
+                    from ... import config
+
+                    if not config.isotropic_matern_higher_order:
+                        raise NotImplementedError(
+                            "the isotropic multivariate Matérn kernel has closed forms for identity and "
+                            "directional derivatives only (no JAX autodiff fallback on the MI355X path); "
+                            "use a `TensorProduct` prior for higher-order operators")
+                    if sum(a) > 2 or sum(b) > 2:
+                        raise NotImplementedError(
+                            "the isotropic multivariate Matérn kernel has closed forms for at most two derivatives "
+                            "per argument (`config.isotropic_matern_higher_order`); use a `TensorProduct` prior "
+                            "for operators of higher order")
+                    if p < 2:
+                        raise ValueError(
+                            f"a multivariate Matérn-{p}+1/2 kernel does not admit a second-order operator "
+                            "(nu >= 5/2 is needed)")
+                    radial = True
+                    continue
                 if sum(a) + sum(b) > p and c != 0.0:
                     raise ValueError(
                         f"a multivariate Matérn-{p}+1/2 kernel does not admit {sum(a) + sum(b)} "
@@ -446,7 +465,8 @@ def lower_groups(base_groups, L0: dict, L1: dict):
                         "(mean-square sense); choose a smoother prior")
         groups.append({
             "d": d,
-            "family": [f[0] for f in factors],
+            # a group with a second-order term is the radial family; all others keep today's family and bits
+            "family": [MATERN_RADIAL if radial else f[0] for f in factors],
             "p": [f[1] for f in factors],
             "lengthscale": [f[2] for f in factors],
             "scale": scale,
