@@ -72,7 +72,7 @@ __device__ __forceinline__ double pcg_sum(const double* part, int c, int G) {
 }
 // which = 0 (start):   rz = <R, Z>, rr = <R, R>: rel = sqrt(rr) / bn, active = rel > rtol
 // which = 1 (alpha):   pq = <P, Q>; alpha = active && pq > 0 ? rz / pq : 0
-// which = 2 (beta):    rz' = <R, Z>, rr = <R, R>; beta = active_old ? rz' / rz : 0; rz = rz'; rel, active as above
+// which = 2 (beta):    rz' = <R, Z>, rr = <R, R>; beta = active_old && pq > 0 ? rz' / rz : 0; rz = rz'; rel, active as above
 __global__ void pcg_scalar_kernel(lpgp_pcg p, int which, double rtol) {
   const int c = threadIdx.x;
   if (c >= p.m) return;
@@ -85,7 +85,7 @@ __global__ void pcg_scalar_kernel(lpgp_pcg p, int which, double rtol) {
     return;
   }
   const double rzn = pcg_sum(p.part() + (size_t)p.m * G, c, G), rrn = pcg_sum(p.part() + (size_t)2 * p.m * G, c, G);
-  if (which == 2) beta[c] = (act[c] != 0.0 && rz[c] != 0.0) ? rzn / rz[c] : 0.0;
+  if (which == 2) beta[c] = (act[c] != 0.0 && pq[c] > 0.0 && rz[c] != 0.0) ? rzn / rz[c] : 0.0;   // (no step taken: P restarts from Z, as in `pcg`)
   rz[c] = rzn;
   rr[c] = rrn;
   rel[c] = sqrt(rrn) / bn[c];
@@ -316,7 +316,7 @@ static int pcg_dots_rz_rr(lpgp_pcg* p, const lpgp_dvec* R, const lpgp_dvec* Z) {
 int lpgp_pcg_start(lpgp_ctx* ctx, lpgp_pcg* p, const lpgp_dvec* R, lpgp_dvec* Z, lpgp_dvec* P, const double* bnorm_host, double rtol, double* rel_host) {
   LPGP_CHECK(ctx && p && R && Z && P && bnorm_host && rel_host, "lpgp_pcg_start: null argument");
   LPGP_DEVICE(ctx);
-  LPGP_CHECK(R->n == p->n && R->m == p->m && Z->ld == R->ld && P->ld == R->ld && Z->m == R->m && P->m == R->m, "lpgp_pcg_start: shape mismatch");
+  LPGP_CHECK(R->n == p->n && R->m == p->m && Z->n == R->n && P->n == R->n && Z->m == R->m && P->m == R->m, "lpgp_pcg_start: shape mismatch");
   hipStream_t st = ctx->s_main;
   LPGP_HIP(hipMemcpyAsync(p->scal(5), bnorm_host, (size_t)p->m * sizeof(double), hipMemcpyHostToDevice, st));
   LPGP_HIP(hipStreamSynchronize(st));
