@@ -125,8 +125,19 @@ class GramProduct:
         return r
 
 
+DELTA_FLOOR = 1e-8            # smallest `delta / max diag G`: what the float64 Woodbury form can carry (see the class)
+
+
 class PivotedCholeskyPreconditioner:
-    """`M = L^T L + delta I`, `L` (r x n) from r greedy pivots of G; `M^{-1}` by Woodbury."""
+    """`M = L^T L + delta I`, `L` (r x n) from r greedy pivots of G; `M^{-1}` by Woodbury.
+
+    Pivoting stops after `rank` rows, after n, or when the largest remaining diagonal entry is at most `rtol * d0`, d0 = max diag G.
+    `delta = max(mean(d), DELTA_FLOOR * d0)`, d the diagonal the pivots leave unexplained (pivot entries and entries explained
+    beyond what is there count as 0).  The floor matters when the factorisation is complete (n <= rank) and d is all rounding:
+    `(R - L^T S^-1 L R) / delta` cancels log10(lambda_max(L^T L) / delta) digits, so at delta = 1e-12 d0 the operator applied was
+    not M^-1 any more (||M M^-1 R - R|| / ||R|| of 1e-2 to 3e-1) and the device form did not converge.  With 1e-8 d0 = sqrt(u) d0
+    the applied operator is M^-1 to 1e-5 and full-rank solves take the two or three iterations of the exact M^-1 (MEASUREMENTS.md,
+    "Matrix-free solves against a dense reference": 1e-10 d0 still trails it, 1e-6 d0 and above cost iterations at noise 1e-6)."""
 
     def __init__(self, G: GramProduct, rank: int, rtol: float = 1e-6):
         n = G.n
@@ -147,7 +158,7 @@ class PivotedCholeskyPreconditioner:
             k += 1
         self.L = L[:k]
         self.rank = k
-        self.delta = max(float(np.mean(d)), 1e-12 * d0)
+        self.delta = max(float(np.mean(d)), DELTA_FLOOR * d0)
         if self.rank:
             S = self.delta * np.eye(self.rank) + self.L @ self.L.T
             self._chol = np.linalg.cholesky(S)

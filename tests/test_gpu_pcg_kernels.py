@@ -317,8 +317,7 @@ def test_refusals(ctx):
 def test_more_than_256_columns_take_the_host_loop(ctx):
     """`gram.solve` with 257 right-hand sides at n = 200: beyond the scalar kernel's workgroup the solve runs the host loop
     (no "device_resident" in `last_solve_info`) and agrees with the dense solve to the posterior bar; 256 columns, the most the
-    device-resident loop takes, do the same on the device.  (Preconditioner of rank 100: at rank >= n the pivoted Cholesky is
-    complete, delta sits at its floor 1e-12 and the device-resident loop does not converge -- MEASUREMENTS.md.)"""
+    device-resident loop takes, do the same on the device."""
     import linpde_gp_amd as lp
     from conftest import POSTERIOR_RTOL
     cf = lp.randprocs.covfuncs
@@ -328,9 +327,8 @@ def test_more_than_256_columns_take_the_host_loop(ctx):
     k = cf.TensorProduct(cf.Matern((), nu=2.5, lengthscales=0.5), cf.Matern((), nu=2.5, lengthscales=0.6))
     prior = lp.GaussianProcess(lp.functions.Zero((2,)), k)
     Bm = rng.standard_normal((n, 257))
-    saved = (lp.config.matrix_free, lp.config.matrix_free_rtol, lp.config.matrix_free_device_iteration, lp.config.matrix_free_preconditioner_rank)
+    saved = (lp.config.matrix_free, lp.config.matrix_free_rtol, lp.config.matrix_free_device_iteration)
     lp.config.matrix_free, lp.config.matrix_free_rtol, lp.config.matrix_free_device_iteration = True, 1e-13, True
-    lp.config.matrix_free_preconditioner_rank = 100          # (below n: a pivoted Cholesky of full rank leaves delta at its floor)
     try:
         u = prior.condition_on_observations(Y, Xo, b=lp.randvars.Normal(np.zeros(n), np.full(n, 1e-2)))
         S256 = u.gram.solve(Bm[:, :256])
@@ -338,7 +336,7 @@ def test_more_than_256_columns_take_the_host_loop(ctx):
         S = u.gram.solve(Bm)
         info = u.last_solve_info
     finally:
-        lp.config.matrix_free, lp.config.matrix_free_rtol, lp.config.matrix_free_device_iteration, lp.config.matrix_free_preconditioner_rank = saved
+        lp.config.matrix_free, lp.config.matrix_free_rtol, lp.config.matrix_free_device_iteration = saved
     assert "device_resident" not in info and info["converged"]
     want = np.linalg.solve(k.matrix(Xo, Xo) + 1e-2 * np.eye(n), Bm)
     assert np.max(np.abs(S - want)) <= POSTERIOR_RTOL * np.max(np.abs(want))
