@@ -919,17 +919,24 @@ int lpgp_mat_clone(lpgp_ctx* ctx, const lpgp_mat* src, int32_t nblocks, lpgp_mat
 int64_t lpgp_mat_size(const lpgp_mat* mat) { return mat ? mat->n : -1; }
 int64_t lpgp_mat_padded_size(const lpgp_mat* mat) { return mat ? mat->pn : -1; }
 
+// What the lpgp_gram_assemble* entry points ask of their target: block (bi, bj) of the lower triangle, not factored yet, and the
+// second point set (`second`: X1 / F1) NULL exactly on the diagonal.
+static int gram_target(const char* fn, const lpgp_mat* mat, int32_t bi, int32_t bj, const void* second, const char* second_name) {
+  LPGP_CHECK(bi >= 0 && bi < (int)mat->blocks.size() && bj >= 0 && bj <= bi, "%s: bad block (%d,%d)", fn, bi, bj);
+  LPGP_CHECK(mat->blocks[bi].poff >= mat->pn_fact, "%s: block %d is already factored", fn, bi);
+  LPGP_CHECK((second == nullptr) == (bi == bj), "%s: %s must be NULL exactly for diagonal blocks", fn, second_name);
+  return 0;
+}
+
 int lpgp_gram_assemble(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, const lpgp_pts* X0,
                        const lpgp_pts* X1, lpgp_mat* mat, int32_t bi, int32_t bj) {
   LPGP_CHECK(ctx && kd && X0 && mat, "lpgp_gram_assemble: null argument");
   LPGP_DEVICE(ctx);
-  LPGP_CHECK(bi >= 0 && bi < (int)mat->blocks.size() && bj >= 0 && bj <= bi, "lpgp_gram_assemble: bad block (%d,%d)", bi, bj);
+  LPGP_TRY(gram_target("lpgp_gram_assemble", mat, bi, bj, X1, "X1"));
   const lpgp_block& Bi = mat->blocks[bi];
   const lpgp_block& Bj = mat->blocks[bj];
-  LPGP_CHECK(Bi.poff >= mat->pn_fact, "lpgp_gram_assemble: block %d is already factored", bi);
   LPGP_CHECK(X0->n == Bi.n, "lpgp_gram_assemble: X0 has %lld points, block %d has %lld rows", (long long)X0->n, bi, (long long)Bi.n);
-  const bool sym = (X1 == nullptr);
-  LPGP_CHECK(sym == (bi == bj), "lpgp_gram_assemble: X1 must be NULL exactly for diagonal blocks");
+  const bool sym = (bi == bj);
   const lpgp_pts* Xc = sym ? X0 : X1;
   LPGP_CHECK(Xc->n == Bj.n && Xc->d == X0->d && kd[0].d == X0->d, "lpgp_gram_assemble: shape mismatch");
   DevDesc desc;
@@ -953,12 +960,10 @@ int lpgp_gram_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_t 
   LPGP_CHECK(!ctx->distributed(), "%s: single GPU only (this context has joined a multi-GPU job)", fn);
   LPGP_MAT_ALIVE(mat, "lpgp_gram_assemble_weighted");
   LPGP_CHECK(mat->hidden.empty(), "%s: a strict prefix of the blocks is in view (lpgp_mat_set_view)", fn);
-  LPGP_CHECK(bi >= 0 && bi < (int)mat->blocks.size() && bj >= 0 && bj <= bi, "%s: bad block (%d,%d)", fn, bi, bj);
+  LPGP_TRY(gram_target(fn, mat, bi, bj, X1, "X1"));
   const lpgp_block& Bi = mat->blocks[bi];
   const lpgp_block& Bj = mat->blocks[bj];
-  LPGP_CHECK(Bi.poff >= mat->pn_fact, "%s: block %d is already factored", fn, bi);
   const bool sym = (bi == bj);
-  LPGP_CHECK(sym == (X1 == nullptr), "%s: X1 must be NULL exactly for diagonal blocks", fn);
   LPGP_CHECK(w0_host != nullptr, "%s: null row weights", fn);
   LPGP_CHECK(sym ? w1_host == nullptr : w1_host != nullptr, "%s: the column weights must be NULL exactly for diagonal blocks", fn);
   LPGP_TRY_RC(check_wpairs(pairs, npairs, A0, A1, sym ? WP_SYM : WP_RECT, fn));
@@ -975,12 +980,10 @@ int lpgp_gram_assemble_grid(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups
   LPGP_CHECK(ctx && kd && F0 && mat, "lpgp_gram_assemble_grid: null argument");
   LPGP_DEVICE(ctx);
   LPGP_CHECK(ngroups >= 1 && ngroups <= LPGP_MAXG, "lpgp_gram_assemble_grid: bad ngroups %d", ngroups);
-  LPGP_CHECK(bi >= 0 && bi < (int)mat->blocks.size() && bj >= 0 && bj <= bi, "lpgp_gram_assemble_grid: bad block (%d,%d)", bi, bj);
+  LPGP_TRY(gram_target("lpgp_gram_assemble_grid", mat, bi, bj, F1, "F1"));
   const lpgp_block& Bi = mat->blocks[bi];
   const lpgp_block& Bj = mat->blocks[bj];
-  LPGP_CHECK(Bi.poff >= mat->pn_fact, "lpgp_gram_assemble_grid: block %d is already factored", bi);
-  const bool sym = (F1 == nullptr);
-  LPGP_CHECK(sym == (bi == bj), "lpgp_gram_assemble_grid: F1 must be NULL exactly for diagonal blocks");
+  const bool sym = (bi == bj);
   const int D = kd[0].d;
   LPGP_CHECK(D >= 1 && D <= LPGP_MAXD, "lpgp_gram_assemble_grid: d=%d", D);
   LPGP_CHECK(kron_fits(kd, ngroups), "lpgp_gram_assemble_grid: the Kronecker path does not hold this sum (lpgp_kron_fits tells beforehand)");
@@ -1160,6 +1163,60 @@ int lpgp_potrf_enqueue(lpgp_ctx* ctx, lpgp_mat* mat) {
   return 0;
 }
 
+// Consecutive entries of a block row that share a descriptor (value observations against value observations: the whole row incl.
+// the diagonal block; the cross blocks of a differential block against the boundary blocks; the rows of a cross-covariance) go
+// into as few launches as the job table allows (assemble.hip: launch_assemble_batch).  Owns the descriptor and the jobs of the
+// pending run; add() launches it first when the descriptor changes, flush() launches what is pending.
+struct LPGP_LOCAL AsmRun {
+  lpgp_ctx* ctx;
+  double* out;                     // where the blocks go: column-major with leading dimension ld, laid out by lay
+  int64_t ld;
+  Layout2D lay;
+  std::vector<char>* assembled = nullptr;      // rows of a cross-covariance: entry `block` is set once that block's launch is issued
+  DevDesc desc;
+  std::vector<AsmJob> jobs;
+  std::vector<int> blocks;
+  int add(const DevDesc& d, const AsmJob& job, int block = -1) {
+    if (!jobs.empty() && !assemble_same_fast(desc, d)) LPGP_TRY(flush());
+    if (jobs.empty()) desc = d;
+    jobs.push_back(job);
+    blocks.push_back(block);
+    return 0;
+  }
+  int flush() {
+    if (jobs.empty()) return 0;
+    const int rc = launch_assemble_batch(ctx, ctx->s_main, desc, jobs.data(), (int)jobs.size(), out, ld, lay);
+    if (rc == 0 && assembled)
+      for (int b : blocks)
+        if (b >= 0 && b < (int)assembled->size()) (*assembled)[(size_t)b] = 1;
+    jobs.clear();
+    blocks.clear();
+    return rc;
+  }
+};
+
+// The block a conditioning has declared is dropped again on every way out but the good one; the error text of the step that
+// failed stays (lpgp_mat_pop_block succeeds and would not touch it, but be explicit).
+struct LPGP_LOCAL PopBlock {
+  lpgp_ctx* ctx;
+  lpgp_mat* mat;
+  bool armed = true;
+  ~PopBlock() {
+    if (!armed) return;
+    const std::string msg = lpgp::last_error();
+    (void)lpgp_mat_pop_block(ctx, mat);
+    set_error("%s", msg.c_str());
+  }
+};
+
+// identity tail of block B and its noise (dn entries: dv[i] + dscalar) in ONE launch behind the assembly (launch_finish_block)
+static int finish_block(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_block& B, int64_t dn, const double* dv, double dscalar) {
+  launch_finish_block(ctx->s_main, mat->a, mat->lr_cap, B.poff + B.n, B.pn - B.n, mat->cap, mat_layout(ctx), B.poff, dn, dv, dscalar);
+  const hipError_t e = hipGetLastError();
+  LPGP_CHECK(e == hipSuccess, "lpgp_mat_condition: %s", hipGetErrorString(e));
+  return 0;
+}
+
 int lpgp_mat_condition(lpgp_ctx* ctx, lpgp_mat* mat, int64_t n, const lpgp_pts* X_new, const lpgp_cond_block* row, int32_t nrow,
                        double noise_scalar, const double* noise_diag, const double* noise_dense, int32_t lazy, int32_t* info) {
   LPGP_CHECK(ctx && mat && row && n > 0, "lpgp_mat_condition: bad argument");
@@ -1179,105 +1236,51 @@ int lpgp_mat_condition(lpgp_ctx* ctx, lpgp_mat* mat, int64_t n, const lpgp_pts* 
   const bool fused_finish = ctx->asm_batch && !noise_dense;
   const int bi = mat_add_block_impl(ctx, mat, n, !fused_finish);
   if (bi < 0) return bi;
-  int rc = 0;
-  if (ctx->asm_batch && !ctx->distributed()) {
-    // the block row with as few launches as it has DIFFERENT descriptors: consecutive entries of the per-entry path that
-    // share one (value observations against value observations: the whole row incl. the diagonal block; the cross blocks
-    // of a differential block against the boundary blocks) go into one launch (assemble.hip: launch_assemble_batch)
-    const lpgp_block Bi = mat->blocks[bi];
-    std::vector<DevDesc> descs((size_t)nrow);
-    std::vector<AsmJob> jobs;
-    int run_start = -1;
-    auto flush = [&](int upto) -> int {
-      if (run_start < 0 || jobs.empty()) { run_start = -1; jobs.clear(); return 0; }
-      int r = launch_assemble_batch(ctx, ctx->s_main, descs[(size_t)run_start], jobs.data(), (int)jobs.size(), mat->a, mat->lr_cap, mat_layout(ctx));
-      (void)upto;
-      run_start = -1;
-      jobs.clear();
-      return r;
-    };
-    for (int j = 0; j < nrow && rc == 0; ++j) {
-      const lpgp_cond_block& e = row[j];
-      if (e.F0) {
-        rc = flush(j);
-        if (rc == 0) rc = lpgp_gram_assemble_grid(ctx, e.kd, e.ngroups, e.F0, j == bi ? nullptr : e.F1, mat, bi, j);
-        continue;
-      }
-      const lpgp_pts* Xc = (j == bi) ? X_new : e.X1;
-      const lpgp_block& Bj = mat->blocks[j];
-      // (no early return in here: a failure must reach the roll-back of the new block below)
-      if (!(X_new && Xc && e.kd)) {
-        set_error("lpgp_mat_condition: null point set or descriptor in row entry %d", j);
-        rc = -1;
-        break;
-      }
-      if (!(X_new->n == Bi.n && Xc->n == Bj.n && Xc->d == X_new->d && e.kd[0].d == X_new->d)) {
-        set_error("lpgp_mat_condition: shape mismatch in row entry %d", j);
-        rc = -1;
-        break;
-      }
-      rc = lower_kdesc(e.kd, e.ngroups, &descs[(size_t)j]);
-      if (rc != 0) break;
-      if (run_start >= 0 && !assemble_same_fast(descs[(size_t)run_start], descs[(size_t)j])) rc = flush(j);
-      if (rc != 0) break;
-      if (run_start < 0) run_start = j;
-      jobs.push_back(AsmJob{X_new->x, X_new->n, X_new->n_pad, Xc->x, Xc->n, Xc->n_pad, Bi.poff, Bj.poff, j == bi ? 1 : 0});
-    }
-    if (rc == 0) rc = flush(nrow);
-  } else
-  for (int j = 0; j < nrow && rc == 0; ++j) {
+  PopBlock undo{ctx, mat};
+  const lpgp_block B = mat->blocks[bi];
+  // the block row with as few launches as it has DIFFERENT descriptors; without `asm_batch`, or in a multi-GPU job, entry by entry
+  const bool batch = ctx->asm_batch && !ctx->distributed();
+  AsmRun run{ctx, mat->a, mat->lr_cap, mat_layout(ctx)};
+  DevDesc desc;
+  for (int j = 0; j < nrow; ++j) {
     const lpgp_cond_block& e = row[j];
-    if (e.F0)
-      rc = lpgp_gram_assemble_grid(ctx, e.kd, e.ngroups, e.F0, j == bi ? nullptr : e.F1, mat, bi, j);
-    else
-      rc = lpgp_gram_assemble(ctx, e.kd, e.ngroups, X_new, j == bi ? nullptr : e.X1, mat, bi, j);
-  }
-  if (rc == 0 && noise_scalar != 0.0 && !fused_finish) rc = lpgp_mat_add_diag(ctx, mat, bi, nullptr, noise_scalar);
-  if (rc == 0 && noise_dense) rc = lpgp_mat_add_dense(ctx, mat, bi, noise_dense);
-  if (rc == 0 && fused_finish && !noise_diag) {
-    const lpgp_block& B = mat->blocks[bi];
-    launch_finish_block(ctx->s_main, mat->a, mat->lr_cap, B.poff + B.n, B.pn - B.n, mat->cap, mat_layout(ctx), B.poff, noise_scalar != 0.0 ? B.n : 0,
-                        nullptr, noise_scalar);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("lpgp_mat_condition: %s", hipGetErrorString(e));
-      rc = -1;
+    if (e.F0) {
+      LPGP_TRY(run.flush());
+      LPGP_TRY(lpgp_gram_assemble_grid(ctx, e.kd, e.ngroups, e.F0, j == bi ? nullptr : e.F1, mat, bi, j));
+      continue;
     }
+    const lpgp_pts* Xc = (j == bi) ? X_new : e.X1;
+    const lpgp_block& Bj = mat->blocks[j];
+    LPGP_CHECK(X_new && Xc && e.kd, "lpgp_mat_condition: null point set or descriptor in row entry %d", j);
+    LPGP_CHECK(X_new->n == B.n && Xc->n == Bj.n && Xc->d == X_new->d && e.kd[0].d == X_new->d, "lpgp_mat_condition: shape mismatch in row entry %d", j);
+    LPGP_TRY(lower_kdesc(e.kd, e.ngroups, &desc));
+    LPGP_TRY(run.add(desc, AsmJob{X_new->x, X_new->n, X_new->n_pad, Xc->x, Xc->n, Xc->n_pad, B.poff, Bj.poff, j == bi ? 1 : 0}));
+    if (!batch) LPGP_TRY(run.flush());
   }
-  if (rc == 0 && noise_diag) {
+  LPGP_TRY(run.flush());
+  if (noise_scalar != 0.0 && !fused_finish) LPGP_TRY(lpgp_mat_add_diag(ctx, mat, bi, nullptr, noise_scalar));
+  if (noise_dense) LPGP_TRY(lpgp_mat_add_dense(ctx, mat, bi, noise_dense));
+  if (fused_finish && !noise_diag) LPGP_TRY(finish_block(ctx, mat, B, noise_scalar != 0.0 ? B.n : 0, nullptr, noise_scalar));
+  if (noise_diag) {
     // the vector is staged into the block's own segment of the weights buffer (unused until the first solve, which is
     // stream-ordered behind the kernel below) through a stream that is idle during conditionings: nothing waits for the
     // panel stream, where an enqueued factorisation of the previous block may still be running
-    const lpgp_block& B = mat->blocks[bi];
     // (only while an enqueued factorisation is in flight -- `unchecked` -- is the side stream worth anything; otherwise the
     //  panel stream, which orders the upload behind whatever a caller of the C API left running on it: lpgp.h, "streams")
     hipStream_t sc = (mat->unchecked && ctx->s_upd_all && !ctx->single_stream && !ctx->distributed()) ? ctx->s_upd_all : ctx->s_main;
     hipError_t e = hipMemcpyAsync(mat->w + B.poff, noise_diag, (size_t)B.n * sizeof(double), hipMemcpyHostToDevice, sc);
     if (e == hipSuccess) e = hipStreamSynchronize(sc);
-    if (e != hipSuccess) {
-      set_error("lpgp_mat_condition: noise upload: %s", hipGetErrorString(e));
-      rc = -1;
-    } else if (fused_finish) {
-      launch_finish_block(ctx->s_main, mat->a, mat->lr_cap, B.poff + B.n, B.pn - B.n, mat->cap, mat_layout(ctx), B.poff, B.n, mat->w + B.poff, 0.0);
-      if ((e = hipGetLastError()) != hipSuccess) {
-        set_error("lpgp_mat_condition: %s", hipGetErrorString(e));
-        rc = -1;
-      }
-    } else {
-      rc = launch_add_diag(ctx->s_main, mat->a, mat->lr_cap, B.poff, B.n, mat->w + B.poff, 0.0, mat_layout(ctx));
-    }
+    LPGP_CHECK(e == hipSuccess, "lpgp_mat_condition: noise upload: %s", hipGetErrorString(e));
+    if (fused_finish) LPGP_TRY(finish_block(ctx, mat, B, B.n, mat->w + B.poff, 0.0));
+    else LPGP_TRY(launch_add_diag(ctx->s_main, mat->a, mat->lr_cap, B.poff, B.n, mat->w + B.poff, 0.0, mat_layout(ctx)));
   }
   int32_t h = 0;
   // lazy == 2: the block row is assembled and the factorisation is left to whoever needs the factor first -- the next
   // lpgp_mat_condition / lpgp_potrf / lpgp_potrf_enqueue, or lpgp_potrf_predict, which lets the prediction ride inside it
-  if (rc == 0 && lazy != 2) rc = lazy ? lpgp_potrf_enqueue(ctx, mat) : lpgp_potrf(ctx, mat, &h);
-  if (rc != 0 || h != 0) {
-    // keep the error text of the failing step: lpgp_mat_pop_block succeeds and would not touch it, but be explicit
-    const std::string msg = lpgp::last_error();
-    if (lpgp_mat_pop_block(ctx, mat) != 0 || rc != 0) set_error("%s", msg.c_str());
-  }
+  if (lazy != 2) LPGP_TRY(lazy ? lpgp_potrf_enqueue(ctx, mat) : lpgp_potrf(ctx, mat, &h));
   if (info) *info = h;
-  return rc;
+  undo.armed = (h != 0);           // (a factorisation that found the matrix not positive definite: status reported, block dropped)
+  return 0;
 }
 
 int lpgp_mat_check(lpgp_ctx* ctx, lpgp_mat* mat, int32_t* info, int32_t* block) {
@@ -1533,15 +1536,23 @@ int lpgp_rhs_destroy(lpgp_rhs* r) {
   return 0;
 }
 
+// What the lpgp_cross_assemble* entry points ask of their target: the handles there (tested before any is read), blocks
+// [bi, bi + nb) of the matrix, and a right-hand side made for this matrix and these test points.
+static int cross_target(const char* fn, const lpgp_pts* X_test, const lpgp_rhs* rhs, const lpgp_mat* mat, int32_t bi, int32_t nb) {
+  LPGP_CHECK(X_test && rhs && mat, "%s: null argument", fn);
+  LPGP_CHECK(bi >= 0 && nb >= 0 && bi + nb <= (int)mat->blocks.size(), "%s: bad block %d", fn, bi);
+  LPGP_CHECK(rhs->ld == mat->pn, "%s: rhs was created for a different matrix size", fn);
+  LPGP_CHECK(X_test->n == rhs->m, "%s: shape mismatch: X_test has %lld points, rhs has %lld columns", fn, (long long)X_test->n, (long long)rhs->m);
+  return 0;
+}
+
 int lpgp_cross_assemble(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, const lpgp_pts* X_obs,
                         const lpgp_pts* X_test, lpgp_rhs* rhs, const lpgp_mat* mat, int32_t bi) {
-  LPGP_CHECK(ctx && kd && X_obs && X_test && rhs && mat, "lpgp_cross_assemble: null argument");
+  LPGP_CHECK(ctx && kd && X_obs, "lpgp_cross_assemble: null argument");
   LPGP_DEVICE(ctx);
-  LPGP_CHECK(bi >= 0 && bi < (int)mat->blocks.size(), "lpgp_cross_assemble: bad block %d", bi);
+  LPGP_TRY(cross_target("lpgp_cross_assemble", X_test, rhs, mat, bi, 1));
   const lpgp_block& B = mat->blocks[bi];
-  LPGP_CHECK(X_obs->n == B.n && X_test->n == rhs->m && X_obs->d == X_test->d && kd[0].d == X_obs->d,
-             "lpgp_cross_assemble: shape mismatch");
-  LPGP_CHECK(rhs->ld == mat->pn, "lpgp_cross_assemble: rhs was created for a different matrix size");
+  LPGP_CHECK(X_obs->n == B.n && X_obs->d == X_test->d && kd[0].d == X_obs->d, "lpgp_cross_assemble: shape mismatch");
   DevDesc desc;
   int rc = lower_kdesc(kd, ngroups, &desc);
   if (rc != 0) return rc;
@@ -1554,15 +1565,14 @@ int lpgp_cross_assemble(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, co
 int lpgp_cross_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_t npairs, const double* w_host, int32_t A,
                                  const lpgp_pts* X_obs, const lpgp_pts* X_test, lpgp_rhs* rhs, const lpgp_mat* mat, int32_t bi) {
   static const char* fn = "lpgp_cross_assemble_weighted";
-  LPGP_CHECK(ctx && X_obs && X_test && rhs && mat, "%s: null argument", fn);
+  LPGP_CHECK(ctx && X_obs, "%s: null argument", fn);
   LPGP_DEVICE(ctx);
   LPGP_CHECK(!ctx->distributed(), "%s: single GPU only (this context has joined a multi-GPU job)", fn);
-  LPGP_CHECK(bi >= 0 && bi < (int)mat->blocks.size(), "%s: bad block %d", fn, bi);
+  LPGP_TRY(cross_target(fn, X_test, rhs, mat, bi, 1));
   const lpgp_block& B = mat->blocks[bi];
   LPGP_CHECK(w_host != nullptr, "%s: null weights", fn);
   LPGP_TRY_RC(check_wpairs(pairs, npairs, A, 1, WP_CROSS, fn));
-  LPGP_CHECK(X_obs->n == B.n && X_test->n == rhs->m && X_obs->d == X_test->d && pairs[0].kd[0].d == X_obs->d, "%s: shape mismatch", fn);
-  LPGP_CHECK(rhs->ld == mat->pn, "%s: rhs was created for a different matrix size", fn);
+  LPGP_CHECK(X_obs->n == B.n && X_obs->d == X_test->d && pairs[0].kd[0].d == X_obs->d, "%s: shape mismatch", fn);
   int rc = 0;
   if (X_test->n > 0 && X_obs->n > 0) {
     const std::vector<double> ones((size_t)X_test->n, 1.0);
@@ -1574,36 +1584,21 @@ int lpgp_cross_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_t
 
 int lpgp_cross_assemble_row(lpgp_ctx* ctx, const lpgp_cross_block* blocks, int32_t nblocks, const lpgp_pts* X_test, lpgp_rhs* rhs,
                             const lpgp_mat* mat) {
-  LPGP_CHECK(ctx && blocks && X_test && rhs && mat, "lpgp_cross_assemble_row: null argument");
+  LPGP_CHECK(ctx && blocks, "lpgp_cross_assemble_row: null argument");
   LPGP_DEVICE(ctx);
+  LPGP_TRY(cross_target("lpgp_cross_assemble_row", X_test, rhs, mat, 0, nblocks));
   LPGP_CHECK(nblocks == (int32_t)mat->blocks.size(), "lpgp_cross_assemble_row: %d entries for %d blocks", nblocks, (int)mat->blocks.size());
-  LPGP_CHECK(rhs->ld == mat->pn && X_test->n == rhs->m, "lpgp_cross_assemble_row: rhs was created for a different matrix size or point count");
-  std::vector<DevDesc> descs((size_t)nblocks);
-  std::vector<AsmJob> jobs;
-  int run_start = -1, rc = 0;
-  auto flush = [&]() -> int {
-    int r = 0;
-    if (run_start >= 0 && !jobs.empty())
-      r = launch_assemble_batch(ctx, ctx->s_main, descs[(size_t)run_start], jobs.data(), (int)jobs.size(), rhs->v, rhs->ld, Layout2D());
-    run_start = -1;
-    jobs.clear();
-    return r;
-  };
-  for (int bi = 0; bi < nblocks && rc == 0; ++bi) {
+  AsmRun run{ctx, rhs->v, rhs->ld, Layout2D(), &rhs->assembled};
+  DevDesc desc;
+  for (int bi = 0; bi < nblocks; ++bi) {
     const lpgp_cross_block& e = blocks[bi];
     const lpgp_block& B = mat->blocks[(size_t)bi];
     if (!e.kd || !e.X_obs) continue;                       // a block without cross-covariance: its rows stay zero (rhs_clear_unassembled)
     LPGP_CHECK(e.X_obs->n == B.n && e.X_obs->d == X_test->d && e.kd[0].d == X_test->d, "lpgp_cross_assemble_row: shape mismatch in block %d", bi);
-    rc = lower_kdesc(e.kd, e.ngroups, &descs[(size_t)bi]);
-    if (rc != 0) break;
-    if (run_start >= 0 && !assemble_same_fast(descs[(size_t)run_start], descs[(size_t)bi])) rc = flush();
-    if (rc != 0) break;
-    if (run_start < 0) run_start = bi;
-    jobs.push_back(AsmJob{e.X_obs->x, e.X_obs->n, e.X_obs->n_pad, X_test->x, X_test->n, X_test->n_pad, B.poff, 0, 0});
-    if (bi < (int)rhs->assembled.size()) rhs->assembled[(size_t)bi] = 1;
+    LPGP_TRY(lower_kdesc(e.kd, e.ngroups, &desc));
+    LPGP_TRY(run.add(desc, AsmJob{e.X_obs->x, e.X_obs->n, e.X_obs->n_pad, X_test->x, X_test->n, X_test->n_pad, B.poff, 0, 0}, bi));
   }
-  if (rc == 0) rc = flush();
-  return rc;       // asynchronous (see lpgp_gram_assemble)
+  return run.flush();       // asynchronous (see lpgp_gram_assemble)
 }
 
 int lpgp_trsm_lower(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_rhs* V) {

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 
 #include "lpgp_internal.h"
 #include "eval_entries.h"
@@ -530,46 +531,45 @@ static int fast_mode(const FastDesc& fd, int d) {
     if (fd.parity[c] & mask) return 1;
   return 2;
 }
-static thread_local const AsmBatch* g_asm_batch = nullptr;      // the job table of the assembly launch being dispatched (launch_fast below)
-template <int KIND, int D, int N0, int N1, int MODE, class Args>
-static void launch_fast_mode(dim3 grid, hipStream_t stream, const FastDesc& fd, const Args& a) {
+// `a`: the kernel's arguments behind the descriptor (the assembly: AsmArgs and the job table; the product: MvArgs)
+template <int KIND, int D, int N0, int N1, int MODE, class... Args>
+static void launch_fast_mode(dim3 grid, hipStream_t stream, const FastDesc& fd, const Args&... a) {
   if constexpr (KIND == 0) {
-    static const AsmBatch none{};
-    hipLaunchKernelGGL((assemble_fast_kernel<D, N0, N1, MODE>), grid, dim3(256), 0, stream, fd, a, g_asm_batch ? *g_asm_batch : none);
+    hipLaunchKernelGGL((assemble_fast_kernel<D, N0, N1, MODE>), grid, dim3(256), 0, stream, fd, a...);
   } else {
-    hipLaunchKernelGGL((matvec_fast_kernel<D, N0, N1, MODE>), grid, dim3(256), 0, stream, fd, a);
+    hipLaunchKernelGGL((matvec_fast_kernel<D, N0, N1, MODE>), grid, dim3(256), 0, stream, fd, a...);
   }
 }
-template <int KIND, int D, int N0, int N1, class Args>
-static void launch_fast_one(dim3 grid, hipStream_t stream, const FastDesc& fd, const Args& a) {
+template <int KIND, int D, int N0, int N1, class... Args>
+static void launch_fast_one(dim3 grid, hipStream_t stream, const FastDesc& fd, const Args&... a) {
   switch (fast_mode(fd, D)) {
-    case 2: launch_fast_mode<KIND, D, N0, N1, 2>(grid, stream, fd, a); break;
-    case 1: launch_fast_mode<KIND, D, N0, N1, 1>(grid, stream, fd, a); break;
-    default: launch_fast_mode<KIND, D, N0, N1, 0>(grid, stream, fd, a); break;
+    case 2: launch_fast_mode<KIND, D, N0, N1, 2>(grid, stream, fd, a...); break;
+    case 1: launch_fast_mode<KIND, D, N0, N1, 1>(grid, stream, fd, a...); break;
+    default: launch_fast_mode<KIND, D, N0, N1, 0>(grid, stream, fd, a...); break;
   }
 }
-template <int KIND, int D, int N0, class Args>
-static void launch_fast_n0(int n1, dim3 grid, hipStream_t stream, const FastDesc& fd, const Args& a) {
+template <int KIND, int D, int N0, class... Args>
+static void launch_fast_n0(int n1, dim3 grid, hipStream_t stream, const FastDesc& fd, const Args&... a) {
   if constexpr (D == 1) {
-    launch_fast_one<KIND, 1, N0, 1>(grid, stream, fd, a);
+    launch_fast_one<KIND, 1, N0, 1>(grid, stream, fd, a...);
   } else {
     switch (n1) {
-      case 1: launch_fast_one<KIND, D, N0, 1>(grid, stream, fd, a); break;
-      case 2: launch_fast_one<KIND, D, N0, 2>(grid, stream, fd, a); break;
-      case 3: launch_fast_one<KIND, D, N0, 3>(grid, stream, fd, a); break;
-      case 4: launch_fast_one<KIND, D, N0, 4>(grid, stream, fd, a); break;
-      default: launch_fast_one<KIND, D, N0, 5>(grid, stream, fd, a); break;
+      case 1: launch_fast_one<KIND, D, N0, 1>(grid, stream, fd, a...); break;
+      case 2: launch_fast_one<KIND, D, N0, 2>(grid, stream, fd, a...); break;
+      case 3: launch_fast_one<KIND, D, N0, 3>(grid, stream, fd, a...); break;
+      case 4: launch_fast_one<KIND, D, N0, 4>(grid, stream, fd, a...); break;
+      default: launch_fast_one<KIND, D, N0, 5>(grid, stream, fd, a...); break;
     }
   }
 }
-template <int KIND, int D, class Args>
-static void launch_fast(int n0, int n1, dim3 grid, hipStream_t stream, const FastDesc& fd, const Args& a) {
+template <int KIND, int D, class... Args>
+static void launch_fast(int n0, int n1, dim3 grid, hipStream_t stream, const FastDesc& fd, const Args&... a) {
   switch (n0) {
-    case 1: launch_fast_n0<KIND, D, 1>(n1, grid, stream, fd, a); break;
-    case 2: launch_fast_n0<KIND, D, 2>(n1, grid, stream, fd, a); break;
-    case 3: launch_fast_n0<KIND, D, 3>(n1, grid, stream, fd, a); break;
-    case 4: launch_fast_n0<KIND, D, 4>(n1, grid, stream, fd, a); break;
-    default: launch_fast_n0<KIND, D, 5>(n1, grid, stream, fd, a); break;
+    case 1: launch_fast_n0<KIND, D, 1>(n1, grid, stream, fd, a...); break;
+    case 2: launch_fast_n0<KIND, D, 2>(n1, grid, stream, fd, a...); break;
+    case 3: launch_fast_n0<KIND, D, 3>(n1, grid, stream, fd, a...); break;
+    case 4: launch_fast_n0<KIND, D, 4>(n1, grid, stream, fd, a...); break;
+    default: launch_fast_n0<KIND, D, 5>(n1, grid, stream, fd, a...); break;
   }
 }
 
@@ -594,16 +594,139 @@ static size_t desc_used_bytes(const DevDesc& host_desc) {
   return offsetof(DevDesc, coef) + (size_t)desc_coef_used(host_desc) * sizeof(double);
 }
 
-// Copy a lowered descriptor into the next slot of the context's ring (pinned host -> device,
-// asynchronous); the caller records slot.done behind the kernel that reads it.
-static int stage_desc(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, lpgp_ctx::DescSlot** out) {
+// A generic kernel and the descriptor it reads: the lowered descriptor is copied into the next slot of the context's ring (pinned
+// host -> device, asynchronous), `launch(device copy)` runs as one profiled interval, and the slot's event is recorded behind it.
+template <class Launch>
+static int launch_staged(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, int kernel, double flops, double bytes, Launch&& launch) {
   lpgp_ctx::DescSlot& slot = ctx->desc_ring[ctx->desc_next];
   ctx->desc_next = (ctx->desc_next + 1) % lpgp_ctx::DESC_RING;
   if (slot.used) LPGP_HIP(hipEventSynchronize(slot.done));
-  const size_t bytes = desc_used_bytes(host_desc);
-  std::memcpy(slot.h, &host_desc, bytes);
-  LPGP_HIP(hipMemcpyAsync(slot.d, slot.h, bytes, hipMemcpyHostToDevice, stream));
-  *out = &slot;
+  const size_t used = desc_used_bytes(host_desc);
+  std::memcpy(slot.h, &host_desc, used);
+  LPGP_HIP(hipMemcpyAsync(slot.d, slot.h, used, hipMemcpyHostToDevice, stream));
+  {
+    ProfScope prof(ctx, stream, kernel, flops, bytes);
+    launch(slot.d);
+  }
+  LPGP_HIP(hipGetLastError());
+  LPGP_HIP(hipEventRecord(slot.done, stream));
+  slot.used = true;
+  return 0;
+}
+
+// The one place where the run-time (d, factors, radial) of a launch become the template arguments <D, FACTORS, RADIAL> of the generic
+// kernels: f(D, FACTORS, RADIAL) with integral constants.  Radial takes no factors; the caller has refused a d outside dim_ok.
+static bool dim_ok(int d) { return d >= 1 && d <= 4; }
+template <class F>
+static void dispatch_dim(int d, bool factors, bool radial, F&& f) {
+  auto with = [&](auto D) {
+    if (radial) f(D, std::false_type{}, std::true_type{});
+    else if (factors) f(D, std::true_type{}, std::false_type{});
+    else f(D, std::false_type{}, std::false_type{});
+  };
+  switch (d) {
+    case 1: with(std::integral_constant<int, 1>{}); break;
+    case 2: with(std::integral_constant<int, 2>{}); break;
+    case 3: with(std::integral_constant<int, 3>{}); break;
+    default: with(std::integral_constant<int, 4>{}); break;
+  }
+}
+#define LPGP_CV(x) decltype(x)::value       // the value of an integral constant handed to a generic lambda
+
+// measurement aids (AsmArgs::flags, bits 1 and 2)
+static int asm_diag() {
+  static const int diag = [] { const char* e = std::getenv("LPGP_ASM_DIAG"); return e ? std::atoi(e) : 0; }();
+  return diag;
+}
+// AsmArgs::flags of a launch with this descriptor (bit 0 alone: MvArgs::factors)
+// (radial groups take no per-point factors: their exponent is not a sum over dimensions)
+static int asm_flags(const lpgp_ctx* ctx, const DevDesc& host_desc, bool radial) {
+  return ((ctx->asm_factors && host_desc.ngroups <= FACT_MAXG && !radial) ? 1 : 0) | ((asm_diag() & 3) << 1);
+}
+// the common shapes on the specialised kernels (descriptor by value: no staging, no slot), unless one of `flags` asks for what
+// only the generic kernels do
+static bool fast_path(const lpgp_ctx* ctx, const DevDesc& host_desc, int flags, FastDesc* fd, int* n0, int* n1) {
+  return ctx->asm_fast && flags == 0 && fast_shape(host_desc, fd, n0, n1);
+}
+
+// One block as the kernels take it; false: the block is empty (nothing to stage, nothing to write).
+static bool asm_args(const AsmJob& J, double* out, int64_t ld, const Layout2D& lay, AsmArgs* a) {
+  a->x0 = J.x0; a->x1 = J.x1; a->n0 = J.n0; a->n1 = J.n1; a->n0_pad = J.n0_pad; a->n1_pad = J.n1_pad;
+  a->out = out; a->ld = ld; a->row_off = J.row_off; a->col_off = J.col_off; a->lower_only = J.lower_only;
+  a->lay = lay;
+  a->tiles_r = (int)((J.n0 + AT - 1) / AT);
+  a->tiles_c = (int)((J.n1 + AT - 1) / AT);
+  return a->tiles_r != 0 && a->tiles_c != 0;
+}
+static double asm_entries(const AsmJob& J) {
+  return J.lower_only ? 0.5 * (double)J.n0 * ((double)J.n0 + 1.0) : (double)J.n0 * (double)J.n1;
+}
+
+// column tiles per workgroup of assemble_fast_kernel: as many as leave >= 16 workgroups per CU in the launch (at most ctx->asm_ct)
+// (rectangular blocks only: on a lower-triangle launch the groups that straddle the diagonal do one to four tiles and
+//  the launch loses its balance -- Gram block of 16 384 scattered points: 3.6 TB/s with four tiles per workgroup, 4.3 with
+//  one; scratch/assemble_lower.py)
+static int fast_ct(const lpgp_ctx* ctx, int tiles_r, int tiles_c, int lower_only) {
+  int ct = 1;
+  while (!lower_only && ct < ctx->asm_ct && (int64_t)tiles_r * ((tiles_c + 2 * ct - 1) / (2 * ct)) >= 16 * (int64_t)(ctx->cus > 0 ? ctx->cus : 256)) ct *= 2;
+  return ct;
+}
+
+// ONE launch of the specialised kernel for up to ASM_MAXJ blocks that share `fd`: a workgroup finds its block in the job table;
+// a launch with one block runs on the AsmArgs alone, which are the first block's.
+static int launch_fast_jobs(lpgp_ctx* ctx, hipStream_t stream, int d, const FastDesc& fd, int N0, int N1, const AsmJob* jobs, int njobs,
+                            double* out, int64_t ld, const Layout2D& lay) {
+  AsmBatch bt;
+  AsmArgs first;
+  double entries = 0.0;
+  int wgs = 0;
+  for (int j = 0; j < njobs; ++j) {
+    AsmArgs a;
+    if (!asm_args(jobs[j], out, ld, lay, &a)) continue;
+    a.ct = fast_ct(ctx, a.tiles_r, a.tiles_c, a.lower_only);
+    if (bt.njobs == 0) first = a;
+    bt.job[bt.njobs] = AsmJobDev{a.x0, a.x1, a.n0, a.n1, a.n0_pad, a.n1_pad, a.row_off, a.col_off, a.lower_only, a.tiles_r, a.tiles_c, a.ct};
+    bt.wg0[bt.njobs++] = wgs;
+    wgs += a.tiles_r * ((a.tiles_c + a.ct - 1) / a.ct);
+    entries += asm_entries(jobs[j]);
+  }
+  if (bt.njobs == 0) return 0;
+  bt.wg0[bt.njobs] = wgs;
+  {
+    ProfScope prof(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * entries);
+    if (d == 1) launch_fast<0, 1>(N0, N1, dim3((unsigned)wgs), stream, fd, first, bt);
+    else launch_fast<0, 2>(N0, N1, dim3((unsigned)wgs), stream, fd, first, bt);
+  }
+  LPGP_HIP(hipGetLastError());
+  return 0;
+}
+
+// Several blocks that share `host_desc` in as few launches as the job table allows (ASM_MAXJ per launch); without `asm_batch`, with a
+// measurement aid, or with a descriptor outside the specialised kernel's shapes (then through the generic kernel): one launch per block.
+int launch_assemble_batch(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, const AsmJob* jobs, int njobs, double* out, int64_t ld,
+                          const Layout2D& lay) {
+  const bool radial = desc_has_radial(host_desc);
+  const int flags = asm_flags(ctx, host_desc, radial);
+  FastDesc fd;
+  int N0 = 0, N1 = 0;
+  if (fast_path(ctx, host_desc, flags, &fd, &N0, &N1)) {
+    const int per = (ctx->asm_batch && asm_diag() == 0) ? ASM_MAXJ : 1;
+    for (int j0 = 0; j0 < njobs; j0 += per)
+      LPGP_TRY_RC(launch_fast_jobs(ctx, stream, host_desc.d, fd, N0, N1, jobs + j0, njobs - j0 < per ? njobs - j0 : per, out, ld, lay));
+    return 0;
+  }
+  for (int j = 0; j < njobs; ++j) {
+    AsmArgs a;
+    if (!asm_args(jobs[j], out, ld, lay, &a)) continue;
+    LPGP_CHECK(dim_ok(host_desc.d), "assemble: d=%d", host_desc.d);
+    a.flags = flags;
+    const dim3 grid((unsigned)((int64_t)a.tiles_r * a.tiles_c));
+    LPGP_TRY_RC(launch_staged(ctx, stream, host_desc, LPGP_K_ASSEMBLE, 0.0, 8.0 * asm_entries(jobs[j]), [&](const DevDesc* d_desc) {
+      dispatch_dim(host_desc.d, flags & 1, radial, [&](auto D, auto F, auto R) {
+        hipLaunchKernelGGL((assemble_kernel<LPGP_CV(D), LPGP_CV(F), LPGP_CV(R)>), grid, dim3(256), 0, stream, d_desc, a);
+      });
+    }));
+  }
   return 0;
 }
 
@@ -611,66 +734,8 @@ int launch_assemble(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc,
                     int64_t n0, int64_t n0_pad, const double* x1, int64_t n1, int64_t n1_pad,
                     double* out, int64_t ld, int64_t row_off, int64_t col_off, int lower_only,
                     const Layout2D& lay) {
-  AsmArgs a;
-  a.x0 = x0; a.x1 = x1; a.n0 = n0; a.n1 = n1; a.n0_pad = n0_pad; a.n1_pad = n1_pad;
-  a.out = out; a.ld = ld; a.row_off = row_off; a.col_off = col_off; a.lower_only = lower_only;
-  a.lay = lay;
-  a.tiles_r = (int)((n0 + AT - 1) / AT);
-  a.tiles_c = (int)((n1 + AT - 1) / AT);
-  if (a.tiles_r == 0 || a.tiles_c == 0) return 0;
-  static const int diag = [] { const char* e = std::getenv("LPGP_ASM_DIAG"); return e ? std::atoi(e) : 0; }();
-  const bool radial = desc_has_radial(host_desc);      // (radial groups take no per-point factors: their exponent is not a sum over dimensions)
-  a.flags = ((ctx->asm_factors && host_desc.ngroups <= FACT_MAXG && !radial) ? 1 : 0) | ((diag & 3) << 1);
-  dim3 grid((unsigned)((int64_t)a.tiles_r * a.tiles_c));
-  double entries = lower_only ? 0.5 * (double)n0 * ((double)n0 + 1.0) : (double)n0 * (double)n1;
-  {
-    // the common shapes on the specialised kernel (descriptor by value: no staging, no slot)
-    FastDesc fd;
-    int N0 = 0, N1 = 0;
-    if (ctx->asm_fast && a.flags == 0 && fast_shape(host_desc, &fd, &N0, &N1)) {
-      prof_begin(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * entries);
-      // column tiles per workgroup: as many as leave >= 16 workgroups per CU in the launch (at most ctx->asm_ct)
-      // (rectangular blocks only: on a lower-triangle launch the groups that straddle the diagonal do one to four tiles and
-      //  the launch loses its balance -- Gram block of 16 384 scattered points: 3.6 TB/s with four tiles per workgroup, 4.3 with
-      //  one; scratch/assemble_lower.py)
-      int ct = 1;
-      while (!lower_only && ct < ctx->asm_ct && (int64_t)a.tiles_r * ((a.tiles_c + 2 * ct - 1) / (2 * ct)) >= 16 * (int64_t)(ctx->cus > 0 ? ctx->cus : 256)) ct *= 2;
-      a.ct = ct;
-      grid = dim3((unsigned)((int64_t)a.tiles_r * ((a.tiles_c + ct - 1) / ct)));
-      if (host_desc.d == 1) launch_fast<0, 1>(N0, N1, grid, stream, fd, a);
-      else launch_fast<0, 2>(N0, N1, grid, stream, fd, a);
-      prof_end(ctx, stream);
-      LPGP_HIP(hipGetLastError());
-      return 0;
-    }
-  }
-  lpgp_ctx::DescSlot* slotp = nullptr;
-  int rc_ = stage_desc(ctx, stream, host_desc, &slotp);
-  if (rc_ != 0) return rc_;
-  lpgp_ctx::DescSlot& slot = *slotp;
-  const DevDesc* d_desc = slot.d;
-  prof_begin(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * entries);
-  if (radial) {
-    switch (host_desc.d) {
-      case 1: hipLaunchKernelGGL((assemble_kernel<1, false, true>), grid, dim3(256), 0, stream, d_desc, a); break;
-      case 2: hipLaunchKernelGGL((assemble_kernel<2, false, true>), grid, dim3(256), 0, stream, d_desc, a); break;
-      case 3: hipLaunchKernelGGL((assemble_kernel<3, false, true>), grid, dim3(256), 0, stream, d_desc, a); break;
-      case 4: hipLaunchKernelGGL((assemble_kernel<4, false, true>), grid, dim3(256), 0, stream, d_desc, a); break;
-      default: prof_end(ctx, stream); LPGP_CHECK(false, "assemble: d=%d", host_desc.d);
-    }
-  } else
-  switch (host_desc.d) {
-    case 1: if (a.flags & 1) hipLaunchKernelGGL((assemble_kernel<1, true>), grid, dim3(256), 0, stream, d_desc, a); else hipLaunchKernelGGL((assemble_kernel<1, false>), grid, dim3(256), 0, stream, d_desc, a); break;
-    case 2: if (a.flags & 1) hipLaunchKernelGGL((assemble_kernel<2, true>), grid, dim3(256), 0, stream, d_desc, a); else hipLaunchKernelGGL((assemble_kernel<2, false>), grid, dim3(256), 0, stream, d_desc, a); break;
-    case 3: if (a.flags & 1) hipLaunchKernelGGL((assemble_kernel<3, true>), grid, dim3(256), 0, stream, d_desc, a); else hipLaunchKernelGGL((assemble_kernel<3, false>), grid, dim3(256), 0, stream, d_desc, a); break;
-    case 4: if (a.flags & 1) hipLaunchKernelGGL((assemble_kernel<4, true>), grid, dim3(256), 0, stream, d_desc, a); else hipLaunchKernelGGL((assemble_kernel<4, false>), grid, dim3(256), 0, stream, d_desc, a); break;
-    default: LPGP_CHECK(false, "assemble: d=%d", host_desc.d);
-  }
-  prof_end(ctx, stream);
-  LPGP_HIP(hipGetLastError());
-  LPGP_HIP(hipEventRecord(slot.done, stream));
-  slot.used = true;
-  return 0;
+  const AsmJob job{x0, n0, n0_pad, x1, n1, n1_pad, row_off, col_off, lower_only};
+  return launch_assemble_batch(ctx, stream, host_desc, &job, 1, out, ld, lay);
 }
 
 // One block of a variable-coefficient operator pair (assemble_weighted_kernel): lowers every pair, stages the descriptors
@@ -685,7 +750,9 @@ int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs
   LPGP_CHECK(npairs >= 1 && npairs <= WT_MAXP && A0 >= 1 && A0 <= LPGP_MAXW && A1 >= 1 && A1 <= LPGP_MAXW, "assemble_weighted: bad sizes");
   const int64_t n0 = X0->n, n1 = X1->n;
   const int d = X0->d;
-  if (n0 <= 0 || n1 <= 0) return 0;                // an empty block: nothing to stage, nothing to write
+  const AsmJob job{X0->x, n0, X0->n_pad, X1->x, n1, X1->n_pad, row_off, col_off, sym ? 1 : 0};
+  AsmArgs a;
+  if (!asm_args(job, out, ld, lay, &a)) return 0;
   std::vector<char> h;
   size_t off_desc[WT_MAXP];
   bool radial = false;
@@ -701,6 +768,7 @@ int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs
       std::memcpy(h.data() + off_desc[p], desc.get(), bytes);
     }
   }
+  LPGP_CHECK(dim_ok(d), "assemble_weighted: d=%d", d);
   const size_t off_w0 = h.size(), w0_bytes = (size_t)A0 * (size_t)n0 * sizeof(double);
   h.resize(off_w0 + w0_bytes);
   std::memcpy(h.data() + off_w0, w0_host, w0_bytes);
@@ -711,13 +779,6 @@ int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs
     h.resize(off_w1 + w1_bytes);
     std::memcpy(h.data() + off_w1, w1_host, w1_bytes);
   }
-  AsmArgs a;
-  a.x0 = X0->x; a.x1 = X1->x; a.n0 = n0; a.n1 = n1; a.n0_pad = X0->n_pad; a.n1_pad = X1->n_pad;
-  a.out = out; a.ld = ld; a.row_off = row_off; a.col_off = col_off; a.lower_only = sym ? 1 : 0;
-  a.lay = lay;
-  a.tiles_r = (int)((n0 + AT - 1) / AT);
-  a.tiles_c = (int)((n1 + AT - 1) / AT);
-  if (a.tiles_r == 0 || a.tiles_c == 0) return 0;
   DevBuf buf;
   LPGP_TRY(DevBuf::pool(ctx, h.size(), &buf));
   StreamDrain drain{stream};                       // (behind `h` and `buf`: the copy out of `h` has landed before either goes)
@@ -735,34 +796,14 @@ int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs
   wa.w0_stride = n0;
   wa.w1_stride = n1;
   const dim3 grid((unsigned)((int64_t)a.tiles_r * a.tiles_c));
-  const double entries = sym ? 0.5 * (double)n0 * ((double)n0 + 1.0) : (double)n0 * (double)n1;
-  prof_begin(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * entries);
-  if (radial) {
-    switch (d) {
-      case 1: hipLaunchKernelGGL((assemble_weighted_kernel<1, true>), grid, dim3(256), 0, stream, wa, a); break;
-      case 2: hipLaunchKernelGGL((assemble_weighted_kernel<2, true>), grid, dim3(256), 0, stream, wa, a); break;
-      case 3: hipLaunchKernelGGL((assemble_weighted_kernel<3, true>), grid, dim3(256), 0, stream, wa, a); break;
-      case 4: hipLaunchKernelGGL((assemble_weighted_kernel<4, true>), grid, dim3(256), 0, stream, wa, a); break;
-      default: prof_end(ctx, stream); LPGP_CHECK(false, "assemble_weighted: d=%d", d);
-    }
-  } else
-  switch (d) {
-    case 1: hipLaunchKernelGGL((assemble_weighted_kernel<1>), grid, dim3(256), 0, stream, wa, a); break;
-    case 2: hipLaunchKernelGGL((assemble_weighted_kernel<2>), grid, dim3(256), 0, stream, wa, a); break;
-    case 3: hipLaunchKernelGGL((assemble_weighted_kernel<3>), grid, dim3(256), 0, stream, wa, a); break;
-    case 4: hipLaunchKernelGGL((assemble_weighted_kernel<4>), grid, dim3(256), 0, stream, wa, a); break;
-    default: prof_end(ctx, stream); LPGP_CHECK(false, "assemble_weighted: d=%d", d);
+  {
+    ProfScope prof(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * asm_entries(job));
+    dispatch_dim(d, false, radial, [&](auto D, auto, auto R) {
+      hipLaunchKernelGGL((assemble_weighted_kernel<LPGP_CV(D), LPGP_CV(R)>), grid, dim3(256), 0, stream, wa, a);
+    });
   }
-  prof_end(ctx, stream);
   LPGP_HIP(hipGetLastError());
   return drain.wait();
-}
-
-// column tiles per workgroup of a rectangular block (see launch_assemble)
-static int fast_ct(const lpgp_ctx* ctx, int tiles_r, int tiles_c, int lower_only) {
-  int ct = 1;
-  while (!lower_only && ct < ctx->asm_ct && (int64_t)tiles_r * ((tiles_c + 2 * ct - 1) / (2 * ct)) >= 16 * (int64_t)(ctx->cus > 0 ? ctx->cus : 256)) ct *= 2;
-  return ct;
 }
 
 bool assemble_same_fast(const DevDesc& p, const DevDesc& q) {
@@ -772,55 +813,6 @@ bool assemble_same_fast(const DevDesc& p, const DevDesc& q) {
   int a0, a1, b0, b1;
   if (p.d != q.d || !fast_shape(p, &fp, &a0, &a1) || !fast_shape(q, &fq, &b0, &b1) || a0 != b0 || a1 != b1) return false;
   return std::memcmp(&fp, &fq, sizeof(FastDesc)) == 0;
-}
-
-// Several blocks that share `host_desc` in as few launches as the job table allows (ASM_MAXJ per launch); descriptors outside the
-// specialised kernel's shapes, per-point factors or the measurement aids: one launch_assemble per block, as before.
-int launch_assemble_batch(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, const AsmJob* jobs, int njobs, double* out, int64_t ld,
-                          const Layout2D& lay) {
-  FastDesc fd;
-  int N0 = 0, N1 = 0;
-  static const int diag = [] { const char* e = std::getenv("LPGP_ASM_DIAG"); return e ? std::atoi(e) : 0; }();
-  const bool fast = ctx->asm_fast && ctx->asm_batch && diag == 0 && !(ctx->asm_factors && host_desc.ngroups <= FACT_MAXG) && fast_shape(host_desc, &fd, &N0, &N1);
-  if (!fast || njobs <= 1) {
-    for (int j = 0; j < njobs; ++j)
-      LPGP_TRY_RC(launch_assemble(ctx, stream, host_desc, jobs[j].x0, jobs[j].n0, jobs[j].n0_pad, jobs[j].x1, jobs[j].n1, jobs[j].n1_pad, out, ld,
-                                  jobs[j].row_off, jobs[j].col_off, jobs[j].lower_only, lay));
-    return 0;
-  }
-  for (int j0 = 0; j0 < njobs; j0 += ASM_MAXJ) {
-    AsmBatch bt;
-    double entries = 0.0;
-    int wgs = 0;
-    for (int j = j0; j < njobs && j < j0 + ASM_MAXJ; ++j) {
-      const AsmJob& J = jobs[j];
-      const int tr = (int)((J.n0 + AT - 1) / AT), tc = (int)((J.n1 + AT - 1) / AT);
-      if (tr == 0 || tc == 0) continue;
-      AsmJobDev& d = bt.job[bt.njobs];
-      d.x0 = J.x0; d.x1 = J.x1; d.n0 = J.n0; d.n1 = J.n1; d.n0_pad = J.n0_pad; d.n1_pad = J.n1_pad;
-      d.row_off = J.row_off; d.col_off = J.col_off; d.lower_only = J.lower_only;
-      d.tiles_r = tr; d.tiles_c = tc; d.ct = fast_ct(ctx, tr, tc, J.lower_only);
-      bt.wg0[bt.njobs] = wgs;
-      wgs += tr * ((tc + d.ct - 1) / d.ct);
-      ++bt.njobs;
-      entries += J.lower_only ? 0.5 * (double)J.n0 * ((double)J.n0 + 1.0) : (double)J.n0 * (double)J.n1;
-    }
-    if (bt.njobs == 0) continue;
-    bt.wg0[bt.njobs] = wgs;
-    AsmArgs a;                       // the first job's fields (a launch with ONE job runs on them alone)
-    const AsmJobDev& f = bt.job[0];
-    a.x0 = f.x0; a.x1 = f.x1; a.n0 = f.n0; a.n1 = f.n1; a.n0_pad = f.n0_pad; a.n1_pad = f.n1_pad;
-    a.out = out; a.ld = ld; a.row_off = f.row_off; a.col_off = f.col_off; a.lower_only = f.lower_only; a.lay = lay;
-    a.tiles_r = f.tiles_r; a.tiles_c = f.tiles_c; a.ct = f.ct; a.flags = 0;
-    prof_begin(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * entries);
-    g_asm_batch = &bt;
-    if (host_desc.d == 1) launch_fast<0, 1>(N0, N1, dim3((unsigned)wgs), stream, fd, a);
-    else launch_fast<0, 2>(N0, N1, dim3((unsigned)wgs), stream, fd, a);
-    g_asm_batch = nullptr;
-    prof_end(ctx, stream);
-    LPGP_HIP(hipGetLastError());
-  }
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -936,50 +928,30 @@ int launch_matvec(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, c
   a.x0 = x0; a.x1 = x1; a.n0 = n0; a.n1 = n1; a.n0_pad = n0_pad; a.n1_pad = n1_pad;
   a.v = v; a.v_stride = v_stride; a.part = part; a.nr = nr;
   const bool radial = desc_has_radial(host_desc);
-  a.factors = (ctx->asm_factors && host_desc.ngroups <= FACT_MAXG && !radial) ? 1 : 0;
+  a.factors = asm_flags(ctx, host_desc, radial) & 1;      // (the product has no measurement aids)
   a.tiles_r = (int)((n0 + AT - 1) / AT);
   a.tiles_c = (int)((n1 + AT - 1) / AT);
   a.splits = splits;
-  dim3 grid((unsigned)((int64_t)a.tiles_r * splits));
-  {
-    FastDesc fd;
-    int N0 = 0, N1 = 0;
-    if (ctx->asm_fast && !a.factors && fast_shape(host_desc, &fd, &N0, &N1)) {      // the common shapes: specialised evaluation
-      prof_begin(ctx, stream, LPGP_K_MATVEC, 2.0 * (double)n0 * (double)n1 * nr, 0.0);
+  const dim3 grid((unsigned)((int64_t)a.tiles_r * splits));
+  const double flops = 2.0 * (double)n0 * (double)n1 * nr;
+  FastDesc fd;
+  int N0 = 0, N1 = 0;
+  // (either way the profiled interval ends before the reduction is launched)
+  if (fast_path(ctx, host_desc, a.factors, &fd, &N0, &N1)) {      // the common shapes: specialised evaluation
+    {
+      ProfScope prof(ctx, stream, LPGP_K_MATVEC, flops, 0.0);
       if (host_desc.d == 1) launch_fast<1, 1>(N0, N1, grid, stream, fd, a);
       else launch_fast<1, 2>(N0, N1, grid, stream, fd, a);
-      prof_end(ctx, stream);
-      LPGP_HIP(hipGetLastError());
-      hipLaunchKernelGGL(mv_reduce_kernel, dim3((unsigned)((n0 + 255) / 256), (unsigned)nr), dim3(256), 0, stream,
-                         (const double*)part, out, n0, n0_pad, splits, nr, out_stride, accumulate);
-      LPGP_HIP(hipGetLastError());
-      return 0;
     }
+    LPGP_HIP(hipGetLastError());
+  } else {
+    LPGP_CHECK(dim_ok(host_desc.d), "matvec: d=%d", host_desc.d);
+    LPGP_TRY_RC(launch_staged(ctx, stream, host_desc, LPGP_K_MATVEC, flops, 0.0, [&](const DevDesc* d_desc) {
+      dispatch_dim(host_desc.d, a.factors != 0, radial, [&](auto D, auto F, auto R) {
+        hipLaunchKernelGGL((matvec_kernel<LPGP_CV(D), LPGP_CV(F), LPGP_CV(R)>), grid, dim3(256), 0, stream, d_desc, a);
+      });
+    }));
   }
-  lpgp_ctx::DescSlot* slot = nullptr;
-  int rc = stage_desc(ctx, stream, host_desc, &slot);
-  if (rc != 0) return rc;
-  prof_begin(ctx, stream, LPGP_K_MATVEC, 2.0 * (double)n0 * (double)n1 * nr, 0.0);
-  if (radial) {
-    switch (host_desc.d) {
-      case 1: hipLaunchKernelGGL((matvec_kernel<1, false, true>), grid, dim3(256), 0, stream, slot->d, a); break;
-      case 2: hipLaunchKernelGGL((matvec_kernel<2, false, true>), grid, dim3(256), 0, stream, slot->d, a); break;
-      case 3: hipLaunchKernelGGL((matvec_kernel<3, false, true>), grid, dim3(256), 0, stream, slot->d, a); break;
-      case 4: hipLaunchKernelGGL((matvec_kernel<4, false, true>), grid, dim3(256), 0, stream, slot->d, a); break;
-      default: prof_end(ctx, stream); LPGP_CHECK(false, "matvec: d=%d", host_desc.d);
-    }
-  } else
-  switch (host_desc.d) {
-    case 1: if (a.factors) hipLaunchKernelGGL((matvec_kernel<1, true>), grid, dim3(256), 0, stream, slot->d, a); else hipLaunchKernelGGL((matvec_kernel<1, false>), grid, dim3(256), 0, stream, slot->d, a); break;
-    case 2: if (a.factors) hipLaunchKernelGGL((matvec_kernel<2, true>), grid, dim3(256), 0, stream, slot->d, a); else hipLaunchKernelGGL((matvec_kernel<2, false>), grid, dim3(256), 0, stream, slot->d, a); break;
-    case 3: if (a.factors) hipLaunchKernelGGL((matvec_kernel<3, true>), grid, dim3(256), 0, stream, slot->d, a); else hipLaunchKernelGGL((matvec_kernel<3, false>), grid, dim3(256), 0, stream, slot->d, a); break;
-    case 4: if (a.factors) hipLaunchKernelGGL((matvec_kernel<4, true>), grid, dim3(256), 0, stream, slot->d, a); else hipLaunchKernelGGL((matvec_kernel<4, false>), grid, dim3(256), 0, stream, slot->d, a); break;
-    default: LPGP_CHECK(false, "matvec: d=%d", host_desc.d);
-  }
-  prof_end(ctx, stream);
-  LPGP_HIP(hipGetLastError());
-  LPGP_HIP(hipEventRecord(slot->done, stream));
-  slot->used = true;
   hipLaunchKernelGGL(mv_reduce_kernel, dim3((unsigned)((n0 + 255) / 256), (unsigned)nr), dim3(256), 0, stream,
                      (const double*)part, out, n0, n0_pad, splits, nr, out_stride, accumulate);
   LPGP_HIP(hipGetLastError());

@@ -371,6 +371,15 @@ struct LPGP_LOCAL EventPair {
 // profiling helpers: bracket launches of `kernel` on `stream`
 void prof_begin(lpgp_ctx* ctx, hipStream_t stream, int kernel, double flops, double bytes);
 void prof_end(lpgp_ctx* ctx, hipStream_t stream);
+// ... paired on every way out of the scope of the launch
+struct LPGP_LOCAL ProfScope {
+  lpgp_ctx* ctx;
+  hipStream_t stream;
+  ProfScope(lpgp_ctx* c, hipStream_t s, int kernel, double flops, double bytes) : ctx(c), stream(s) { prof_begin(c, s, kernel, flops, bytes); }
+  ProfScope(const ProfScope&) = delete;
+  ProfScope& operator=(const ProfScope&) = delete;
+  ~ProfScope() { prof_end(ctx, stream); }
+};
 int prof_collect(lpgp_ctx* ctx);
 
 // gemm.hip --------------------------------------------------------------------------------

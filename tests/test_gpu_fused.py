@@ -288,6 +288,64 @@ def test_batched_block_rows_are_bit_identical():
     assert prior._rows_seen == sum(-(-(17 + 11 * k) // 128) * 128 for k in range(17))        # (the next chain from this prior starts with room for it)
 
 
+def test_batched_block_rows_take_the_launches_their_runs_predict():
+    """The launch structure behind the bit identity above: a run of r row entries that share a descriptor takes ceil(r / 8) launches
+    of the assembly kernel with `asm_batch = 1` (eight jobs per table) and r launches with `asm_batch = 0`; a change of descriptor
+    ends a run.  Read off the `assemble` profiling slot around `lpgp_mat_condition` and `lpgp_cross_assemble_row`, with explicit
+    (descriptor, points) rows, so that neither the grid path nor the host package's choices enter."""
+    import linpde_gp_amd as lp
+    from linpde_gp_amd import _engine
+    from linpde_gp_amd.randprocs._gaussian_process import _lowered
+    ctx = _engine.default_context()
+    cf = lp.randprocs.covfuncs
+    ident = {(0,): 1.0}
+    kdA = _lowered(cf.Matern((1,), nu=2.5, lengthscales=0.5), ident, ident)
+    kdB = _lowered(cf.Matern((1,), nu=2.5, lengthscales=0.3), ident, ident)
+    rng = np.random.default_rng(23)
+    Xs = [rng.uniform(-1, 1, (17 + 11 * k, 1)) for k in range(10)]
+    Xt = np.linspace(-1, 1, 50)[:, None]
+
+    def launches():
+        return ctx.profile_get()["assemble"]["launches"]
+
+    saved = ctx.get_option("asm_batch")
+    counts, out = {}, {}
+    ctx.profile_reset(); ctx.profile_enable(["assemble"])
+    try:
+        for batch in (1, 0):
+            ctx.set_option("asm_batch", batch)
+            # ten value blocks in a chain, each against all earlier ones with ONE descriptor: rows of 1 .. 10 entries
+            P = [_engine.Points(ctx, X) for X in Xs]
+            Pt = _engine.Points(ctx, Xt)
+            mat = _engine.GramMatrix(ctx)
+            n0 = launches()
+            for k in range(10):
+                assert mat.condition(Xs[k].shape[0], P[k], [(kdA, P[j]) for j in range(k)] + [(kdA, None)], noise_scalar=1e-2, lazy=0) == 0
+            n1 = launches()
+            # the rows of a cross-covariance against the ten blocks, one descriptor
+            rhs = _engine.Rhs(ctx, mat, Xt.shape[0])
+            rhs.cross_assemble_row([(kdA, P[j]) for j in range(10)], Pt)
+            n2 = launches()
+            # a row whose entries alternate between two descriptors of the specialised shape: A, A, B, A (assembled only)
+            alt = _engine.GramMatrix(ctx)
+            for k in range(3):
+                assert alt.condition(Xs[k].shape[0], P[k], [(kdA, P[j]) for j in range(k)] + [(kdA, None)], noise_scalar=1e-2, lazy=2) == 0
+            n3 = launches()
+            assert alt.condition(Xs[3].shape[0], P[3], [(kdA, P[0]), (kdA, P[1]), (kdB, P[2]), (kdA, None)], noise_scalar=1e-2, lazy=2) == 0
+            n4 = launches()
+            counts[batch] = (n1 - n0, n2 - n1, n4 - n3)
+            out[batch] = (np.tril(mat.todense("factor")), rhs.to_host(), alt.todense("gram"))
+            print(f"asm_batch={batch}: assemble launches: chain {n1 - n0}, cross row {n2 - n1}, row A A B A {n4 - n3}")
+            del rhs, mat, alt
+    finally:
+        ctx.set_option("asm_batch", saved)
+        ctx.profile_enable(False)
+    assert counts[1] == (8 * 1 + 2 * 2, -(-10 // 8), 3)
+    assert counts[0] == (sum(range(1, 11)), 10, 4)
+    for a, b in zip(out[1], out[0]):
+        np.testing.assert_array_equal(a, b)
+
+
 @pytest.mark.parametrize("make", [lambda P: P.poisson_1d(512, n_bdry_repeats=16, noise_var=1e-4, m=256),        # one resident panel behind an old one
                                   lambda P: P.poisson_2d(n_side=32, m_side=16),                                # two resident panels
                                   lambda P: P.poisson_2d(n_side=40, n_bdry=40, m_side=24),                     # panels off the block grid, 640 columns
