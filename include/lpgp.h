@@ -38,8 +38,22 @@ extern "C" {
  * by kernels of their own (one sqrt, one exponential per entry).  Refused: p < 2 with a derivative on both arguments or two
  * on one, more than two derivatives per argument, dlog_lengthscale != 0, p > 6.  Family 3 keeps its own lowering and bits.  Both isotropic families check the orders of EVERY
  * term before they drop the terms with coef == 0, so a zero-coefficient term of too high an order is refused, not ignored
- * (the Python layer never sends one: it drops zero terms before it lowers). */
-enum lpgp_family { LPGP_MATERN_HALFINT = 1, LPGP_EXPQUAD = 2, LPGP_MATERN_ISO = 3, LPGP_MATERN_RADIAL = 4 };
+ * (the Python layer never sends one: it drops zero terms before it lowers).
+ * LPGP_WENDLAND, LPGP_WENDLAND_ISO: Wendland's compactly supported piecewise polynomials (Wendland 2004, Def. 9.11, Thm.
+ * 9.12-9.13; the reference's `WendlandCovarianceFunction`): p[j] carries k = 0 .. 3, l = floor(d / 2) + k + 1,
+ * phi_{d,k} = I^k (1 - r)_+^l with (I f)(r) = int_r^inf t f(t) dt, normalised so that phi(0) = 1; the value is exactly 0 for
+ * r > 1 and r <= 1 counts as inside.  Every derivative is again (1 - r)^e times a polynomial, so all forms below are exact
+ * closed forms (csrc/lower.cpp: integer polynomials, one rounding per stored coefficient).
+ *   LPGP_WENDLAND: a univariate product-form FACTOR phi_{1,k}(|x_j - x'_j| / lengthscale[j]) of dimension j, free to stand
+ *   beside Matern and ExpQuad factors in one descriptor; derivative orders n0 + n1 <= 2 k per dimension (more is refused).
+ *   LPGP_WENDLAND_ISO: the isotropic phi_{d,k}(|| (x - x') / lengthscale ||) over all d dimensions of the descriptor (each
+ *   carries this family and one k; per-dimension lengthscales allowed), with at most one derivative per argument: identity
+ *   and directional derivatives.  Refused: any derivative at k = 0, a derivative on both arguments at k = 1 (its form carries
+ *   a 1 / s term), more than one derivative per argument; orders are checked before zero-coefficient terms are dropped.
+ *   Both refuse dlog_lengthscale != 0 and k outside 0 .. 3.  Descriptors that hold either run kernel instantiations of their
+ *   own, which also skip the evaluation of 64 x 64 tiles whose row and column points are out of each other's reach. */
+enum lpgp_family { LPGP_MATERN_HALFINT = 1, LPGP_EXPQUAD = 2, LPGP_MATERN_ISO = 3, LPGP_MATERN_RADIAL = 4, LPGP_WENDLAND = 5,
+                   LPGP_WENDLAND_ISO = 6 };
 
 typedef struct lpgp_ctx lpgp_ctx;   /* one per process / per GPU                          */
 typedef struct lpgp_pts lpgp_pts;   /* device-resident point set (n x d)                  */
@@ -72,7 +86,7 @@ typedef struct {
   lpgp_term terms[LPGP_MAXT];
   /* 0: the kernel itself.  j + 1: its derivative with respect to log lengthscale[j] -- the form above is closed under it
    * (csrc/lower.cpp), so every assembly / product entry point evaluates d G / d log l_j like any other block.  Product-form
-   * families only (LPGP_MATERN_ISO and LPGP_MATERN_RADIAL are refused).  A zero-initialised descriptor keeps its meaning.                        */
+   * families only (LPGP_MATERN_ISO and LPGP_MATERN_RADIAL are refused), and no group with a Wendland factor.  A zero-initialised descriptor keeps its meaning.                        */
   int32_t   dlog_lengthscale;
 } lpgp_kdesc;
 

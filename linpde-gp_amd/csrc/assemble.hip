@@ -106,14 +106,31 @@ __device__ __forceinline__ void stage_factors(const DevDesc* __restrict__ desc, 
   }
 }
 
+// min / max of v over the lanes of the wave that have `valid` set (at least one has), the same value in every lane: a butterfly of
+// six exchanges (the COMPACT instantiations: bounding boxes of a tile's points)
+__device__ __forceinline__ void wave_minmax(double v, bool valid, double& lo, double& hi) {
+  lo = valid ? v : __builtin_huge_val();
+  hi = valid ? v : -__builtin_huge_val();
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lo = fmin(lo, __shfl_xor(lo, off, 64));
+    hi = fmax(hi, __shfl_xor(hi, off, 64));
+  }
+}
+
 // FACTORS: the per-point exponential factors (`asm_factors`, off by default) need 2 x FACT_MAXG * D * 2 * 64 doubles of LDS (32 KB
 // at D = 4); the default instantiation carries the 4-KB exponential table only (the generic kernel is the one that
 // takes everything the specialised kernels reject -- D >= 3, several groups, isotropic -- and ran at 4 / 3 workgroups per CU)
-// RADIAL (never with FACTORS): the descriptor holds a radial Matern group (eval_entries.h: eval_radial_group); kernels of their
-// own, picked on the host, so that the instantiations above the radial family are what they were
-template <int D, bool FACTORS, bool RADIAL = false>
+// VAR (eval_entries.h: EvalVariant; EV_PLAIN whenever FACTORS): EV_RADIAL -- the descriptor holds a radial Matern group
+// (eval_radial_group); EV_COMPACT -- it holds a Wendland group.  Kernels of their own, picked on the host, so that the instantiations
+// above these families are what they were.  EV_COMPACT also knows empty tiles: wave j reduces the bounding box of the tile's valid
+// row and column points in dimension j, and where every group of the descriptor is compact and out of reach between the two boxes
+// (lpgp_out_of_reach: the entries' own operations on the boxes' gap, so the result is bit-identical) the tile stores its zeros
+// without evaluating anything -- the matrix is not pre-cleared.
+template <int D, bool FACTORS, int VAR = EV_PLAIN>
 __global__ __launch_bounds__(256) void assemble_kernel(const DevDesc* __restrict__ desc, AsmArgs a) {
   __shared__ double sx1[D][AT];
+  __shared__ double s_box[VAR == EV_COMPACT ? D : 1][4];
   __shared__ double sfr[FACTORS ? FACT_MAXG * D * 2 * AT : 1], sfc[FACTORS ? FACT_MAXG * D * 2 * AT : 1];
   __shared__ __attribute__((aligned(16))) double s_exp[2 * EXP_TAB_N];      // table of lpgp_exp_neg (eval_entries.h)
   __shared__ int s_fast;
@@ -143,7 +160,26 @@ __global__ __launch_bounds__(256) void assemble_kernel(const DevDesc* __restrict
   if (threadIdx.x == 0) s_fast = FACTORS ? (a.flags & 1) : 0;
   s_exp[threadIdx.x] = g_exp_table[threadIdx.x], s_exp[threadIdx.x + 256] = g_exp_table[threadIdx.x + 256];         // (256 threads, 256 entries)
   const ExpTab etab{s_exp};
+  if constexpr (VAR == EV_COMPACT) {
+    if (wu < D) {                                      // (D <= 4 waves: one dimension each; padded lanes stay out)
+      double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+      for (int j = 0; j < D; ++j)
+        if (j == wu) { v0 = xr[j]; v1 = xc[j]; }
+      double rlo, rhi, clo, chi;
+      wave_minmax(v0, row < a.n0, rlo, rhi);
+      wave_minmax(v1, col < a.n1, clo, chi);
+      if (lane == 0) { s_box[wu][0] = rlo; s_box[wu][1] = rhi; s_box[wu][2] = clo; s_box[wu][3] = chi; }
+    }
+  }
   __syncthreads();
+  bool empty = false;                                  // workgroup-uniform: every lane reads the same boxes
+  if constexpr (VAR == EV_COMPACT) {
+    double rlo[D], rhi[D], clo[D], chi[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) { rlo[j] = s_box[j][0]; rhi[j] = s_box[j][1]; clo[j] = s_box[j][2]; chi[j] = s_box[j][3]; }
+    empty = (a.flags & 6) == 0 && lpgp_out_of_reach<D>(desc, rlo, rhi, clo, chi);
+  }
   if (FACTORS && (a.flags & 1)) {
     // waves 0,1: row factors; waves 2,3: column factors
     if (wu < 2) stage_factors<D>(desc, xr, x0, row < a.n0, sfr, lane, wu, 2, &s_fast);
@@ -166,10 +202,11 @@ __global__ __launch_bounds__(256) void assemble_kernel(const DevDesc* __restrict
     } else if (fast) {
       LdsFactors<D> fac{sfr + lane, sfc + cb};
       eval_entries<D, AEK, LdsFactors<D>>(desc, dx, res, etab, fac);
-    } else if constexpr (RADIAL) {
-      eval_entries_radial<D, AEK>(desc, dx, res, etab);
+    } else if (VAR == EV_COMPACT && empty) {
+#pragma unroll
+      for (int e = 0; e < AEK; ++e) res[e] = 0.0;
     } else {
-      eval_entries<D, AEK>(desc, dx, res, etab);
+      eval_entries_var<VAR, D, AEK>(desc, dx, res, etab);
     }
     if (a.flags & 4) {
 #pragma unroll
@@ -206,7 +243,7 @@ struct WeightArgs {
   int64_t w0_stride, w1_stride;
 };
 
-template <int D, bool RADIAL = false>       // RADIAL: some pair's descriptor holds a radial Matern group
+template <int D, int VAR = EV_PLAIN>       // VAR: some pair's descriptor holds a radial Matern group (EV_RADIAL) or a Wendland group (EV_COMPACT)
 __global__ __launch_bounds__(256) void assemble_weighted_kernel(WeightArgs wa, AsmArgs a) {
   __shared__ double sx1[D][AT];
   __shared__ double sw1[LPGP_MAXW][AT];
@@ -249,8 +286,7 @@ __global__ __launch_bounds__(256) void assemble_weighted_kernel(WeightArgs wa, A
     for (int p = 0; p < wa.npairs; ++p) {
       const int qa = wa.pa[p], qb = wa.pb[p];                // (uniform: scalar loads from the kernel arguments)
       double res[AEK];
-      if constexpr (RADIAL) eval_entries_radial<D, AEK>(wa.desc[p], dx, res, etab);
-      else eval_entries<D, AEK>(wa.desc[p], dx, res, etab);
+      eval_entries_var<VAR, D, AEK>(wa.desc[p], dx, res, etab);
       const double wrow = qa == 0 ? wr[0] : (qa == 1 ? wr[1] : (qa == 2 ? wr[2] : wr[3]));      // (selects: no indexed register file)
       if (p == 0) {                                            // (a product, not fma(w, v, +0.0): keeps the sign of a zero entry)
 #pragma unroll
@@ -503,6 +539,8 @@ static bool fast_shape(const DevDesc& d, FastDesc* fd, int* n0, int* n1) {
   if (d.d < 1 || d.d > 2 || d.ngroups != 1) return false;
   const DevGroup& G = d.g[0];
   if (G.iso || G.ncls < 1 || G.ncls > 2) return false;
+  for (int j = 0; j < d.d; ++j)
+    if (ek_kind(G.expkind[j]) == EK_COMPACT) return false;             // a Wendland dimension: the generic COMPACT kernels
   const int N0 = G.deg[0] + 1, N1 = d.d > 1 ? G.deg[1] + 1 : 1;
   if (N0 < 1 || N0 > 5 || N1 < 1 || N1 > 5 || G.ncls * N0 * N1 > FAST_MAXC) return false;
   fd->scale = G.scale;
@@ -614,15 +652,20 @@ static int launch_staged(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_
   return 0;
 }
 
-// The one place where the run-time (d, factors, radial) of a launch become the template arguments <D, FACTORS, RADIAL> of the generic
-// kernels: f(D, FACTORS, RADIAL) with integral constants.  Radial takes no factors; the caller has refused a d outside dim_ok.
+// The one place where the run-time (d, factors, variant) of a launch become the template arguments <D, FACTORS, VAR> of the generic
+// kernels: f(D, FACTORS, VAR) with integral constants.  Radial and compact take no factors; the caller has refused a d outside dim_ok.
 static bool dim_ok(int d) { return d >= 1 && d <= 4; }
+// the variant a descriptor needs: EV_COMPACT evaluates everything, EV_RADIAL everything but Wendland groups
+static int desc_variant(const DevDesc& desc) {
+  return desc_has_compact(desc) ? EV_COMPACT : (desc_has_radial(desc) ? EV_RADIAL : EV_PLAIN);
+}
 template <class F>
-static void dispatch_dim(int d, bool factors, bool radial, F&& f) {
+static void dispatch_dim(int d, bool factors, int var, F&& f) {
   auto with = [&](auto D) {
-    if (radial) f(D, std::false_type{}, std::true_type{});
-    else if (factors) f(D, std::true_type{}, std::false_type{});
-    else f(D, std::false_type{}, std::false_type{});
+    if (var == EV_COMPACT) f(D, std::false_type{}, std::integral_constant<int, EV_COMPACT>{});
+    else if (var == EV_RADIAL) f(D, std::false_type{}, std::integral_constant<int, EV_RADIAL>{});
+    else if (factors) f(D, std::true_type{}, std::integral_constant<int, EV_PLAIN>{});
+    else f(D, std::false_type{}, std::integral_constant<int, EV_PLAIN>{});
   };
   switch (d) {
     case 1: with(std::integral_constant<int, 1>{}); break;
@@ -639,9 +682,9 @@ static int asm_diag() {
   return diag;
 }
 // AsmArgs::flags of a launch with this descriptor (bit 0 alone: MvArgs::factors)
-// (radial groups take no per-point factors: their exponent is not a sum over dimensions)
-static int asm_flags(const lpgp_ctx* ctx, const DevDesc& host_desc, bool radial) {
-  return ((ctx->asm_factors && host_desc.ngroups <= FACT_MAXG && !radial) ? 1 : 0) | ((asm_diag() & 3) << 1);
+// (radial groups take no per-point factors: their exponent is not a sum over dimensions; nor do the compact instantiations)
+static int asm_flags(const lpgp_ctx* ctx, const DevDesc& host_desc, int var) {
+  return ((ctx->asm_factors && host_desc.ngroups <= FACT_MAXG && var == EV_PLAIN) ? 1 : 0) | ((asm_diag() & 3) << 1);
 }
 // the common shapes on the specialised kernels (descriptor by value: no staging, no slot), unless one of `flags` asks for what
 // only the generic kernels do
@@ -705,8 +748,8 @@ static int launch_fast_jobs(lpgp_ctx* ctx, hipStream_t stream, int d, const Fast
 // measurement aid, or with a descriptor outside the specialised kernel's shapes (then through the generic kernel): one launch per block.
 int launch_assemble_batch(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, const AsmJob* jobs, int njobs, double* out, int64_t ld,
                           const Layout2D& lay) {
-  const bool radial = desc_has_radial(host_desc);
-  const int flags = asm_flags(ctx, host_desc, radial);
+  const int var = desc_variant(host_desc);
+  const int flags = asm_flags(ctx, host_desc, var);
   FastDesc fd;
   int N0 = 0, N1 = 0;
   if (fast_path(ctx, host_desc, flags, &fd, &N0, &N1)) {
@@ -722,8 +765,8 @@ int launch_assemble_batch(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host
     a.flags = flags;
     const dim3 grid((unsigned)((int64_t)a.tiles_r * a.tiles_c));
     LPGP_TRY_RC(launch_staged(ctx, stream, host_desc, LPGP_K_ASSEMBLE, 0.0, 8.0 * asm_entries(jobs[j]), [&](const DevDesc* d_desc) {
-      dispatch_dim(host_desc.d, flags & 1, radial, [&](auto D, auto F, auto R) {
-        hipLaunchKernelGGL((assemble_kernel<LPGP_CV(D), LPGP_CV(F), LPGP_CV(R)>), grid, dim3(256), 0, stream, d_desc, a);
+      dispatch_dim(host_desc.d, flags & 1, var, [&](auto D, auto F, auto V) {
+        hipLaunchKernelGGL((assemble_kernel<LPGP_CV(D), LPGP_CV(F), LPGP_CV(V)>), grid, dim3(256), 0, stream, d_desc, a);
       });
     }));
   }
@@ -755,13 +798,13 @@ int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs
   if (!asm_args(job, out, ld, lay, &a)) return 0;
   std::vector<char> h;
   size_t off_desc[WT_MAXP];
-  bool radial = false;
+  int var = EV_PLAIN;
   {
     std::unique_ptr<DevDesc> desc(new DevDesc);
     for (int p = 0; p < npairs; ++p) {
       LPGP_TRY_RC(lower_kdesc(pairs[p].kd, pairs[p].ngroups, desc.get()));
       LPGP_CHECK(desc->d == d, "assemble_weighted: pair %d lowers to d=%d, the points have d=%d", p, desc->d, d);
-      radial = radial || desc_has_radial(*desc);
+      if (desc_variant(*desc) > var) var = desc_variant(*desc);       // (EV_COMPACT evaluates what EV_RADIAL does)
       const size_t bytes = desc_used_bytes(*desc);
       off_desc[p] = h.size();
       h.resize(h.size() + (bytes + 15) / 16 * 16);
@@ -798,8 +841,8 @@ int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs
   const dim3 grid((unsigned)((int64_t)a.tiles_r * a.tiles_c));
   {
     ProfScope prof(ctx, stream, LPGP_K_ASSEMBLE, 0.0, 8.0 * asm_entries(job));
-    dispatch_dim(d, false, radial, [&](auto D, auto, auto R) {
-      hipLaunchKernelGGL((assemble_weighted_kernel<LPGP_CV(D), LPGP_CV(R)>), grid, dim3(256), 0, stream, wa, a);
+    dispatch_dim(d, false, var, [&](auto D, auto, auto V) {
+      hipLaunchKernelGGL((assemble_weighted_kernel<LPGP_CV(D), LPGP_CV(V)>), grid, dim3(256), 0, stream, wa, a);
     });
   }
   LPGP_HIP(hipGetLastError());
@@ -825,9 +868,11 @@ bool assemble_same_fast(const DevDesc& p, const DevDesc& q) {
 // slab of each 64-column tile, up to MV_R right-hand sides ride along per evaluation.
 // Partial sums per split go to `part`; mv_reduce_kernel adds them in a fixed order.
 // ---------------------------------------------------------------------------------------
-template <int D, bool FACTORS, bool RADIAL = false>
+// EV_COMPACT: a column tile out of reach of this workgroup's rows (see assemble_kernel) contributes nothing and is not evaluated
+template <int D, bool FACTORS, int VAR = EV_PLAIN>
 __global__ __launch_bounds__(256) void matvec_kernel(const DevDesc* __restrict__ desc, MvArgs a) {
   __shared__ double sx1[D][AT];
+  __shared__ double s_rbox[VAR == EV_COMPACT ? D : 1][2], s_cbox[VAR == EV_COMPACT ? D : 1][2];
   __shared__ double sv[MV_R][AT];
   __shared__ double red[3][MV_R][AT];
   // per-point exponential factors (see assemble_kernel): origin = the first row of this workgroup's row tile; the row
@@ -854,6 +899,17 @@ __global__ __launch_bounds__(256) void matvec_kernel(const DevDesc* __restrict__
   if (threadIdx.x == 0) { s_fast_r = FACTORS ? a.factors : 0; s_fast_c[0] = 1; s_fast_c[1] = 1; }
   s_exp[threadIdx.x] = g_exp_table[threadIdx.x], s_exp[threadIdx.x + 256] = g_exp_table[threadIdx.x + 256];
   const ExpTab etab{s_exp};
+  if constexpr (VAR == EV_COMPACT) {
+    if (wu < D) {                                      // the rows' bounding box, once: wave j reduces dimension j
+      double v0 = 0.0;
+#pragma unroll
+      for (int j = 0; j < D; ++j)
+        if (j == wu) v0 = xr[j];
+      double lo, hi;
+      wave_minmax(v0, row < a.n0, lo, hi);
+      if (lane == 0) { s_rbox[wu][0] = lo; s_rbox[wu][1] = hi; }
+    }
+  }
   __syncthreads();
   if (FACTORS && a.factors) stage_factors<D>(desc, xr, x0, row < a.n0, sfr, lane, wu, 4, &s_fast_r);
 
@@ -868,8 +924,25 @@ __global__ __launch_bounds__(256) void matvec_kernel(const DevDesc* __restrict__
       for (int j = 0; j < D; ++j) xc[j] = (c < a.n1) ? a.x1[j * a.n1_pad + c] : 0.0;
       if (FACTORS && a.factors) stage_factors<D>(desc, xc, x0, c < a.n1, sfc, lane, wu, 4, &s_fast_c[tc & 1]);
       if (threadIdx.x == 0) s_fast_c[(tc + 1) & 1] = 1;       // the next tile's flag (read two barriers from now)
+      if constexpr (VAR == EV_COMPACT) {
+        if (wu < D) {                                          // this tile's column box (read behind the barrier below, rewritten behind the next one)
+          double v1 = 0.0;
+#pragma unroll
+          for (int j = 0; j < D; ++j)
+            if (j == wu) v1 = xc[j];
+          double lo, hi;
+          wave_minmax(v1, c < a.n1, lo, hi);
+          if (lane == 0) { s_cbox[wu][0] = lo; s_cbox[wu][1] = hi; }
+        }
+      }
     }
     __syncthreads();
+    if constexpr (VAR == EV_COMPACT) {
+      double rlo[D], rhi[D], clo[D], chi[D];
+#pragma unroll
+      for (int j = 0; j < D; ++j) { rlo[j] = s_rbox[j][0]; rhi[j] = s_rbox[j][1]; clo[j] = s_cbox[j][0]; chi[j] = s_cbox[j][1]; }
+      if (lpgp_out_of_reach<D>(desc, rlo, rhi, clo, chi)) continue;      // (workgroup-uniform: every lane reads the same boxes)
+    }
     const bool fast = FACTORS && s_fast_r != 0 && s_fast_c[tc & 1] != 0;
 #pragma unroll 1
     for (int pass = 0; pass < 16 / AEK; ++pass) {
@@ -882,10 +955,8 @@ __global__ __launch_bounds__(256) void matvec_kernel(const DevDesc* __restrict__
       if (fast) {
         LdsFactors<D> fac{sfr + lane, sfc + cb};
         eval_entries<D, AEK, LdsFactors<D>>(desc, dx, res, etab, fac);
-      } else if constexpr (RADIAL) {
-        eval_entries_radial<D, AEK>(desc, dx, res, etab);
       } else {
-        eval_entries<D, AEK>(desc, dx, res, etab);
+        eval_entries_var<VAR, D, AEK>(desc, dx, res, etab);
       }
 #pragma unroll
       for (int e = 0; e < AEK; ++e)
@@ -927,8 +998,8 @@ int launch_matvec(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, c
   MvArgs a;
   a.x0 = x0; a.x1 = x1; a.n0 = n0; a.n1 = n1; a.n0_pad = n0_pad; a.n1_pad = n1_pad;
   a.v = v; a.v_stride = v_stride; a.part = part; a.nr = nr;
-  const bool radial = desc_has_radial(host_desc);
-  a.factors = asm_flags(ctx, host_desc, radial) & 1;      // (the product has no measurement aids)
+  const int var = desc_variant(host_desc);
+  a.factors = asm_flags(ctx, host_desc, var) & 1;      // (the product has no measurement aids)
   a.tiles_r = (int)((n0 + AT - 1) / AT);
   a.tiles_c = (int)((n1 + AT - 1) / AT);
   a.splits = splits;
@@ -947,8 +1018,8 @@ int launch_matvec(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, c
   } else {
     LPGP_CHECK(dim_ok(host_desc.d), "matvec: d=%d", host_desc.d);
     LPGP_TRY_RC(launch_staged(ctx, stream, host_desc, LPGP_K_MATVEC, flops, 0.0, [&](const DevDesc* d_desc) {
-      dispatch_dim(host_desc.d, a.factors != 0, radial, [&](auto D, auto F, auto R) {
-        hipLaunchKernelGGL((matvec_kernel<LPGP_CV(D), LPGP_CV(F), LPGP_CV(R)>), grid, dim3(256), 0, stream, d_desc, a);
+      dispatch_dim(host_desc.d, a.factors != 0, var, [&](auto D, auto F, auto V) {
+        hipLaunchKernelGGL((matvec_kernel<LPGP_CV(D), LPGP_CV(F), LPGP_CV(V)>), grid, dim3(256), 0, stream, d_desc, a);
       });
     }));
   }
@@ -1274,7 +1345,7 @@ bool kron_fits(const lpgp_kdesc* kd, int ngroups) {
   int nterms = 0;
   for (int g = 0; g < ngroups; ++g) {
     const lpgp_kdesc& K = kd[g];
-    if (K.d != D || K.family[0] == LPGP_MATERN_ISO || K.family[0] == LPGP_MATERN_RADIAL || K.nterms < 0 || K.nterms > LPGP_MAXT) return false;
+    if (K.d != D || K.family[0] == LPGP_MATERN_ISO || K.family[0] == LPGP_MATERN_RADIAL || K.family[0] == LPGP_WENDLAND_ISO || K.nterms < 0 || K.nterms > LPGP_MAXT) return false;
     if (K.dlog_lengthscale != 0) return false;   // a lengthscale derivative (lower.cpp) is assembled entry-wise: the 1-D factor matrices are built from plain factors
     nterms += K.nterms;
     if (nterms > KR_MAXT) return false;
@@ -1322,6 +1393,7 @@ int launch_assemble_kron(lpgp_ctx* ctx, hipStream_t stream, const lpgp_kdesc* kd
     const lpgp_kdesc& K = kd[g];
     LPGP_CHECK(K.d == D, "kron assembly: group %d has d=%d != %d", g, K.d, D);
     LPGP_CHECK(K.family[0] != LPGP_MATERN_ISO && K.family[0] != LPGP_MATERN_RADIAL, "kron assembly: an isotropic Matern is not a product over dimensions");
+    LPGP_CHECK(K.family[0] != LPGP_WENDLAND_ISO, "kron assembly: an isotropic Wendland is not a product over dimensions");
     for (int t = 0; t < K.nterms; ++t) {
       LPGP_CHECK(a.nterms < KR_MAXT, "kron assembly: more than %d terms (lpgp_kron_fits tells beforehand)", KR_MAXT);
       const int ti = a.nterms++;

@@ -208,9 +208,25 @@ LPGP_HD void eval_radial_group(const DevDesc* __restrict__ desc, const DevGroup&
   for (int e = 0; e < NE; ++e) res[e] = fma(G.scale * lpgp_exp_neg(sv[e], tab), tot[e], res[e]);
 }
 
-// RADIAL: the descriptor may hold radial Matern groups (iso == 2).  The launch sites pick the RADIAL instantiations on the host
-// (desc_has_radial); the others never meet such a group and carry none of its code.
-template <int D, int NE, class Fac, class Coef, bool RADIAL = false>
+// (1 - r)^n for 0 <= r <= 1, n >= 0 uniform: a scalar loop of multiplies (Wendland groups; no exponential, no table read)
+template <int NE>
+LPGP_HD void lpgp_pow_1m(const double (&r)[NE], int n, double (&m)[NE]) {
+  double t[NE];
+#pragma unroll
+  for (int e = 0; e < NE; ++e) t[e] = 1.0 - r[e];
+  for (int k = n; k > 0; --k) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e) m[e] *= t[e];
+  }
+}
+
+// Which groups an instantiation may meet.  EV_RADIAL: radial Matern groups (iso == 2) too.  EV_COMPACT: everything -- Wendland
+// dimensions and isotropic Wendland groups (expkind 3) beside all the other families, so that sums such as Wendland + Matern
+// work.  The launch sites pick the variant on the host (desc_has_radial, desc_has_compact); EV_PLAIN never meets a radial or
+// compact group and carries none of their code.
+enum EvalVariant { EV_PLAIN = 0, EV_RADIAL = 1, EV_COMPACT = 2 };
+
+template <int D, int NE, class Fac, class Coef, int VAR = EV_PLAIN>
 LPGP_HD void eval_entries(const DevDesc* __restrict__ desc,
                                              const double (&dx)[D][NE], double (&res)[NE], const Fac& fac, const Coef& coef,
                                              const ExpTab& tab) {
@@ -219,7 +235,7 @@ LPGP_HD void eval_entries(const DevDesc* __restrict__ desc,
   for (int e = 0; e < AE; ++e) res[e] = 0.0;
   for (int g = 0; g < desc->ngroups; ++g) {
     const DevGroup& G = desc->g[g];
-    if constexpr (RADIAL) {
+    if constexpr (VAR != EV_PLAIN) {
       if (G.iso == 2) {
         eval_radial_group<D, NE>(desc, G, dx, res, tab);
         continue;
@@ -270,6 +286,22 @@ LPGP_HD void eval_entries(const DevDesc* __restrict__ desc,
           v2[e] = fma(v2[e], sv[e], c2);
         }
       }
+      if constexpr (VAR == EV_COMPACT) {
+        if (ek_kind(G.expkind[0]) == EK_COMPACT) {
+          // isotropic Wendland: (1 - s)^pow inside the support (s^2 <= 1, so 1 - s >= 0), exactly 0.0 outside -- by a select,
+          // not by a product with zero
+          double cm[AE];
+#pragma unroll
+          for (int e = 0; e < AE; ++e) cm[e] = 1.0;
+          lpgp_pow_1m<AE>(sv, ek_pow(G.expkind[0]), cm);
+#pragma unroll
+          for (int e = 0; e < AE; ++e) {
+            const double v = fma(G.scale * cm[e], fma(quad[e], v2[e], fma(lin[e], v1[e], v0[e])), res[e]);
+            res[e] = s2[e] <= 1.0 ? v : res[e];
+          }
+          continue;
+        }
+      }
 #pragma unroll
       for (int e = 0; e < AE; ++e)
         res[e] = fma(G.scale * lpgp_exp_neg(sv[e], tab), fma(quad[e], v2[e], fma(lin[e], v1[e], v0[e])), res[e]);
@@ -278,9 +310,10 @@ LPGP_HD void eval_entries(const DevDesc* __restrict__ desc,
     double r[D][AE];
     unsigned sg[D][AE];
     double expo[AE], ef[AE];
-    bool per_entry_exp = !Fac::enabled;       // some dimension of the group still needs exp(-expo) per entry
+    bool per_entry_exp = !Fac::enabled && VAR != EV_COMPACT;       // some dimension of the group still needs exp(-expo) per entry
+    bool inside[AE];                                               // EV_COMPACT: within the support of every Wendland dimension
 #pragma unroll
-    for (int e = 0; e < AE; ++e) { expo[e] = 0.0; ef[e] = 1.0; }
+    for (int e = 0; e < AE; ++e) { expo[e] = 0.0; ef[e] = 1.0; inside[e] = true; }
 #pragma unroll
     for (int j = 0; j < D; ++j) {
       const double a = G.a[j];
@@ -290,6 +323,15 @@ LPGP_HD void eval_entries(const DevDesc* __restrict__ desc,
         double v = a * dx[j][e];
         sg[j][e] = lpgp_hi32(v) & 0x80000000u;
         r[j][e] = fabs(v);
+      }
+      if constexpr (VAR == EV_COMPACT) {
+        if (ek_kind(kind) == EK_COMPACT) {
+          // a Wendland dimension: (1 - r)^pow inside the support (r <= 1), no exponential; outside, the select below
+#pragma unroll
+          for (int e = 0; e < AE; ++e) inside[e] = inside[e] && r[j][e] <= 1.0;
+          lpgp_pow_1m<AE>(r[j], ek_pow(kind), ef);
+          continue;
+        }
       }
       if (Fac::enabled && kind == 1) {
 #pragma unroll
@@ -366,7 +408,23 @@ LPGP_HD void eval_entries(const DevDesc* __restrict__ desc,
         tot[e] += v;
       }
     }
-    if (per_entry_exp) {
+    if constexpr (VAR == EV_COMPACT) {
+      // outside the support the group contributes nothing: a select, so that no (possibly negative or non-finite) power
+      // of 1 - r > 1 ever meets the polynomial
+      if (per_entry_exp) {
+#pragma unroll
+        for (int e = 0; e < AE; ++e) {
+          const double v = fma(G.scale * (ef[e] * lpgp_exp_neg(expo[e], tab)), tot[e], res[e]);
+          res[e] = inside[e] ? v : res[e];
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < AE; ++e) {
+          const double v = fma(G.scale * ef[e], tot[e], res[e]);
+          res[e] = inside[e] ? v : res[e];
+        }
+      }
+    } else if (per_entry_exp) {
 #pragma unroll
       for (int e = 0; e < AE; ++e) res[e] = fma(G.scale * (ef[e] * lpgp_exp_neg(expo[e], tab)), tot[e], res[e]);
     } else {
@@ -385,7 +443,55 @@ LPGP_HD void eval_entries(const DevDesc* __restrict__ desc, const double (&dx)[D
 // the same for a descriptor that may hold radial Matern groups
 template <int D, int NE = AE>
 LPGP_HD void eval_entries_radial(const DevDesc* __restrict__ desc, const double (&dx)[D][NE], double (&res)[NE], const ExpTab& tab) {
-  eval_entries<D, NE, NoFactors, MemCoef, true>(desc, dx, res, NoFactors(), MemCoef{desc->coef}, tab);
+  eval_entries<D, NE, NoFactors, MemCoef, EV_RADIAL>(desc, dx, res, NoFactors(), MemCoef{desc->coef}, tab);
+}
+
+// the same for a descriptor of any kind, Wendland groups included
+template <int D, int NE = AE>
+LPGP_HD void eval_entries_compact(const DevDesc* __restrict__ desc, const double (&dx)[D][NE], double (&res)[NE], const ExpTab& tab) {
+  eval_entries<D, NE, NoFactors, MemCoef, EV_COMPACT>(desc, dx, res, NoFactors(), MemCoef{desc->coef}, tab);
+}
+
+// by variant (the generic kernels of assemble.hip)
+template <int VAR, int D, int NE>
+LPGP_HD void eval_entries_var(const DevDesc* __restrict__ desc, const double (&dx)[D][NE], double (&res)[NE], const ExpTab& tab) {
+  eval_entries<D, NE, NoFactors, MemCoef, VAR>(desc, dx, res, NoFactors(), MemCoef{desc->coef}, tab);
+}
+
+// Can NO entry between a row point in the box [rmin, rmax] and a column point in the box [cmin, cmax] lie inside the support of
+// any group?  True only if every group is compact and out of reach: a product-form group through one Wendland dimension with
+// a_j gap_j > 1, an isotropic Wendland group through sum_j (a_j gap_j)^2 > 1, gap_j the distance between the two intervals.
+// The decision runs the operations of the entries themselves -- a difference of two coordinates, the product with a_j, the
+// same fma chain, the same comparison -- on arguments that bound every entry's from below; rounding is monotone, so the decision
+// implies the per-entry selects above and a block is bit-identical with and without the shortcut.
+template <int D>
+LPGP_HD bool lpgp_out_of_reach(const DevDesc* __restrict__ desc, const double (&rmin)[D], const double (&rmax)[D], const double (&cmin)[D],
+                               const double (&cmax)[D]) {
+  double gap[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) gap[j] = fmax(fmax(rmin[j] - cmax[j], cmin[j] - rmax[j]), 0.0);
+  bool out = true;
+  for (int g = 0; g < desc->ngroups; ++g) {
+    const DevGroup& G = desc->g[g];
+    bool far = false;
+    if (G.iso) {
+      if (G.iso == 1 && ek_kind(G.expkind[0]) == EK_COMPACT) {
+        double s2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+          const double u = G.a[j] * gap[j];
+          s2 = fma(u, u, s2);
+        }
+        far = !(s2 <= 1.0);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < D; ++j)
+        if (ek_kind(G.expkind[j]) == EK_COMPACT && !(fabs(G.a[j] * gap[j]) <= 1.0)) far = true;
+    }
+    out = out && far;
+  }
+  return out;
 }
 
 }  // namespace lpgp

@@ -288,6 +288,188 @@ static int lower_radial_group(const lpgp_kdesc& K, int d, DevGroup& G, double* c
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// Wendland's compactly supported functions (Wendland 2004, Def. 9.11, Thm. 9.12-9.13): phi_{d,k} = I^k (1 - r)_+^l,
+// l = floor(d / 2) + k + 1, (I f)(r) = int_r^1 t f(t) dt, normalised to phi(0) = 1.  Everything below is exact integer
+// arithmetic: W.num is an integer polynomial in r proportional to phi on [0, 1] (content removed), phi = num / num[0].
+// With m = l + k,  d^n phi / dr^n = (1 - r)^{m - n} q_n(r),  deg q_n <= k: the division by (1 - r)^{m - n} is synthetic and
+// must leave no remainder.  Expanded in powers of r phi has large alternating coefficients (they sum to 11 669 in absolute
+// value for d = 4, k = 3); q_0 has positive ones only, which is why the device evaluates the factored form.
+// ---------------------------------------------------------------------------------------
+typedef __int128 wint;
+constexpr int WEND_MAXK = 3;
+constexpr int WEND_N = 24;          // coefficients of any polynomial below (degree l + 2 k <= 12 for d <= 4, k <= 3)
+
+static wint wgcd(wint a, wint b) {
+  if (a < 0) a = -a;
+  if (b < 0) b = -b;
+  while (b != 0) { const wint t = a % b; a = b; b = t; }
+  return a;
+}
+
+struct Wendland {
+  int l, k, m, deg;
+  wint num[WEND_N];
+};
+
+static void wendland_build(int dim, int k, Wendland& W) {
+  W.l = dim / 2 + k + 1;
+  W.k = k;
+  W.m = W.l + k;
+  for (int i = 0; i < WEND_N; ++i) W.num[i] = 0;
+  // (1 - r)^l
+  W.num[0] = 1;
+  W.deg = 0;
+  for (int it = 0; it < W.l; ++it) {
+    for (int i = W.deg + 1; i >= 1; --i) W.num[i] -= W.num[i - 1];
+    ++W.deg;
+  }
+  for (int it = 0; it < k; ++it) {
+    // L * int_r^1 t f(t) dt = sum_j c_j (L / (j + 2)) (1 - r^{j + 2}),  L = lcm(2 .. deg + 2)
+    wint L = 1;
+    for (int j = 2; j <= W.deg + 2; ++j) L = L / wgcd(L, j) * j;
+    wint nxt[WEND_N];
+    for (int i = 0; i < WEND_N; ++i) nxt[i] = 0;
+    for (int j = 0; j <= W.deg; ++j) {
+      const wint c = W.num[j] * (L / (j + 2));
+      nxt[0] += c;
+      nxt[j + 2] -= c;
+    }
+    W.deg += 2;
+    wint g = 0;
+    for (int i = 0; i <= W.deg; ++i) g = wgcd(g, nxt[i]);
+    for (int i = 0; i < WEND_N; ++i) W.num[i] = g != 0 ? nxt[i] / g : nxt[i];
+  }
+}
+
+// q (k + 1 + extra integers over the denominator W.num[0]) = (1 - r)^extra * q_n(r),  d^n phi / dr^n = (1 - r)^{m - n} q_n(r);
+// n <= m.  false: the division left a remainder (never, by Thm. 9.12: an internal error).
+static bool wendland_q(const Wendland& W, int n, int extra, wint* q /* WEND_N */) {
+  wint cur[WEND_N];
+  int deg = W.deg;
+  for (int i = 0; i < WEND_N; ++i) cur[i] = W.num[i];
+  for (int it = 0; it < n; ++it) {
+    for (int i = 0; i < deg; ++i) cur[i] = (i + 1) * cur[i + 1];
+    cur[deg] = 0;
+    if (deg > 0) --deg;
+  }
+  for (int it = 0; it < W.m - n; ++it) {
+    // cur = (1 - r) Q:  Q_0 = cur_0, Q_i = cur_i + Q_{i-1}, and cur_deg + Q_{deg-1} = 0
+    for (int i = 1; i <= deg; ++i) cur[i] += cur[i - 1];
+    if (cur[deg] != 0) return false;
+    if (deg > 0) --deg;
+  }
+  for (int it = 0; it < extra; ++it) {
+    for (int i = deg + 1; i >= 1; --i) cur[i] -= cur[i - 1];
+    ++deg;
+  }
+  for (int i = 0; i < WEND_N; ++i) q[i] = cur[i];
+  return true;
+}
+
+// Isotropic Wendland with at most one derivative per argument: the algebra of lower_iso_group with phi in place of kappa.  With
+// u = a .* (x - x'), s = |u|:   d/dx_i phi = a_i u_i phi'/s = -d/dx'_i phi,
+//   d/dx_i d/dx'_j phi = -[ a_i a_j u_i u_j (phi'' - phi'/s)/s^2 + a_i^2 delta_ij phi'/s ],
+// phi^(n) = (1 - s)^{m - n} q_n(s).  phi'/s is a polynomial times a power of (1 - s) for k >= 1 (q_1(0) = 0) and
+// (phi'' - phi'/s)/s^2 for k >= 2 (the odd coefficients of phi below 2 k + 1 vanish); both divisions are checked to be exact.
+// With o = the highest total order of a term (0, 1 or 2) the group multiplies by (1 - s)^{m - o} and keeps
+//   Q0 = c00 (1 - s)^o q_0 - tr (1 - s)^{o - 1} q_1/s,   Q1 = (1 - s)^{o - 1} q_1/s,   Q2 = -(q_2 - (1 - s) q_1/s)/s^2,
+// so a group without derivatives is the factored form (1 - s)^m q_0(s) itself, with the positive coefficients of q_0.
+static int lower_wendland_iso_group(const lpgp_kdesc& K, int d, DevGroup& G, double* coef, int& coef_used) {
+  LPGP_CHECK(K.dlog_lengthscale == 0,
+             "lower_kdesc: the derivative with respect to a lengthscale is not implemented for the Wendland families (LPGP_WENDLAND_ISO)");
+  const int k = K.p[0];
+  LPGP_CHECK(k >= 0 && k <= WEND_MAXK, "lower_kdesc: Wendland k=%d unsupported (0 .. %d)", k, WEND_MAXK);
+  LPGP_CHECK(d >= 2, "lower_kdesc: LPGP_WENDLAND_ISO needs d >= 2 (d = 1 is the product-form family LPGP_WENDLAND)");
+  long double a[LPGP_MAXD];
+  for (int j = 0; j < d; ++j) {
+    LPGP_CHECK(K.family[j] == LPGP_WENDLAND_ISO && K.p[j] == k, "lower_kdesc: an isotropic Wendland spans all dimensions with one k");
+    LPGP_CHECK(K.lengthscale[j] > 0, "lower_kdesc: lengthscale must be positive");
+    const double as = 1.0 / K.lengthscale[j];
+    a[j] = as;
+    G.a[j] = as;
+    G.deg[j] = 0;
+  }
+  G.iso = 1;
+  long double c00 = 0, tr = 0, w[LPGP_MAXD] = {0, 0, 0, 0}, B[LPGP_MAXD][LPGP_MAXD] = {};
+  bool first = false, second = false;
+  int omax = 0;
+  for (int t = 0; t < K.nterms; ++t) {
+    const lpgp_term& T = K.terms[t];
+    int i0 = -1, i1 = -1, o0 = 0, o1 = 0;
+    for (int j = 0; j < d; ++j) {
+      LPGP_CHECK(T.n0[j] >= 0 && T.n1[j] >= 0, "lower_kdesc: derivative order out of range");
+      o0 += T.n0[j];
+      o1 += T.n1[j];
+      if (T.n0[j]) i0 = j;
+      if (T.n1[j]) i1 = j;
+    }
+    LPGP_CHECK(o0 <= 1 && o1 <= 1,
+               "lower_kdesc: the isotropic Wendland has closed forms for identity and directional derivatives only");
+    LPGP_CHECK(o0 + o1 == 0 || k >= 1, "lower_kdesc: the Wendland function with k = 0 is not differentiable");
+    LPGP_CHECK(o0 + o1 < 2 || k >= 2,
+               "lower_kdesc: an isotropic Wendland with k = 1 takes no derivative on both arguments (its form carries a 1/s term)");
+    if (T.coef == 0.0) continue;
+    if (o0 + o1 > omax) omax = o0 + o1;
+    if (!o0 && !o1) c00 += T.coef;
+    else if (o0 && !o1) { w[i0] += T.coef * a[i0]; first = true; }
+    else if (!o0 && o1) { w[i1] -= T.coef * a[i1]; first = true; }
+    else {
+      B[i0][i1] += T.coef * a[i0] * a[i1];
+      if (i0 == i1) tr += T.coef * a[i0] * a[i0];
+      second = true;
+    }
+  }
+  Wendland W;
+  wendland_build(d, k, W);
+  const int o = omax;
+  const int deg = k + o;
+  wint q0[WEND_N], q1s[WEND_N], q2s[WEND_N], q1s_lo[WEND_N];
+  for (int i = 0; i < WEND_N; ++i) q1s[i] = q2s[i] = q1s_lo[i] = 0;
+  LPGP_CHECK(wendland_q(W, 0, o, q0), "lower_kdesc: internal error, phi_{%d,%d} is not divisible by its power of (1 - r)", d, k);
+  if (o >= 1) {
+    wint q1[WEND_N];
+    // (1 - s)^{o - 1} q_1 / s
+    LPGP_CHECK(wendland_q(W, 1, o - 1, q1) && q1[0] == 0, "lower_kdesc: internal error, phi'_{%d,%d}/s is no polynomial", d, k);
+    for (int i = 0; i + 1 < WEND_N; ++i) q1s[i] = q1[i + 1];
+  }
+  if (o >= 2) {
+    wint q1[WEND_N], q2[WEND_N];
+    // q_2 - (1 - s) q_1 / s, divided by s^2
+    LPGP_CHECK(wendland_q(W, 1, 1, q1) && q1[0] == 0 && wendland_q(W, 2, 0, q2), "lower_kdesc: internal error in the Wendland tables");
+    for (int i = 0; i + 1 < WEND_N; ++i) q2[i] -= q1[i + 1];
+    LPGP_CHECK(q2[0] == 0 && q2[1] == 0, "lower_kdesc: internal error, (phi'' - phi'/s)/s^2 of phi_{%d,%d} is no polynomial", d, k);
+    for (int i = 0; i + 2 < WEND_N; ++i) q2s[i] = -q2[i + 2];
+  }
+  G.deg[0] = deg;
+  for (int j = 0; j < d; ++j) G.expkind[j] = ek_compact(W.m - o);
+  LPGP_CHECK(coef_used + 3 * (deg + 1) <= MAXCOEF, "lower_kdesc: coefficient table overflow");
+  double* Q0 = coef + coef_used;
+  double* Q1 = Q0 + (deg + 1);
+  double* Q2 = Q1 + (deg + 1);
+  const long double den = (long double)W.num[0];
+  for (int i = 0; i <= deg; ++i) {
+    Q0[i] = (double)((c00 * (long double)q0[i] - tr * (long double)q1s[i]) / den);
+    Q1[i] = (double)((long double)q1s[i] / den);
+    Q2[i] = (double)((long double)q2s[i] / den);
+  }
+  for (int i = deg + 1; i < WEND_N; ++i)
+    LPGP_CHECK(q0[i] == 0 && q1s[i] == 0 && q2s[i] == 0, "lower_kdesc: internal error, a Wendland polynomial of degree above %d", deg);
+  G.ncls = 3;
+  G.parity[0] = 0; G.parity[1] = 1; G.parity[2] = 1;
+  G.coef_off[0] = coef_used;
+  G.coef_off[1] = coef_used + (deg + 1);
+  G.coef_off[2] = coef_used + 2 * (deg + 1);
+  coef_used += 3 * (deg + 1);
+  G.has_lin = first ? 1 : 0;
+  G.has_quad = second ? 1 : 0;
+  for (int i = 0; i < LPGP_MAXD; ++i) {
+    G.w[i] = (double)w[i];
+    for (int j = 0; j < LPGP_MAXD; ++j) G.B[i * LPGP_MAXD + j] = (double)(0.5L * (B[i][j] + B[j][i]));
+  }
+  return 0;
+}
+
 // d / d log lengthscale of one Matern factor of total order n (lpgp_kdesc::dlog_lengthscale).  The factor a^n e^{-r} P_n(r),
 // r = a |x - x'|, depends on the lengthscale through a ~ 1 / lengthscale alone, and
 //   d/d log a [a^n e^{-r} P_n(r)] = a^n e^{-r} [n P_n(r) + r (P_n' - P_n)(r)] = a^n e^{-r} [n P_n(r) + r P_{n+1}(r)]:
@@ -351,13 +533,38 @@ int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out) {
       if (rc != 0) return rc;
       continue;
     }
+    if (K.family[0] == LPGP_WENDLAND_ISO) {
+      int rc = lower_wendland_iso_group(K, d, G, out->coef, coef_used);
+      if (rc != 0) return rc;
+      continue;
+    }
     LPGP_CHECK(K.dlog_lengthscale >= 0 && K.dlog_lengthscale <= d, "lower_kdesc: dlog_lengthscale=%d out of range (0 .. d=%d)",
                K.dlog_lengthscale, d);
     const int jd = K.dlog_lengthscale - 1;       // the dimension whose factor is differentiated by its log lengthscale (-1: none)
     long double a[LPGP_MAXD];
+    // Wendland dimensions (LPGP_WENDLAND): a term of total order n = n0 + n1 <= 2 k contributes
+    //   a^n (-1)^{n1} sign(x - x')^n (1 - r)^{m - n} q_n(r),   r = a |x - x'|, a = 1 / lengthscale, m = l + k = 2 k + 1;
+    // the group multiplies by the common power (1 - r)_+^{m - nmax} (nmax: the highest order of the dimension over the terms)
+    // and the coefficient tensor keeps (1 - r)^{nmax - n} q_n(r), of degree <= k + nmax <= 9
+    Wendland wend[LPGP_MAXD];
+    int wmax[LPGP_MAXD] = {0, 0, 0, 0};
     for (int j = 0; j < d; ++j) {
       LPGP_CHECK(K.lengthscale[j] > 0, "lower_kdesc: lengthscale must be positive");
-      if (K.family[j] == LPGP_MATERN_HALFINT) {
+      if (K.family[j] == LPGP_WENDLAND) {
+        LPGP_CHECK(K.dlog_lengthscale == 0,
+                   "lower_kdesc: the derivative with respect to a lengthscale is not implemented for the Wendland families (LPGP_WENDLAND)");
+        LPGP_CHECK(K.p[j] >= 0 && K.p[j] <= WEND_MAXK, "lower_kdesc: Wendland k=%d unsupported (0 .. %d)", K.p[j], WEND_MAXK);
+        wendland_build(1, K.p[j], wend[j]);
+        for (int t = 0; t < K.nterms; ++t) {
+          const int n0 = K.terms[t].n0[j], n1 = K.terms[t].n1[j];
+          LPGP_CHECK(n0 >= 0 && n1 >= 0, "lower_kdesc: derivative order out of range");
+          LPGP_CHECK(n0 + n1 <= 2 * K.p[j], "lower_kdesc: a Wendland factor with k = %d is not %d times differentiable (at most 2 k)",
+                     K.p[j], n0 + n1);
+          if (n0 + n1 > wmax[j]) wmax[j] = n0 + n1;
+        }
+        a[j] = 1.0 / K.lengthscale[j];
+        G.expkind[j] = ek_compact(wend[j].m - wmax[j]);
+      } else if (K.family[j] == LPGP_MATERN_HALFINT) {
         LPGP_CHECK(K.p[j] >= 0 && K.p[j] <= 6, "lower_kdesc: Matern p=%d unsupported", K.p[j]);
         // probnum Matern._scale_factors = sqrt(2 nu) / lengthscale, in fp64 like the reference
         double as = std::sqrt(2.0 * (K.p[j] + 0.5)) / K.lengthscale[j];
@@ -379,6 +586,7 @@ int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out) {
         LPGP_CHECK(K.terms[t].n0[j] >= 0 && K.terms[t].n1[j] >= 0 && n <= 12,
                    "lower_kdesc: derivative order out of range");
         int dg = (K.family[j] == LPGP_MATERN_HALFINT) ? K.p[j] : n;
+        if (K.family[j] == LPGP_WENDLAND) dg = K.p[j] + wmax[j] - n;
         if (j == jd) dg += (K.family[j] == LPGP_MATERN_HALFINT) ? 1 : 2;
         if (dg > deg) deg = dg;
       }
@@ -398,7 +606,14 @@ int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out) {
         int n = T.n0[j] + T.n1[j];
         if (n & 1) parity |= (1 << j);
         pref *= std::pow(a[j], n);
-        if (K.family[j] == LPGP_MATERN_HALFINT) {
+        if (K.family[j] == LPGP_WENDLAND) {
+          if (T.n1[j] & 1) pref = -pref;
+          wint qi[WEND_N];
+          LPGP_CHECK(wendland_q(wend[j], n, wmax[j] - n, qi), "lower_kdesc: internal error, phi_{1,%d}^(%d) is not divisible by its power of (1 - r)",
+                     K.p[j], n);
+          qdeg[j] = K.p[j] + wmax[j] - n;
+          for (int i = 0; i <= qdeg[j]; ++i) q[j][i] = (long double)qi[i] / (long double)wend[j].num[0];
+        } else if (K.family[j] == LPGP_MATERN_HALFINT) {
           if (T.n1[j] & 1) pref = -pref;
           if (j == jd) matern_poly_dlog(K.p[j], n, q[j]);
           else matern_poly(K.p[j], n, q[j]);
@@ -456,6 +671,13 @@ double desc_diag(const DevDesc& desc) {
   return v;
 }
 
+bool desc_has_compact(const DevDesc& desc) {
+  for (int g = 0; g < desc.ngroups; ++g)
+    for (int j = 0; j < desc.d; ++j)
+      if (ek_kind(desc.g[g].expkind[j]) == EK_COMPACT) return true;
+  return false;
+}
+
 bool desc_has_radial(const DevDesc& desc) {
   for (int g = 0; g < desc.ngroups; ++g)
     if (desc.g[g].iso == 2) return true;
@@ -472,6 +694,7 @@ int desc_coef_used(const DevDesc& desc) {
       if (end > ncoef) ncoef = end;
       continue;
     }
+    // (product form: a dense tensor per class; the isotropic Matern and Wendland groups: three polynomials of degree deg[0], deg[1..] = 0)
     for (int c = 0; c < G.ncls; ++c) {
       int len = 1;
       for (int dd = 0; dd < desc.d; ++dd) len *= G.deg[dd] + 1;

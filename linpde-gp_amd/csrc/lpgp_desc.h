@@ -27,7 +27,8 @@ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 // ---- lowered kernel descriptor (device form) ------------------------------------------
 // entry = sum_g scale_g * exp(-sum_d E_d(r_d)) * sum_c sgn^{parity_c} Poly_c(r_1..r_d),
 // r_d = |a_d (x_d - x'_d)|, E = r (Matern) or r^2/2 (ExpQuad); Poly_c dense nested-Horner
-// coefficient tensor.  Built on the host by lower_kdesc (lower.cpp).
+// coefficient tensor.  Built on the host by lower_kdesc (lower.cpp).  A Wendland dimension (expkind 3) replaces its exponential
+// by (1 - r_d)_+^{pow_d}: an integer power inside the support, a select of exactly 0.0 outside.
 constexpr int MAXCLS = 16;         // parity classes (2^d, d <= 4)
 constexpr int RAD_M = 5;           // radial Matern group: psi^(0) .. psi^(4)
 constexpr int RAD_NEG = 3;         // ... negative powers of s a Theta_m may carry (p >= 2, m <= 4: at most s^-3)
@@ -36,7 +37,9 @@ constexpr int MAXCOEF = 8192;      // coefficient doubles over all groups (only 
 struct DevGroup {
   double scale;
   double a[LPGP_MAXD];
-  int32_t expkind[LPGP_MAXD];      // 1: exp(-r), 2: exp(-r^2/2)
+  int32_t expkind[LPGP_MAXD];      // 1: exp(-r), 2: exp(-r^2/2); low byte 3: (1 - r)_+^pow (Wendland; the COMPACT instantiations only) with the
+                                   // integer power in the bits above it -- ek_kind / ek_pow below.  (The power shares the word because the size of
+                                   // this struct and the bytes of every descriptor without a Wendland group are pinned: tests/golden/lowering_c1_c3.npz.)
   int32_t deg[LPGP_MAXD];          // polynomial degree per dim
   int32_t ncls;
   int32_t parity[MAXCLS];          // bit d set => factor sign(x_d - x'_d)
@@ -53,10 +56,19 @@ struct DevGroup {
   // coef_off[1]: the monomials of Pi_0, Pi_1, .., Pi_4 one after another, parity[1 + m] of them for Pi_m, two doubles each: the
   //   coefficient, and a double whose low 32 bits hold the exponents of u_0..u_3, three bits each (a sparse list: 6 monomials
   //   for a pair of Laplacians in 2-D, 15 in 4-D, against 5^d coefficients per m of a dense tensor).
+  // isotropic Wendland group (LPGP_WENDLAND_ISO): iso == 1 with expkind[.] == 3, the same three polynomials and
+  //   entry = scale * (1 - s)_+^{ek_pow(expkind[0])} * [ Q0(s) + (w . u) Q1(s) + (u^T B u) Q2(s) ]   (inside: s^2 <= 1)
   int32_t iso, has_lin, has_quad;
   double w[LPGP_MAXD];
   double B[LPGP_MAXD * LPGP_MAXD];
 };
+
+// DevGroup::expkind of a Wendland dimension: kind 3 and the integer power of (1 - r) the group multiplies by (>= 1 for a product-form
+// dimension, >= 0 for an isotropic group, which carries it in every dimension)
+constexpr int EK_COMPACT = 3;
+constexpr int32_t ek_compact(int pow) { return (int32_t)(EK_COMPACT | (pow << 8)); }
+constexpr int ek_kind(int32_t e) { return e & 0xff; }
+constexpr int ek_pow(int32_t e) { return e >> 8; }
 
 struct DevDesc {
   int32_t d;
@@ -70,6 +82,8 @@ constexpr int rad_theta_len(int p) { return p + 1 + RAD_NEG; }
 int lower_kdesc(const lpgp_kdesc* kd, int ngroups, DevDesc* out);
 // does the lowered descriptor hold a radial Matern group (iso == 2)?  Those are evaluated by the RADIAL instantiations only.
 bool desc_has_radial(const DevDesc& desc);
+// does it hold a Wendland dimension or an isotropic Wendland group (expkind 3)?  Those are evaluated by the COMPACT instantiations only.
+bool desc_has_compact(const DevDesc& desc);
 // doubles of the coefficient table the descriptor uses (what travels to the device)
 int desc_coef_used(const DevDesc& desc);
 // The pair list and the weight counts of lpgp_gram_assemble_weighted / lpgp_cross_assemble_weighted (`fn`: the name in the

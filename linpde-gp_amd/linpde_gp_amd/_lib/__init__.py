@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("LPGP_LIB", os.path.join(_HERE, "liblpgp.so"))     # $
 MAXD, MAXT, MAXG = 4, 256, 16
 MAXW = 4            # LPGP_MAXW: coefficient functions per variable-coefficient operator
 MATERN_HALFINT, EXPQUAD, MATERN_ISO, MATERN_RADIAL = 1, 2, 3, 4
+WENDLAND, WENDLAND_ISO = 5, 6     # compactly supported Wendland functions: univariate product-form factor / isotropic over all d
 K_ASSEMBLE, K_SYRK, K_GEMM, K_POTRF_TILE, K_TRSM, K_COUNT = 0, 1, 2, 3, 4, 5
 KERNEL_NAMES = ("assemble", "syrk_trailing", "gemm", "potrf_tile", "trsm_gemm", "syrk_panel", "gemm_small", "matvec", "syrk_lookahead",
                 "assemble_grid", "panel_fused", "comm", "trmm")

@@ -985,7 +985,7 @@ class ConditionalGaussianProcess(GaussianProcess):
         (`lpgp_mat_evidence_grad`); a diagonal noise needs no matrix (`lpgp_mat_evidence_grad_diag`).  Three n x n matrices are
         alive at most.  An earlier posterior of a chain answers for its own blocks; flushes, verifies and raises as
         `log_marginal_likelihood`.  An isotropic multivariate Matern prior raises `NotImplementedError` (no closed form of its
-        lengthscale derivative here; use a `TensorProduct` prior)."""
+        lengthscale derivative here; use a `TensorProduct` prior), and so does a prior with a Wendland summand."""
         if _has_variable(self._blocks):
             raise NotImplementedError(f"`log_marginal_likelihood_gradient` is not available on a chain with {_VARIABLE} yet")
         base = self._prior.cov
@@ -997,6 +997,9 @@ class ConditionalGaussianProcess(GaussianProcess):
         if any(f[0][0] == covfuncs.MATERN_ISO for _, f in base_groups):
             raise NotImplementedError("`log_marginal_likelihood_gradient` is not available for the isotropic multivariate Matérn kernel "
                                       "(its lengthscale derivative has no closed form here); use a `TensorProduct` prior")
+        if any(f[0] in (covfuncs.WENDLAND, covfuncs.WENDLAND_ISO) for _, fs in base_groups for f in fs):
+            raise NotImplementedError("`log_marginal_likelihood_gradient` is not available for a prior with a Wendland summand "
+                                      "(the lengthscale derivative of the Wendland families is not built)")
         self._check_current()
         mat = self._state.mat
         r = self._residual()

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..._lib import EXPQUAD, MATERN_HALFINT, MATERN_ISO, MATERN_RADIAL, MAXD, MAXG, MAXT
+from ..._lib import EXPQUAD, MATERN_HALFINT, MATERN_ISO, MATERN_RADIAL, MAXD, MAXG, MAXT, WENDLAND, WENDLAND_ISO
 
 
 def _as_shape(shape):
@@ -209,6 +209,52 @@ class ExpQuad(CovarianceFunction):
 
     def _base_groups(self):
         return [(1.0, [(EXPQUAD, 0, float(l)) for l in self._lengthscales])]
+
+
+class WendlandCovarianceFunction(CovarianceFunction):
+    """Compactly supported radial kernel k = phi_{d,k}(||(x - x') / lengthscales||) with Wendland's piecewise polynomial
+    phi_{d,k} (Wendland 2004, Def. 9.11; `covfuncs/_wendland.py`): exactly zero beyond the support radius, 2k times
+    continuously differentiable.  Gram matrices are sparse; tiles whose points are out of each other's reach are not evaluated.
+
+    input_shape () or (1,): the univariate phi_{1,k}, every derivative order up to 2k, and a `TensorProduct` factor (Laplacians,
+    the heat operator, `VariableCoefficientOperator`s on a tensor product of Wendland factors, alone or beside Matérn factors).
+    input_shape (d,), 2 <= d <= 4: the isotropic phi_{d,k} (scalar or per-dimension lengthscales) with identity and directional
+    derivatives: none at k = 0, none on both arguments at k = 1.  The reference evaluates derivatives by JAX autodiff; here they
+    are exact closed forms, (1 - r)^e times a polynomial.  k = 0 .. 3."""
+
+    def __init__(self, input_shape, k, lengthscales=None):
+        super().__init__(input_shape)
+        d = max(self.input_size, 1)
+        if d > MAXD:
+            raise NotImplementedError(f"at most {MAXD} input dimensions are supported")
+        if int(k) != k or not 0 <= int(k) <= 3:
+            raise NotImplementedError("Wendland functions are built for k = 0, 1, 2, 3")
+        self._d = d
+        self._k = int(k)
+        self._lengthscales = np.asarray(lengthscales if lengthscales is not None else 1.0, dtype=np.double)
+        try:
+            ls = np.broadcast_to(self._lengthscales, (d,)).copy()
+        except ValueError:
+            raise ValueError(f"`lengthscales` must be a scalar or have shape ({d},)") from None
+        if not (ls > 0).all():
+            raise ValueError("`lengthscales` must be positive")
+        self._ls = ls
+
+    @property
+    def d(self):
+        return self._d
+
+    @property
+    def k(self):
+        return self._k
+
+    @property
+    def lengthscales(self):
+        return self._lengthscales
+
+    def _base_groups(self):
+        fam = WENDLAND_ISO if self._d > 1 else WENDLAND
+        return [(1.0, [(fam, self._k, float(l)) for l in self._ls])]
 
 
 class TensorProduct(CovarianceFunction):
@@ -458,7 +504,24 @@ def lower_groups(base_groups, L0: dict, L1: dict):
                         f"a multivariate Matérn-{p}+1/2 kernel does not admit {sum(a) + sum(b)} "
                         "derivative(s) in closed form (not enough differentiability)")
                 continue
+            if factors[0][0] == WENDLAND_ISO:
+                k, na, nb = factors[0][1], sum(a), sum(b)
+                if na > 1 or nb > 1:
+                    raise NotImplementedError(
+                        "the isotropic Wendland kernel has closed forms for identity and directional derivatives only; "
+                        "use a `TensorProduct` of univariate Wendland factors for higher-order operators")
+                if na + nb > 0 and k == 0:
+                    raise ValueError("the Wendland kernel with k = 0 is not differentiable")
+                if na + nb == 2 and k == 1:
+                    raise NotImplementedError(
+                        "a derivative on both arguments of the isotropic Wendland kernel with k = 1 is not built (its form "
+                        "carries a 1/s term); use k >= 2 or a `TensorProduct` of univariate Wendland factors")
+                continue
             for j, (fam, p, _) in enumerate(factors):
+                if fam == WENDLAND and a[j] + b[j] > 2 * p:
+                    raise ValueError(
+                        f"a Wendland factor with k = {p} is not {a[j] + b[j]} times differentiable (at most 2k); "
+                        "choose a smoother prior")
                 if fam == MATERN_HALFINT and a[j] + b[j] > 2 * p:
                     raise ValueError(
                         f"a Matérn-{p}+1/2 factor is not {a[j] + b[j]} times differentiable "
@@ -559,7 +622,7 @@ def _base(k: CovarianceFunction) -> CovarianceFunction:
 
 
 __all__ = [
-    "CovarianceFunction", "Matern", "ExpQuad", "TensorProduct", "ScaledCovarianceFunction",
+    "CovarianceFunction", "Matern", "ExpQuad", "WendlandCovarianceFunction", "TensorProduct", "ScaledCovarianceFunction",
     "SumCovarianceFunction", "Zero", "DifferentiatedCovarianceFunction",
     "ProcessVectorCrossCovariance", "apply_linfuncop", "apply_linfunctl_to_pv_crosscov", "lower_groups",
 ]
