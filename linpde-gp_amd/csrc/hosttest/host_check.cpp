@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../eval_entries.h"
+#include "host_factors.h"
 #include "../options.h"
 
 using namespace lpgp;
@@ -29,24 +30,7 @@ static void eval_block(const DevDesc& desc, const double* X0, int64_t n0, const 
     }
 }
 
-// The factored evaluation (eval_entries.h: `Fac`; on the device the per-point factors sit in LDS, assemble.hip:
-// LdsFactors): per-point exponentials e^{-+ a (x - x0)} of every Matern dimension relative to the first column point
-// of the 8-column strip, the per-entry exponential as the minimum of the two products -- the SAME eval_entries code path.
-template <int D>
-struct HostFactors {
-  static constexpr bool enabled = true;
-  const DevDesc* desc;
-  double xr[D], xc[D][AE], x0[D];
-  double pair(int g, int j, int e) const {
-    const double a = desc->g[g].a[j];
-    double rp, rm, cp, cm, t;
-    lpgp_exp_factors(a, xr[j], x0[j], rp, rm, t);
-    lpgp_exp_factors(a, xc[j][e], x0[j], cp, cm, t);
-    const double p1 = rp * cm, p2 = rm * cp;
-    return p1 < p2 ? p1 : p2;
-  }
-};
-
+// The factored evaluation: HostFactors (host_factors.h) relative to the first column point of the 8-column strip.
 template <int D>
 static void eval_block_fact(const DevDesc& desc, const double* X0, int64_t n0, const double* X1, int64_t n1, double* out) {
   for (int64_t i = 0; i < n0; ++i)

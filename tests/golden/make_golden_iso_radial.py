@@ -19,7 +19,17 @@
       points under -Lap (f = 2 pi^2 sin pi x sin pi y), then 32 boundary values 0 with a 1e-8 nugget, 20 prediction points;
       Gram matrix, Cholesky solve, mean and variance in 50-digit mpmath (as make_golden_multiblock.py).
 
-Run:  python tests/golden/make_golden_iso_radial.py      (a few minutes)
+  iso_first.npz
+    First-order operators on the same kernel (the isotropic group of the first-order lowering, `LPGP_MATERN_ISO`: value, directional
+    derivative and the mixed u^T B u term), by the same machinery: SymPy derivatives in mpmath, the all-summands-absolute envelope of
+    the closed form, the same 24 x 24 planted point layout (an own seed, so that iso_radial.npz does not change).
+      cases      d in {2, 3}  x  nu in {3/2, 5/2, 7/2}, anisotropic lengthscales; nu = 1/2 for id_id only, nu = 3/2 without grad_grad
+                 and mix (a derivative on both arguments: the lowering refuses it there)                       tag  d{d}_nu{2 nu}2
+      operators  id_id, grad_id (<v, grad> on the first argument), id_grad (<w, grad'> on the second), grad_grad (<v, grad>,
+                 <w, grad'>, v != w: the matrix B of the mixed term is not symmetric), mix (c + <v, grad> on both arguments)
+      {tag}_{op}    the block (float64),  {tag}_{op}_E  its envelope, float32 rounded UP (an upper bound needs no more digits)
+
+Run:  python tests/golden/make_golden_iso_radial.py [iso_radial | iso_first]     (a few minutes each; no argument: both)
 """
 import itertools
 import os
@@ -45,9 +55,9 @@ def matern_poly(p):
 
 
 class Kernel:
-    """All partial derivatives of f(delta) = kappa(|a .* delta|) up to total order 4, lambdified for mpmath."""
+    """All partial derivatives of f(delta) = kappa(|a .* delta|) up to total order `order`, lambdified for mpmath."""
 
-    def __init__(self, d, p, ls):
+    def __init__(self, d, p, ls, order=4):
         self.d, self.p = d, p
         self.ls = [sp.Rational(str(l)) for l in ls]
         self.a = [sp.sqrt(2 * p + 1) / l for l in self.ls]
@@ -55,7 +65,7 @@ class Kernel:
         s, P = matern_poly(p)
         r = sp.sqrt(sum((a * x) ** 2 for a, x in zip(self.a, dl)))
         f = (P * sp.exp(-s)).subs(s, r)
-        self.alphas = multi_indices(d, 4)
+        self.alphas = multi_indices(d, order)
         cache = {(0,) * d: f}
         for al in sorted(self.alphas, key=sum):
             if al in cache:
@@ -191,6 +201,57 @@ def kernel_case(d, p, ls, rng, out):
     print(f"{tag}: closed form vs SymPy, worst |diff| / E = {worst:.1e}", flush=True)
 
 
+def first_order_pairs(d):
+    z = (0,) * d
+
+    def e(i):
+        return tuple(1 if j == i else 0 for j in range(d))
+
+    v, w, c = (0.7, -0.4, 0.3)[:d], (-0.5, 0.9, 0.6)[:d], 1.5
+    ident = {z: 1.0}
+    gv, gw = {e(i): v[i] for i in range(d)}, {e(i): w[i] for i in range(d)}
+    mix = dict(gv)
+    mix[z] = c
+    return {"id_id": (ident, ident), "grad_id": (gv, ident), "id_grad": (ident, gw), "grad_grad": (gv, gw), "mix": (mix, mix)}, v, w, c
+
+
+def first_order_case(d, p, ls, rng, out):
+    """One (d, nu) case of iso_first.npz; nu = 1/2 (p = 0) is not differentiable: id_id only."""
+    tag = f"d{d}_nu{2 * p + 1}2"
+    K = Kernel(d, p, ls, order=2 if p else 0)
+    ops, v, w, c = first_order_pairs(d)
+    if p == 0:
+        ops = {"id_id": ops["id_id"]}
+    elif p == 1:                         # (the library admits p derivatives in all on the multivariate kernel, as the reference does)
+        ops = {name: ops[name] for name in ("id_id", "grad_id", "id_grad")}
+    X0, X1 = points(d, p, ls, rng)
+    out[f"{tag}_X0"], out[f"{tag}_X1"], out[f"{tag}_lengthscales"] = X0, X1, np.asarray(ls, dtype=float)
+    out[f"{tag}_v"], out[f"{tag}_w"], out[f"{tag}_c"] = np.asarray(v), np.asarray(w), c
+    blocks = {name: (np.zeros((24, 24)), np.zeros((24, 24), dtype=np.float32)) for name in ops}
+    worst = 0.0
+    for i in range(24):
+        for j in range(24):
+            dl = mpf_delta(X0[i], X1[j])
+            D = K.derivs(dl)
+            for name, (L0, L1) in ops.items():
+                terms = term_list(L0, L1)
+                g = sum(mpmath.mpf(c0) * (-1) ** sum(b) * D[tuple(x + y for x, y in zip(a, b))] for c0, a, b in terms)
+                cv, env = K.closed_form(dl, terms)
+                if env == 0:                     # (a directional derivative at coincident points: every summand vanishes)
+                    assert abs(g) < mpmath.mpf(10) ** -40, g
+                    g = mpmath.mpf(0)
+                else:
+                    worst = max(worst, float(abs(g - cv) / env))
+                blocks[name][0][i, j] = float(g)
+                e32 = np.float32(float(env))
+                blocks[name][1][i, j] = e32 if mpmath.mpf(float(e32)) >= env else np.nextafter(e32, np.float32(np.inf))
+    assert worst < 1e-40, worst
+    for name, (G, E) in blocks.items():
+        assert np.all(np.abs(G) <= E.astype(np.double))
+        out[f"{tag}_{name}"], out[f"{tag}_{name}_E"] = G, E
+    print(f"{tag} (first order): closed form vs SymPy, worst |diff| / E = {worst:.1e}", flush=True)
+
+
 def posterior(out):
     d, p, ls, scale = 2, 2, (0.6, 0.5), 1.5
     K = Kernel(d, p, ls)
@@ -250,7 +311,7 @@ def posterior(out):
     print(f"posterior: N = {N}, cond_2(G) = {cond:.2e}", flush=True)
 
 
-def main():
+def main_radial():
     out = {}
     rng = np.random.default_rng(20241017)
     for d, ls in ((2, (0.9, 0.6)), (3, (0.9, 0.6, 1.3))):
@@ -260,6 +321,26 @@ def main():
     path = os.path.join(HERE, "iso_radial.npz")
     np.savez_compressed(path, **out)
     print(f"wrote {path}: {os.path.getsize(path)} bytes")
+
+
+def main_first():
+    out = {}
+    rng = np.random.default_rng(20241019)
+    for d, ls in ((2, (0.9, 0.6)), (3, (0.9, 0.6, 1.3))):
+        for p in (0, 1, 2, 3):
+            first_order_case(d, p, ls, rng, out)
+    path = os.path.join(HERE, "iso_first.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path)} bytes")
+    assert os.path.getsize(path) <= os.path.getsize(os.path.join(HERE, "iso_radial.npz"))
+
+
+def main():
+    which = sys.argv[1:] or ["iso_radial", "iso_first"]
+    if "iso_radial" in which:
+        main_radial()
+    if "iso_first" in which:
+        main_first()
 
 
 if __name__ == "__main__":
