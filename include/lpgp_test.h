@@ -53,6 +53,12 @@ int  lpgp_probe_hbm_write(lpgp_ctx* ctx, int64_t bytes, double* gbps);
  * a resident kernel timed out): the error path of lpgp_mat_check without a broken device                          */
 int  lpgp_test_force_status(lpgp_ctx* ctx, lpgp_mat* mat, int32_t value);
 
+/* the forward half of the single-vector solve alone, z = L^{-1} r, as lpgp_mat_evidence runs it: r_host (logical order,
+ * lpgp_mat_size doubles) is staged into the padded layout with zeros in the padding rows, solved by the form the option
+ * trsv_resident selects (1: the resident kernel of trsv.hip, 0: one launch per tile row, potrf.hip), and z comes back in the
+ * PADDED layout (lpgp_mat_padded_size doubles).  A negative status word (a timed-out hand-over) is returned as an error.  */
+int  lpgp_test_solve_vec_fwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double* z_host_padded);
+
 #ifdef __cplusplus
 }
 #endif

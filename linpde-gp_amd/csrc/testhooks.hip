@@ -4,6 +4,8 @@
 // include/lpgp_test.h.  `nm -D liblpgp.so | grep -E "lpgp_(test|probe|debug)"` is empty.
 
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 
 #include "lpgp_internal.h"
 #include "lpgp_test.h"
@@ -230,6 +232,37 @@ int lpgp_test_force_status(lpgp_ctx* ctx, lpgp_mat* mat, int32_t value) {
   LPGP_HIP(hipMemcpy(mat->d_status, &value, sizeof(int), hipMemcpyHostToDevice));
   mat->unchecked = 1;
   mat->status_known = 0;
+  return 0;
+}
+
+// z = L^{-1} r, the forward half of the single-vector solve alone, as lpgp_mat_evidence runs it: r scattered into the padded layout
+// (zeros in the padding rows), the dispatch on ctx->trsv_resident (trsv.hip solve_vec_fwd_resident, else potrf.hip solve_vec_fwd),
+// z back in the padded layout (mat->pn doubles).  A negative status word (a timed-out hand-over) is a library error.
+int lpgp_test_solve_vec_fwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double* z_host_padded) {
+  LPGP_CHECK(ctx && mat && r_host && z_host_padded, "lpgp_test_solve_vec_fwd: null argument");
+  LPGP_DEVICE(ctx);
+  LPGP_MAT_ALIVE(mat, "lpgp_test_solve_vec_fwd");
+  LPGP_CHECK(!ctx->distributed(), "lpgp_test_solve_vec_fwd: single GPU only");
+  LPGP_CHECK(mat->pn > 0 && mat->pn_fact == mat->pn, "lpgp_test_solve_vec_fwd: matrix is not (fully) factored");
+  LPGP_CHECK(!mat->unchecked, "lpgp_test_solve_vec_fwd: the status of an enqueued factorisation has not been read (lpgp_mat_check)");
+  const int64_t pn = mat->pn, T = pn / TILE;
+  hipStream_t st = ctx->s_main;
+  std::vector<double> h((size_t)pn, 0.0);
+  int info = 0;
+  for (const auto& b : mat->blocks) std::memcpy(h.data() + b.poff, r_host + b.off, (size_t)b.n * sizeof(double));
+  // [r as staged | z + the ticket word of the resident solve]
+  DevBuf buf;
+  LPGP_TRY(DevBuf::raw((size_t)(2 * pn + 2) * sizeof(double), &buf));
+  double* const d = buf.as();
+  StreamDrain drain{st};                         // (the staging vector, the status word and the caller's array are borrowed by the copies)
+  LPGP_HIP(hipMemcpyAsync(d, h.data(), (size_t)pn * sizeof(double), hipMemcpyHostToDevice, st));
+  LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
+  if (ctx->trsv_resident) LPGP_TRY(solve_vec_fwd_resident(ctx, mat, T, d, d + pn, ctx->d_info));
+  else LPGP_TRY(solve_vec_fwd(ctx, st, mat, T, d, d + pn));
+  LPGP_HIP(hipMemcpyAsync(z_host_padded, d + pn, (size_t)pn * sizeof(double), hipMemcpyDeviceToHost, st));
+  LPGP_HIP(hipMemcpyAsync(&info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, st));
+  LPGP_TRY(drain.wait());
+  LPGP_CHECK(info >= 0, "lpgp_test_solve_vec_fwd: resident single-vector solve: a hand-over between workgroups timed out (status %d)", info);
   return 0;
 }
 

@@ -1,0 +1,82 @@
+"""Long-double references computed from a GIVEN lower-triangular factor L (float64 in, `np.longdouble` inside), for the suite
+that holds csrc/evidence.hip and the forward half of the single-vector solve to the device's own factor
+(test_gpu_evidence_backward.py): with L shared between the device and the reference the cond-bound error of the factorisation
+drops out and a measure sees the solve, the column sums, the reductions and the epilogue alone.  Checked against 50-digit
+mpmath in test_factor_reference.py.  A plain module the suites import, not a conftest."""
+import numpy as np
+
+LD = np.longdouble
+U = 2.0 ** -53
+HALF_LOG_2PI = LD(0.5) * np.log(LD(8) * np.arctan(LD(1)))      # 1/2 log 2 pi in long double
+
+
+def forward(L, r):
+    """z = L^{-1} r by rows: z_i = (r_i - sum_{j < i} L_ij z_j) / L_ii."""
+    n = L.shape[0]
+    z = np.zeros(n, dtype=LD)
+    rl = np.asarray(r).astype(LD)
+    for i in range(n):
+        z[i] = (rl[i] - L[i, :i].astype(LD) @ z[:i]) / LD(L[i, i])
+    return z
+
+
+def inverse(L):
+    """W = L^{-1} by rows (lower triangular): W[i, :i + 1] = (e_i - L[i, :i] W[:i, :i + 1]) / L_ii."""
+    n = L.shape[0]
+    W = np.zeros((n, n), dtype=LD)
+    for i in range(n):
+        row = -(L[i, :i].astype(LD) @ W[:i, :i + 1])
+        row[i] += LD(1)
+        W[i, :i + 1] = row / LD(L[i, i])
+    return W
+
+
+def inverse_diag(W):
+    """d_j = sum_i W_ij^2 = diag((L L^T)^{-1})_j for W = L^{-1}."""
+    return np.sum(W * W, axis=0)
+
+
+def logdet(diag):
+    """2 sum log L_ii and 2 sum |log L_ii| (the scale an absolute bound on the sum's error is stated against)."""
+    lg = np.log(np.asarray(diag).astype(LD))
+    return LD(2) * np.sum(lg), LD(2) * np.sum(np.abs(lg))
+
+
+def loo(w, d, y):
+    """The leave-one-out formulas (GPML eqs. 5.10 - 5.12) from w = G^{-1} r, d = diag(G^{-1}) and the observations y:
+    mean = y - w / d, var = 1 / d, logp = 1/2 log d - 1/2 w^2 / d - 1/2 log 2 pi."""
+    w, d, y = (np.asarray(a).astype(LD) for a in (w, d, y))
+    return y - w / d, LD(1) / d, LD(0.5) * np.log(d) - LD(0.5) * w * w / d - HALF_LOG_2PI
+
+
+def lower_mv(L, x, absolute=False):
+    """L x (absolute: |L| |x|) in long double, by rows left of the diagonal."""
+    xl = np.asarray(x).astype(LD)
+    if absolute:
+        xl = np.abs(xl)
+    out = np.empty(L.shape[0], dtype=LD)
+    for i in range(0, L.shape[0], 512):
+        e = min(i + 512, L.shape[0])
+        blk = L[i:e, :e].astype(LD)
+        out[i:e] = (np.abs(blk) if absolute else blk) @ xl[:e]
+    return out
+
+
+def backward_error(L, z, r):
+    """Componentwise backward error of L z = r: max_i |r - L z|_i / (|L| |z| + |r|)_i with the residual in long double; 0/0
+    counts 0, a nonzero residual over 0 fails (the convention of test_gpu_predict_backward.py)."""
+    rl = np.asarray(r).astype(LD)
+    res = np.abs(rl - lower_mv(L, z))
+    den = lower_mv(L, z, absolute=True) + np.abs(rl)
+    zero = den == 0
+    assert not np.any(res[zero] != 0), "a nonzero residual where |L||z| + |r| is zero"
+    return float(np.max(np.where(zero, LD(0), res / np.where(zero, LD(1), den))))
+
+
+def relative_error(got, ref):
+    """max_i |got_i - ref_i| / |ref_i| (a zero reference entry must be met exactly)."""
+    ref = np.asarray(ref).astype(LD)
+    err = np.abs(np.asarray(got).astype(LD) - ref)
+    zero = ref == 0
+    assert not np.any(err[zero] != 0), "a nonzero value where the reference is exactly zero"
+    return float(np.max(np.where(zero, LD(0), err / np.where(zero, LD(1), np.abs(ref)))))

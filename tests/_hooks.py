@@ -17,7 +17,7 @@ from linpde_gp_amd._lib import check
 HOOKS_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "liblpgp_testhooks.so")
 
 EXPORTED = ["lpgp_test_stair_enumerate", "lpgp_test_gemm", "lpgp_test_potrf_tile", "lpgp_test_tile_step", "lpgp_test_panel_solve",
-            "lpgp_debug_tile_xcc", "lpgp_probe_mfma_f64", "lpgp_probe_hbm_write", "lpgp_test_force_status"]
+            "lpgp_debug_tile_xcc", "lpgp_probe_mfma_f64", "lpgp_probe_hbm_write", "lpgp_test_force_status", "lpgp_test_solve_vec_fwd"]
 
 
 def _load() -> C.CDLL:
@@ -41,6 +41,7 @@ def _load() -> C.CDLL:
     sig("lpgp_probe_mfma_f64", C.c_int, vp, pd)
     sig("lpgp_probe_hbm_write", C.c_int, vp, i64, pd)
     sig("lpgp_test_force_status", C.c_int, vp, vp, i32)
+    sig("lpgp_test_solve_vec_fwd", C.c_int, vp, vp, pd, pd)
     return lib
 
 
@@ -123,6 +124,18 @@ def test_potrf_tile(ctx: Context, T: np.ndarray):
     check(lib.lpgp_test_potrf_tile(ctx._h, T.ctypes.data_as(pd), Linv.ctypes.data_as(pd), C.byref(info)),
           "lpgp_test_potrf_tile")
     return T, Linv, info.value
+
+
+def solve_vec_fwd(ctx: Context, mat, r: np.ndarray) -> np.ndarray:
+    """z = L^{-1} r by the forward half of the single-vector solve as `lpgp_mat_evidence` runs it (`lpgp_test_solve_vec_fwd`; the
+    option trsv_resident selects the form).  `r` in Gram order; z comes back in the PADDED layout (`mat.padded_n` doubles)."""
+    r = np.ascontiguousarray(r, dtype=np.double)
+    if r.shape != (mat.n,):
+        raise ValueError(f"residual must have shape ({mat.n},), got {r.shape}")
+    z = np.full(mat.padded_n, np.nan)
+    pd = C.POINTER(C.c_double)
+    check(lib.lpgp_test_solve_vec_fwd(ctx._h, mat._h, r.ctypes.data_as(pd), z.ctypes.data_as(pd)), "lpgp_test_solve_vec_fwd")
+    return z
 
 
 def force_status(ctx: Context, mat, value: int) -> None:

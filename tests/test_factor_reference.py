@@ -1,0 +1,194 @@
+"""tests/_factor_reference.py (the long-double references of test_gpu_evidence_backward.py) against 50-digit mpmath at n = 40, and
+LAPACK's own distance from those references on the matrices the GPU suite uses.  No GPU.
+
+The references must be good to a small fraction of one u = 2^-53 on the cases where a double result is a few u off, or a
+measure "in units of u" means nothing: against mpmath every reference is held to REF_TOL = u / 64 in the measure the GPU suite
+takes of it -- z by its componentwise backward error, a column of L^-1 relative to its 2-norm, d, the logs and the LOO formulas
+componentwise (long double carries 11 more bits; the cases are a factor whose diagonal straddles 1, so that the logs change
+sign, and one whose rows are scaled over twelve decades).  The GPU suite states its bars as multiples of LAPACK's error on the same factor; a LAPACK
+error that is large would make such a bar vacuous, so LAPACK is held here to caps taken from its own measured error on NumPy
+factors of the same matrices (Matern-5/2, lengthscale 0.3, scattered 2-D points, the three noise kinds of _backward.py):
+  z = L^-1 r       componentwise backward error of scipy.linalg.solve_triangular   <= CAP_Z = 8 u     [measured: 0.6 - 5.2 u]
+  d = diag(G^-1)   componentwise relative error of solve_triangular(L, I), column sums of squares in double
+                                                                                    <= CAP_D = 256 u   [measured: 3.7 - 163 u]
+  2 sum log L_ii   |numpy's double value - reference| <= CAP_LOG = 32 u 2 sum |log L_ii| (the ceiling of the device's bar)  [measured: at most 1.24 u]"""
+import mpmath
+import numpy as np
+import pytest
+import scipy.linalg
+
+import _factor_reference as fr
+from _backward import gram_points
+
+U = fr.U
+LD = fr.LD
+REF_TOL = U / 64
+CAP_Z, CAP_D, CAP_LOG = 8 * U, 256 * U, 32 * U
+DPS = 50
+
+
+def matern52_gram(kind, n):
+    X, noise = gram_points(kind, n)
+    r = np.sqrt(5.0) * np.sqrt(np.sum((X[:, None, :] - X[None, :, :]) ** 2, axis=-1)) / 0.3
+    return (1 + r + r * r / 3) * np.exp(-r) + np.diag(noise)
+
+
+def small_factor(case):
+    """n = 40 lower-triangular factors: "straddle": the Cholesky factor of a Matern Gram scaled so that its diagonal runs over
+    [0.03, 30] on both sides of 1; "decades": rows scaled over twelve decades."""
+    rng = np.random.default_rng(40 + len(case))
+    L = np.linalg.cholesky(matern52_gram("m", 40))
+    s = 10.0 ** rng.uniform(-1.5, 1.5, 40) if case == "straddle" else 10.0 ** rng.uniform(-6, 6, 40)
+    L = s[:, None] * L
+    return L, rng.standard_normal(40) * (s if case == "decades" else 1.0), rng.standard_normal(40)
+
+
+def mp_forward(L, r):
+    n = L.shape[0]
+    z = [mpmath.mpf(0)] * n
+    for i in range(n):
+        z[i] = (mpmath.mpf(float(r[i])) - mpmath.fsum(mpmath.mpf(float(L[i, j])) * z[j] for j in range(i))) / mpmath.mpf(float(L[i, i]))
+    return z
+
+
+def mp_inverse(L):
+    n = L.shape[0]
+    Lm = [[mpmath.mpf(float(L[i, j])) for j in range(n)] for i in range(n)]
+    W = [[mpmath.mpf(0)] * n for _ in range(n)]
+    for i in range(n):
+        for c in range(i + 1):
+            W[i][c] = ((1 if c == i else 0) - mpmath.fsum(Lm[i][j] * W[j][c] for j in range(c, i))) / Lm[i][i]
+    return W
+
+
+def as_mp(x):
+    """A long double as an exact mpmath number (hi + lo split: mpf() of a numpy long double goes through float)."""
+    hi = np.float64(x)
+    lo = np.float64(x - LD(hi))
+    return mpmath.mpf(float(hi)) + mpmath.mpf(float(lo))
+
+
+def rel_ld(got, want):
+    worst = mpmath.mpf(0)
+    for g, w in zip(np.asarray(got, dtype=LD).reshape(-1), want):
+        gm = as_mp(g)
+        worst = max(worst, abs(gm - w) / abs(w) if w != 0 else abs(gm))
+    return float(worst)
+
+
+@pytest.mark.parametrize("case", ["straddle", "decades"])
+def test_references_against_mpmath(case):
+    L, r, y = small_factor(case)
+    diag = np.diag(L)
+    if case == "straddle":
+        assert diag.min() < 0.5 and diag.max() > 2.0
+    else:
+        assert np.ptp(np.log10(np.abs(L).max(axis=1))) >= 10.0
+    with mpmath.workdps(DPS):
+        z = mp_forward(L, r)
+        # an entry of z is a sum that may cancel (rows over twelve decades: its relative error is cond-bound in any
+        # precision); what the reference owes is a componentwise backward error far below u -- and backward_error() itself
+        # must agree with the same measure taken in mpmath
+        zl = fr.forward(L, r)
+        print(f"\n[{case}] forward: relative error {rel_ld(zl, z) / U:.2e} u")
+        Lm = [[mpmath.mpf(float(L[i, j])) for j in range(i + 1)] for i in range(40)]
+        zm = [as_mp(v) for v in zl]
+        e = max(float(abs(mpmath.mpf(float(r[i])) - mpmath.fsum(Lm[i][j] * zm[j] for j in range(i + 1)))
+                      / (mpmath.fsum(abs(Lm[i][j] * zm[j]) for j in range(i + 1)) + abs(mpmath.mpf(float(r[i]))))) for i in range(40))
+        print(f"[{case}] forward: componentwise backward error {e / U:.2e} u")
+        assert e <= REF_TOL
+        zd = zl.astype(np.float64)                 # rounded to double the residual is large enough for long double to measure
+        zdm = [mpmath.mpf(float(v)) for v in zd]
+        want = max(float(abs(mpmath.mpf(float(r[i])) - mpmath.fsum(Lm[i][j] * zdm[j] for j in range(i + 1)))
+                         / (mpmath.fsum(abs(Lm[i][j] * zdm[j]) for j in range(i + 1)) + abs(mpmath.mpf(float(r[i]))))) for i in range(40))
+        assert abs(fr.backward_error(L, zd, r) - want) <= REF_TOL and want <= 2 * U
+        W = mp_inverse(L)
+        Wl = fr.inverse(L)
+        assert np.all(np.triu(Wl, 1) == 0)
+        # an entry of L^-1 is a sum that may cancel: no precision gives it to a relative error.  What d = colsum(W * W) needs
+        # is every column to a fraction of its own 2-norm
+        e = max(float(mpmath.sqrt(mpmath.fsum((as_mp(Wl[i, j]) - W[i][j]) ** 2 for i in range(j, 40)) / mpmath.fsum(W[i][j] ** 2 for i in range(j, 40))))
+                for j in range(40))
+        print(f"[{case}] inverse: {e / U:.2e} u of a column's norm")
+        assert e <= REF_TOL
+        d = [mpmath.fsum(W[i][j] ** 2 for i in range(j, 40)) for j in range(40)]
+        dl = fr.inverse_diag(Wl)
+        e = rel_ld(dl, d)
+        print(f"[{case}] inverse diagonal: {e / U:.2e} u; d spans {float(min(d)):.1e} .. {float(max(d)):.1e}")
+        assert e <= REF_TOL
+        logs = [mpmath.log(mpmath.mpf(float(v))) for v in diag]
+        ld, scale = fr.logdet(diag)
+        e = float(abs(as_mp(ld) - 2 * mpmath.fsum(logs)) / (2 * mpmath.fsum(abs(v) for v in logs)))
+        print(f"[{case}] log det: {e / U:.2e} u of 2 sum |log|; log det {float(ld):.3f}, 2 sum |log| {float(scale):.3f}")
+        assert e <= REF_TOL
+        assert float(abs(as_mp(scale) - 2 * mpmath.fsum(abs(v) for v in logs))) <= REF_TOL * float(scale)
+        if case == "straddle":
+            assert abs(float(ld)) < 0.5 * float(scale)          # the logs cancel: the scale is not |log det|
+        # the LOO formulas from (w, d, y), w any vector
+        w = np.random.default_rng(3).standard_normal(40) * np.sqrt(np.asarray(dl, dtype=np.float64))
+        dd = np.asarray(dl, dtype=np.float64)
+        mean, var, logp = fr.loo(w, dd, y)
+        wm, dm, ym = ([mpmath.mpf(float(v)) for v in a] for a in (w, dd, y))
+        e = max(rel_ld(var, [1 / v for v in dm]),
+                rel_ld(logp, [mpmath.log(v) / 2 - a * a / v / 2 - mpmath.log(2 * mpmath.pi) / 2 for a, v in zip(wm, dm)]))
+        print(f"[{case}] LOO var, logp: {e / U:.2e} u")
+        assert e <= REF_TOL
+        # the mean cancels (y - w / d): its error is stated against |y| + |w / d|
+        mm = [b - a / v for a, v, b in zip(wm, dm, ym)]
+        e = max(float(abs(as_mp(g) - m) / (abs(b) + abs(a / v))) for g, m, a, v, b in zip(mean, mm, wm, dm, ym))
+        assert e <= REF_TOL
+
+
+def test_backward_error_conventions():
+    L = np.array([[2.0, 0.0, 0.0], [1.0, 4.0, 0.0], [0.0, 0.0, 1.0]])
+    z = np.array([1.0, 0.5, 0.0])
+    r = L @ z
+    assert fr.backward_error(L, z, r) == 0.0                              # the last row: 0 / 0 counts 0
+    r2 = r.copy()
+    r2[1] += 3.0 * 2.0 ** -50                                              # (r_1 = 3: |L||z| + |r| = 6 + a rounding)
+    assert abs(fr.backward_error(L, z, r2) - 3.0 * 2.0 ** -50 / 6.0) <= 1e-28
+    zbad = z.copy()
+    zbad[2] = 1e-300                                                       # a nonzero over a nonzero denominator: a number
+    assert fr.backward_error(L, zbad, r) == 1.0
+    Lz = np.array([[1.0, 0.0], [1.0, 0.0]])                                # |L||z| + |r| = 0 in both rows, r - L z = 0
+    assert fr.backward_error(Lz, np.array([0.0, 5.0]), np.zeros(2)) == 0.0
+    assert np.isnan(fr.backward_error(L, np.array([1.0, np.nan, 0.0]), r))   # a NaN stays a NaN: no bar is met by it
+    assert fr.relative_error(np.array([1.0 + 2.0 ** -52, 0.0]), np.array([1.0, 0.0])) == 2.0 ** -52
+    with pytest.raises(AssertionError, match="exactly zero"):
+        fr.relative_error(np.array([1e-300]), np.array([0.0]))
+
+
+_lapack = {}
+
+
+def lapack_case(kind, n):
+    if (kind, n) not in _lapack:
+        G = matern52_gram(kind, n)
+        L = np.linalg.cholesky(G)
+        _lapack[(kind, n)] = (L, fr.inverse_diag(fr.inverse(L)))
+    return _lapack[(kind, n)]
+
+
+@pytest.mark.parametrize("n", [100, 128, 300, 700])
+@pytest.mark.parametrize("kind", ["m", "b", "s"])
+def test_lapack_stays_within_the_caps(kind, n):
+    """LAPACK on a NumPy factor of the GPU suite's matrices: the denominators of RATIO_Z and RATIO_D are a few u, not a bar
+    that anything passes."""
+    L, d_ref = lapack_case(kind, n)
+    r = np.random.default_rng(n + 1).standard_normal(n)
+    be = fr.backward_error(L, scipy.linalg.solve_triangular(L, r, lower=True), r)
+    ref = fr.forward(L, r)
+    assert fr.backward_error(L, ref.astype(np.float64), r) <= 2 * U          # the rounded reference: one rounding per entry
+    W = scipy.linalg.solve_triangular(L, np.eye(n), lower=True)
+    ed = fr.relative_error(np.sum(W * W, axis=0), d_ref)
+    diag = np.diag(L)
+    ld, scale = fr.logdet(diag)
+    el = float(abs(LD(2.0 * np.sum(np.log(diag))) - ld) / scale)
+    span = float(np.log10(float(d_ref.max()) / float(d_ref.min())))
+    print(f"\n[{kind} n={n}] solve_triangular backward error {be / U:.2f} u; diag(G^-1) relative error {ed / U:.1f} u over {span:.1f} decades; "
+          f"log det {el / U:.2f} u of 2 sum |log| ({float(ld):.1f} of {float(scale):.1f})")
+    assert be <= CAP_Z
+    assert ed <= CAP_D
+    assert el <= CAP_LOG
+    if kind == "s":
+        assert span >= 8.0
