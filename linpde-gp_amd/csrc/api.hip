@@ -1054,12 +1054,16 @@ static int dist_fail(lpgp_ctx* ctx, int rc) {
 // V <- L^{-1} V and V <- L^{-T} V for the whole view of `mat`: streamed over the ranks of a multi-GPU job (a failure of one
 // rank aborts the communicator), blocked on a single GPU
 static int solve_lower(lpgp_ctx* ctx, lpgp_mat* mat, double* v, int64_t ldv, int64_t m_pad) {
-  return ctx->distributed() ? dist_fail(ctx, trsm_lower_dist(ctx, mat, mat->pn / TILE, v, ldv, m_pad))
-                            : trsm_lower_blocked(ctx, mat, mat->pn / TILE, v, ldv, m_pad);
+  if (ctx->distributed()) return dist_fail(ctx, trsm_lower_dist(ctx, mat, mat->pn / TILE, v, ldv, m_pad));
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
+  return trsm_lower_blocked(ctx, F, mat->pn / TILE, v, ldv, m_pad);
 }
 static int solve_lower_t(lpgp_ctx* ctx, lpgp_mat* mat, double* v, int64_t ldv, int64_t m_pad) {
-  return ctx->distributed() ? dist_fail(ctx, trsm_lower_t_dist(ctx, mat, mat->pn / TILE, v, ldv, m_pad))
-                            : trsm_lower_t_blocked(ctx, mat, mat->pn / TILE, v, ldv, m_pad);
+  if (ctx->distributed()) return dist_fail(ctx, trsm_lower_t_dist(ctx, mat, mat->pn / TILE, v, ldv, m_pad));
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
+  return trsm_lower_t_blocked(ctx, F, mat->pn / TILE, v, ldv, m_pad);
 }
 
 int lpgp_mat_to_host(lpgp_ctx* ctx, lpgp_mat* mat, int32_t what, double* out_host) {
@@ -1385,8 +1389,10 @@ int lpgp_solve_weights(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, doubl
     *hinfo = 0;
     LPGP_TRY(sync_stream(ctx, ctx->s_main));      // (watched: a copy behind a streamed solve whose peer is gone would wait for ever)
   } else {
+    FactorView F;
+    LPGP_TRY(factor_view(mat, &F));
     LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), ctx->s_main));
-    LPGP_TRY(solve_vec(ctx, mat, pn / TILE, mat->w, ctx->d_tmp, ctx->d_info));
+    LPGP_TRY(solve_vec(ctx, F, pn / TILE, mat->w, ctx->d_tmp, ctx->d_info));
     LPGP_HIP(hipMemcpyAsync(hinfo, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->s_main));
   }
   LPGP_HIP(hipMemcpyAsync(hs, mat->w, (size_t)pn * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
@@ -1716,11 +1722,8 @@ int lpgp_rhs_inner(lpgp_ctx* ctx, lpgp_rhs* A, lpgp_rhs* B, double* out_host) {
   DevBuf dc;
   LPGP_TRY(DevBuf::raw(h.size() * sizeof(double), &dc));
   StreamDrain drain{ctx->s_main};
-  GemmArgs g;
-  g.A = A->v; g.B = B->v; g.C = dc.as(); g.lda = A->ld; g.ldb = B->ld; g.ldc = ma;
-  g.mt = (int)(ma / TILE); g.nt = (int)(mb / TILE); g.k = (int)A->ld; g.alpha = 1.0; g.beta = 0.0;
-  g.tri = 0;
-  LPGP_TRY(launch_gemm(ctx, ctx->s_main, 1, 1, g, LPGP_K_GEMM));
+  LPGP_TRY(launch_gemm(ctx, ctx->s_main, 1, 1, mk(A->v, A->ld, B->v, B->ld, dc.as(), ma, (int)(ma / TILE), (int)(mb / TILE), (int)A->ld, 1.0, 0.0, 0),
+                       LPGP_K_GEMM));
   LPGP_HIP(hipMemcpyAsync(h.data(), dc.as(), h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
   LPGP_TRY(drain.wait());
   for (int64_t i = 0; i < A->m; ++i)
@@ -1748,11 +1751,8 @@ int lpgp_rhs_matmul(lpgp_ctx* ctx, const lpgp_rhs* A, const double* B_host, int6
   LPGP_TRY(DevBuf::pool(ctx, bb, &b));
   StreamDrain drain{ctx->s_main};                // (the staging vector is borrowed by the copy)
   LPGP_HIP(hipMemcpyAsync(b.as(), hb.data(), bb, hipMemcpyHostToDevice, ctx->s_main));
-  GemmArgs g;
-  g.A = A->v; g.B = b.as(); g.C = out->v; g.lda = A->ld; g.ldb = ka; g.ldc = out->ld;
-  g.mt = (int)(out->ld / TILE); g.nt = (int)(mp / TILE); g.k = (int)ka; g.alpha = 1.0; g.beta = 0.0;
-  g.tri = 0;
-  LPGP_TRY(launch_gemm(ctx, ctx->s_main, 0, 1, g, LPGP_K_GEMM));
+  LPGP_TRY(launch_gemm(ctx, ctx->s_main, 0, 1,
+                       mk(A->v, A->ld, b.as(), ka, out->v, out->ld, (int)(out->ld / TILE), (int)(mp / TILE), (int)ka, 1.0, 0.0, 0), LPGP_K_GEMM));
   LPGP_TRY(drain.wait());
   *out_new = out.release();
   return 0;
@@ -1776,12 +1776,11 @@ int lpgp_mat_sub_inner(lpgp_ctx* ctx, lpgp_mat* S, int32_t bi, lpgp_rhs* V) {
   const int T = (int)(B.pn / TILE), BW = 4;
   double* const C0 = S->a + B.poff * (S->lr_cap + 1);
   for (int c0 = 0; c0 < T; c0 += BW) {
-    GemmArgs g;
-    g.A = V->v + (int64_t)c0 * TILE * V->ld; g.B = g.A; g.C = C0 + (int64_t)c0 * TILE * (S->lr_cap + 1);
-    g.lda = V->ld; g.ldb = V->ld; g.ldc = S->lr_cap;
-    g.mt = T - c0; g.nt = std::min(BW, T - c0); g.k = (int)V->ld; g.alpha = -1.0; g.beta = 1.0;
-    g.tri = 0;
-    LPGP_TRY(launch_gemm(ctx, ctx->s_main, 1, 1, g, LPGP_K_GEMM));
+    const double* Vc = V->v + (int64_t)c0 * TILE * V->ld;
+    LPGP_TRY(launch_gemm(ctx, ctx->s_main, 1, 1,
+                         mk(Vc, V->ld, Vc, V->ld, C0 + (int64_t)c0 * TILE * (S->lr_cap + 1), S->lr_cap, T - c0, std::min(BW, T - c0), (int)V->ld, -1.0,
+                            1.0, 0),
+                         LPGP_K_GEMM));
   }
   return 0;        // asynchronous: consumers are ordered behind it on the main stream
 }
@@ -1901,11 +1900,8 @@ int lpgp_gemm_host(lpgp_ctx* ctx, int32_t transa, int32_t transb, int64_t m, int
     LPGP_HIP(hipMemcpy2DAsync(pc.as(), (size_t)np_ * sizeof(double), C_host, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)m,
                               hipMemcpyHostToDevice, st));
   }
-  GemmArgs g;
-  g.A = pa.as(); g.B = pb.as(); g.C = pc.as(); g.lda = a_ld; g.ldb = b_ld; g.ldc = np_;
-  g.mt = (int)(np_ / TILE); g.nt = (int)(mp / TILE); g.k = (int)kp; g.alpha = alpha; g.beta = beta;
-  g.tri = 0;
-  LPGP_TRY(launch_gemm(ctx, st, transb ? 1 : 0, transa ? 0 : 1, g, LPGP_K_GEMM));
+  LPGP_TRY(launch_gemm(ctx, st, transb ? 1 : 0, transa ? 0 : 1,
+                       mk(pa.as(), a_ld, pb.as(), b_ld, pc.as(), np_, (int)(np_ / TILE), (int)(mp / TILE), (int)kp, alpha, beta, 0), LPGP_K_GEMM));
   LPGP_HIP(hipMemcpy2DAsync(C_host, (size_t)n * sizeof(double), pc.as(), (size_t)np_ * sizeof(double), (size_t)n * sizeof(double), (size_t)m,
                             hipMemcpyDeviceToHost, st));
   return drain.wait();

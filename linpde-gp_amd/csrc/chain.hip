@@ -396,17 +396,16 @@ __global__ __launch_bounds__(256, 2) void panel_chain_rows_kernel(ChainArgs g) {
 // rows_here = false: the factor workgroup and the twelve in-block row workgroups only; the rows below follow through the flags
 // in a launch of their own (launch_panel_chain_rows).
 // ahead = true: the look-ahead update by the previous panel (columns [p0 - 4, p0), all rows from p0 on) is part of the launch.
-int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, lpgp_mat* mat, int p0, int T, int* d_info, bool rows_here, bool ahead) {
+int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info, bool rows_here, bool ahead) {
   LPGP_CHECK(!ahead || (p0 >= 4 && rows_here), "resident chain: the fused look-ahead needs a previous panel of four tiles and the rows in the same launch");
-  const int64_t ld = mat->cap;
   if (!ctx->d_chain_flags) {
     LPGP_HIP(hipMalloc(&ctx->d_chain_flags, (size_t)CH_SLOTS * CH_SLOT_INTS * sizeof(int)));
     LPGP_HIP(hipMemsetAsync(ctx->d_chain_flags, 0, (size_t)CH_SLOTS * CH_SLOT_INTS * sizeof(int), stream));
   }
   ChainArgs g;
-  g.a = mat->a + (int64_t)p0 * TILE * (ld + 1);
-  g.ld = ld;
-  g.linv = mat->linv + (int64_t)p0 * TILE * TILE;
+  g.a = F.diag(p0);
+  g.ld = F.ld;
+  g.linv = F.inv(p0);
   const int64_t n = ctx->chain_launches++;
   g.slot = ctx->d_chain_flags + (n % CH_SLOTS) * CH_SLOT_INTS;
   ctx->chain_last_slot = g.slot;
@@ -430,15 +429,14 @@ int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, lpgp_mat* mat, int p0,
 }
 
 // rows below the diagonal block of panel p0 (down to tile T), following the chain launched LAST (launch_panel_chain(..., rows_here = false))
-int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, lpgp_mat* mat, int p0, int T, int* d_info) {
+int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info) {
   LPGP_CHECK(ctx->chain_last_slot && ctx->chain_last_p0 == p0, "resident chain: no chain launch of panel %d to follow", p0);
-  const int64_t ld = mat->cap;
   const int below = T - p0 - 4;
   if (below <= 0) return 0;
   ChainArgs g;
-  g.a = mat->a + (int64_t)p0 * TILE * (ld + 1);
-  g.ld = ld;
-  g.linv = mat->linv + (int64_t)p0 * TILE * TILE;
+  g.a = F.diag(p0);
+  g.ld = F.ld;
+  g.linv = F.inv(p0);
   g.slot = ctx->chain_last_slot;
   g.slot_clear = nullptr;
   g.info = d_info;
@@ -455,13 +453,12 @@ int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, lpgp_mat* mat, in
 
 // V: first row of the panel's rows of the right-hand side (rows p0 * 128 ...), `cols` columns (a multiple of 128); the chain of
 // panel p0 must be the LAST one launched (launch_panel_chain), its flag slot is the one this launch follows.
-int launch_panel_chain_v(lpgp_ctx* ctx, hipStream_t stream, lpgp_mat* mat, int p0, double* V, int64_t ldv, int64_t cols, int* d_info) {
+int launch_panel_chain_v(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, double* V, int64_t ldv, int64_t cols, int* d_info) {
   LPGP_CHECK(ctx->chain_last_slot && ctx->chain_last_p0 == p0, "resident chain: no chain launch of panel %d to follow", p0);
-  const int64_t ld = mat->cap;
   ChainArgs g;
-  g.a = mat->a + (int64_t)p0 * TILE * (ld + 1);
-  g.ld = ld;
-  g.linv = mat->linv + (int64_t)p0 * TILE * TILE;
+  g.a = F.diag(p0);
+  g.ld = F.ld;
+  g.linv = F.inv(p0);
   g.slot = ctx->chain_last_slot;
   g.slot_clear = nullptr;
   g.info = d_info;

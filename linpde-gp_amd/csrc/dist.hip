@@ -120,15 +120,6 @@ int sync_stream(lpgp_ctx* ctx, hipStream_t st) {
   }
 }
 
-static inline GemmArgs mk(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int mt, int nt,
-                          int k, double alpha, double beta, int tri) {
-  GemmArgs g;
-  g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.mt = mt; g.nt = nt; g.k = k; g.alpha = alpha; g.beta = beta;
-  g.tri = tri;
-  return g;
-}
-
 // ---- broadcast of a set of device buffers, each from its own root to every rank ---------------------------------
 struct Piece {
   int root;

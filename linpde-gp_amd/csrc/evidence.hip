@@ -176,6 +176,8 @@ static int ev_download(lpgp_ctx* ctx, double* dst, const double* src, size_t dou
 int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]) {
   const int64_t pn = mat->pn, T = pn / TILE;
   hipStream_t st = ctx->s_main;
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
   std::vector<double> h;
   ev_stage(mat, &r_host, 1, &h);
   // [r | lrow] as staged, z + the ticket word of the resident solve, the partials, the result
@@ -186,8 +188,8 @@ int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_
   StreamDrain drain{st};                         // (the staging vector and the caller's array are borrowed by the copies)
   LPGP_TRY(ev_upload(ctx, d, h));
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
-  if (ctx->trsv_resident) LPGP_TRY(solve_vec_fwd_resident(ctx, mat, T, d, d + o_z, ctx->d_info));
-  else LPGP_TRY(solve_vec_fwd(ctx, st, mat, T, d, d + o_z));
+  if (ctx->trsv_resident) LPGP_TRY(solve_vec_fwd_resident(ctx, F, T, d, d + o_z, ctx->d_info));
+  else LPGP_TRY(solve_vec_fwd(ctx, st, F, T, d, d + o_z));
   const int nwg = ev_wgs(pn);
   hipLaunchKernelGGL(evidence_partial_kernel, dim3((unsigned)nwg), dim3(EV_THREADS), 0, st, (const double*)(d + o_z), (const double*)mat->a, mat->lr_cap,
                      reinterpret_cast<const int32_t*>(d + pn), pn, d + o_part);
@@ -202,6 +204,8 @@ int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_
 static int inverse_diag_device(lpgp_ctx* ctx, lpgp_mat* mat, double* d_diag) {
   const int64_t pn = mat->pn, panel = std::min<int64_t>(ctx->inverse_diag_panel, pn);
   hipStream_t st = ctx->s_main;
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
   DevBuf vbuf;                                   // (reuse is ordered on the panel stream, which the blocked solve joins at its end)
   LPGP_TRY(DevBuf::pool(ctx, (size_t)pn * panel * sizeof(double), &vbuf));
   double* const v = vbuf.as();
@@ -210,14 +214,8 @@ static int inverse_diag_device(lpgp_ctx* ctx, lpgp_mat* mat, double* d_diag) {
     const unsigned gy = (unsigned)(pc < 65535 ? pc : 65535), gz = (unsigned)((pc + 65534) / 65535);
     hipLaunchKernelGGL(identity_panel_kernel, dim3((unsigned)((rows / 2 + EV_THREADS - 1) / EV_THREADS), gy, gz), dim3(EV_THREADS), 0, st, v, rows, pc);
     LPGP_HIP(hipGetLastError());
-    // the trailing sub-factor L[j0:, j0:]: its first tile, its first tile inverse, the leading dimension of the whole
-    lpgp_mat sub{};
-    sub.ctx = ctx;
-    sub.cap = mat->cap; sub.lr_cap = mat->lr_cap; sub.lc_cap = mat->lc_cap;
-    sub.a = mat->a + j0 * (mat->cap + 1);
-    sub.linv = mat->linv + j0 * TILE;
-    sub.n = sub.pn = sub.pn_fact = rows;
-    LPGP_TRY(trsm_lower_blocked(ctx, &sub, rows / TILE, v, rows, pc));
+    // against the trailing sub-factor L[j0:, j0:]
+    LPGP_TRY(trsm_lower_blocked(ctx, F.trailing((int)(j0 / TILE)), rows / TILE, v, rows, pc));
     hipLaunchKernelGGL(col_sumsq_lower_kernel, dim3(gy, gz), dim3(EV_THREADS), 0, st, (const double*)v, rows, pc, d_diag + j0);
     LPGP_HIP(hipGetLastError());
   }
@@ -241,6 +239,8 @@ int mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host) {
 int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host, double* logp_host) {
   const int64_t pn = mat->pn, n = mat->n, T = pn / TILE;
   hipStream_t st = ctx->s_main;
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
   std::vector<double> h, res((size_t)(3 * pn + 1));
   const double* vecs[2] = {r_host, y_host};
   ev_stage(mat, vecs, 2, &h);
@@ -253,7 +253,7 @@ int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_
   StreamDrain drain{st};
   LPGP_TRY(ev_upload(ctx, d, h));
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
-  LPGP_TRY(solve_vec(ctx, mat, T, d, d + o_tmp, ctx->d_info));
+  LPGP_TRY(solve_vec(ctx, F, T, d, d + o_tmp, ctx->d_info));
   LPGP_TRY(inverse_diag_device(ctx, mat, d + o_d));
   const int nwg = ev_wgs(pn);
   hipLaunchKernelGGL(loo_epilogue_kernel, dim3((unsigned)nwg), dim3(EV_THREADS), 0, st, (const double*)d, (const double*)(d + o_d), (const double*)(d + pn),

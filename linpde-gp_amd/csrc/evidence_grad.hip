@@ -127,6 +127,8 @@ int mat_inverse_into(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat* out) {
   const int64_t pn = mat->pn, panel = std::min<int64_t>(ctx->inverse_diag_panel, pn);
   const int T = (int)(pn / TILE), BW = 4;
   hipStream_t st = ctx->s_main;
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
   DevBuf wbuf;                                   // W = L^{-1}, pn x pn (reuse is ordered on the panel stream, which the blocked solve joins at its end)
   LPGP_TRY(DevBuf::pool(ctx, (size_t)pn * pn * sizeof(double), &wbuf));
   double* const W = wbuf.as();
@@ -135,14 +137,8 @@ int mat_inverse_into(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat* out) {
   LPGP_HIP(hipGetLastError());
   for (int64_t j0 = 0; j0 < pn; j0 += panel) {
     const int64_t rows = pn - j0, pc = std::min(panel, rows);
-    // the trailing sub-factor L[j0:, j0:] (inverse_diag_device): its first tile, its first tile inverse, the leading dimension of the whole
-    lpgp_mat sub{};
-    sub.ctx = ctx;
-    sub.cap = mat->cap; sub.lr_cap = mat->lr_cap; sub.lc_cap = mat->lc_cap;
-    sub.a = mat->a + j0 * (mat->cap + 1);
-    sub.linv = mat->linv + j0 * TILE;
-    sub.n = sub.pn = sub.pn_fact = rows;
-    LPGP_TRY(trsm_lower_blocked(ctx, &sub, rows / TILE, W + j0 * (pn + 1), pn, pc));
+    // against the trailing sub-factor L[j0:, j0:] (as inverse_diag_device)
+    LPGP_TRY(trsm_lower_blocked(ctx, F.trailing((int)(j0 / TILE)), rows / TILE, W + j0 * (pn + 1), pn, pc));
   }
   // out[c0:, c0 : c0 + BW] = W[c0:, c0:]^T W[c0:, c0 : c0 + BW], band by band (the form of lpgp_mat_sub_inner); the tiles above the
   // diagonal inside a band are written and never read
@@ -190,6 +186,8 @@ static int eg_finish(lpgp_ctx* ctx, hipStream_t st, double* d_part, int nwg, dou
 int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host, double out_host[2]) {
   const int64_t pn = mat->pn, T = pn / TILE;
   hipStream_t st = ctx->s_main;
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
   std::vector<double> h;
   const int64_t off0 = 0, len0 = mat->n;
   eg_stage(mat, &r_host, &off0, &len0, 1, &h);
@@ -202,7 +200,7 @@ int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const 
   LPGP_HIP(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
   ctx->evidence_h2d_bytes += (int64_t)(h.size() * sizeof(double));
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
-  LPGP_TRY(solve_vec(ctx, mat, T, d, d + o_tmp, ctx->d_info));
+  LPGP_TRY(solve_vec(ctx, F, T, d, d + o_tmp, ctx->d_info));
   const int nwg = (int)std::min<int64_t>((pn + EG_WAVES - 1) / EG_WAVES, EG_MAX_WGS);
   hipLaunchKernelGGL(evidence_grad_partial_kernel, dim3((unsigned)nwg), dim3(EG_THREADS), 0, st, (const double*)ginv->a, ginv->lr_cap, (const double*)dG->a,
                      dG->lr_cap, (const double*)d, reinterpret_cast<const int32_t*>(d + pn), pn, d + o_part);
@@ -216,6 +214,8 @@ int mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, i
   const int64_t pn = mat->pn, T = pn / TILE;
   const lpgp_block& B = mat->blocks[(size_t)bi];
   hipStream_t st = ctx->s_main;
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
   std::vector<double> h, v((size_t)B.n, scalar);
   if (v_host) for (int64_t i = 0; i < B.n; ++i) v[(size_t)i] += v_host[i];
   const double* vecs[2] = {r_host, v.data()};
@@ -230,7 +230,7 @@ int mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, i
   LPGP_HIP(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
   ctx->evidence_h2d_bytes += (int64_t)(h.size() * sizeof(double));
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
-  LPGP_TRY(solve_vec(ctx, mat, T, d, d + o_tmp, ctx->d_info));
+  LPGP_TRY(solve_vec(ctx, F, T, d, d + o_tmp, ctx->d_info));
   const int nwg = (int)std::min<int64_t>((pn + EG_THREADS - 1) / EG_THREADS, EG_MAX_WGS);
   hipLaunchKernelGGL(evidence_grad_diag_partial_kernel, dim3((unsigned)nwg), dim3(EG_THREADS), 0, st, (const double*)ginv->a, ginv->lr_cap,
                      (const double*)(d + pn), (const double*)d, reinterpret_cast<const int32_t*>(d + 2 * pn), pn, d + o_part);

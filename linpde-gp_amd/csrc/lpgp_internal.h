@@ -10,6 +10,7 @@
 
 #include "lpgp.h"
 #include "lpgp_desc.h"
+#include "factor_view.h"
 #include "options.h"
 
 namespace lpgp {
@@ -263,6 +264,16 @@ namespace lpgp {
     LPGP_HIP(hipSetDevice((ctx)->device));                      \
   } while (0)
 
+// The factor of a single-GPU matrix as the drivers of potrf.hip, chain.hip and trsv.hip take it.  The leading dimension is that of
+// this rank's share, lr_cap; the drivers address GLOBAL tiles with it, which is right only where the share is the whole matrix:
+// this is the one place that says so.
+inline int factor_view(const lpgp_mat* mat, FactorView* out) {
+  LPGP_CHECK(mat->lr_cap == mat->cap, "single-GPU driver on a distributed matrix: leading dimension %lld, capacity %lld", (long long)mat->lr_cap,
+             (long long)mat->cap);
+  *out = FactorView{mat->a, mat->linv, mat->lr_cap};
+  return 0;
+}
+
 // raise the dynamic shared-memory limit of `fn` once per context (= per device)
 inline int ensure_lds_attr(lpgp_ctx* ctx, const void* fn, size_t bytes) {
   for (const void* f : ctx->lds_attr_done)
@@ -417,6 +428,14 @@ struct GemmArgs {
   unsigned long long* stamps = nullptr;   // diagnostic builds (-DLPGP_STAMP) only
   unsigned long long* timeline = nullptr; // diagnostic builds: per-workgroup life cycle + hardware id
 };
+inline GemmArgs mk(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int mt, int nt, int k, double alpha,
+                   double beta, int tri) {
+  GemmArgs g;
+  g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.mt = mt; g.nt = nt; g.k = k; g.alpha = alpha; g.beta = beta;
+  g.tri = tri;
+  return g;
+}
 int launch_gemm(lpgp_ctx* ctx, hipStream_t stream, int ta, int tb, const GemmArgs& g, int prof_kernel);
 int stair_enumerate_host(const GemmArgs& g, int32_t* out, int64_t cap);
 int64_t gemm_valid_tiles(const GemmArgs& g);
@@ -440,9 +459,9 @@ int launch_trsm_panel(lpgp_ctx* ctx, hipStream_t stream, double* X, int64_t ldx,
                       int nt_cols, int mt, int prof_kernel);
 
 // chain.hip: the whole chain of panel [p0, p0 + 4) (rows down to tile T) in one launch
-int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, lpgp_mat* mat, int p0, int T, int* d_info, bool rows_here = true, bool ahead = false);
-int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, lpgp_mat* mat, int p0, int T, int* d_info);
-int launch_panel_chain_v(lpgp_ctx* ctx, hipStream_t stream, lpgp_mat* mat, int p0, double* V, int64_t ldv, int64_t cols, int* d_info);
+int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info, bool rows_here = true, bool ahead = false);
+int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info);
+int launch_panel_chain_v(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, double* V, int64_t ldv, int64_t cols, int* d_info);
 // potrf.hip -------------------------------------------------------------------------------
 int debug_tile_xcc(int32_t* out8, int reset);
 int launch_potrf_tile(lpgp_ctx* ctx, hipStream_t stream, double* a, int64_t lda, double* linv,
@@ -455,13 +474,14 @@ int trsm_lower_dist(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, int64_t 
 int trsm_lower_t_dist(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, int64_t ldv, int64_t m_pad);
 int factor_to_host_dist(lpgp_ctx* ctx, lpgp_mat* mat, double* out_padded /* pn x pn column-major */);
 int copy2d(hipStream_t st, double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t cols);
-int trsm_lower_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, int64_t ldv, int64_t m_pad);
-int trsm_lower_t_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, int64_t ldv, int64_t m_pad);
+// (the drivers below work on the factor through a FactorView: the trailing sub-factor L[t0:, t0:] is F.trailing(t0))
+int trsm_lower_blocked(lpgp_ctx* ctx, FactorView F, int64_t T, double* v, int64_t ldv, int64_t m_pad);
+int trsm_lower_t_blocked(lpgp_ctx* ctx, FactorView F, int64_t T, double* v, int64_t ldv, int64_t m_pad);
 // v <- G^{-1} v; tmp: T * 128 + 2 doubles of scratch; info: device status word (INT_MIN after a timed-out hand-over of the resident form)
-int solve_vec(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, double* tmp, int* info);
-int solve_vec_resident(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, double* v, double* tmp, int* info);      // trsv.hip
-int solve_vec_fwd(lpgp_ctx* ctx, hipStream_t st, lpgp_mat* mat, int64_t T, double* b, double* x);
-int solve_vec_fwd_resident(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T, const double* b, double* x, int* info);   // trsv.hip: the forward half alone
+int solve_vec(lpgp_ctx* ctx, FactorView F, int64_t T, double* v, double* tmp, int* info);
+int solve_vec_resident(lpgp_ctx* ctx, FactorView F, int64_t T, double* v, double* tmp, int* info);      // trsv.hip
+int solve_vec_fwd(lpgp_ctx* ctx, hipStream_t st, FactorView F, int64_t T, double* b, double* x);
+int solve_vec_fwd_resident(lpgp_ctx* ctx, FactorView F, int64_t T, const double* b, double* x, int* info);   // trsv.hip: the forward half alone
 // evidence.hip: the quantities read off the factor of a fully factored single-GPU matrix (lpgp_mat_evidence, lpgp_mat_inverse_diag, lpgp_mat_loo)
 int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]);
 int mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host);

@@ -55,20 +55,39 @@ int launch_potrf_tile(lpgp_ctx* ctx, hipStream_t stream, double* a, int64_t lda,
 // ---------------------------------------------------------------------------------------
 // helpers
 // ---------------------------------------------------------------------------------------
-static inline GemmArgs mk(const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
-                          int64_t ldc, int mt, int nt, int k, double alpha, double beta, int tri) {
-  GemmArgs g;
-  g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.mt = mt; g.nt = nt; g.k = k; g.alpha = alpha; g.beta = beta;
-  g.tri = tri;
-  return g;
-}
+// (F: the factor, or the matrix being factored, by tiles -- factor_view.h; V: a right-hand side.  p, q, r, c, t: TILE indices.)
 
 // X (mt tiles of rows x one tile column) <- X * Ljj^{-T}, in place; Ljj = diagonal tile jt of the factor
-static inline int panel_trsm(lpgp_ctx* ctx, hipStream_t st, lpgp_mat* mat, int jt, double* X, int mt) {
-  const int64_t ld = mat->cap;
-  return launch_trsm_tile(ctx, st, X, ld, mat->linv + (int64_t)jt * TILE * TILE, mat->a + (int64_t)jt * TILE * (ld + 1), ld, mt,
-                          LPGP_K_TRSM);
+static inline int panel_trsm(lpgp_ctx* ctx, hipStream_t st, FactorView F, int jt, double* X, int mt) {
+  return launch_trsm_tile(ctx, st, X, F.ld, F.inv(jt), F.diag(jt), F.ld, mt, LPGP_K_TRSM);
+}
+
+// SYRK-shaped update of the trailing matrix by the panel columns [p0, p1): rows [r, TR) x columns [r, c_hi) of A -= A[., p0:p1] A[., p0:p1]^T,
+// lower tiles only (C(0, 0) = the diagonal tile r; tri / prof_kernel: which of the three forms, see GemmArgs)
+static int trailing_update(lpgp_ctx* ctx, hipStream_t st, FactorView F, int p0, int p1, int r, int c_hi, int TR, int tri, int prof_kernel,
+                           int occ3 = 1) {
+  GemmArgs g = mk(F.tile(r, p0), F.ld, F.tile(r, p0), F.ld, F.diag(r), F.ld, TR - r, c_hi - r, (p1 - p0) * TILE, -1.0, 1.0, tri);
+  g.occ3 = occ3;
+  return launch_gemm(ctx, st, 0, 0, g, prof_kernel);
+}
+
+// V[r0:r1] -= L[r0:r1, c0:c1] V[c0:c1]; nothing where r1 <= r0
+static int rhs_update(lpgp_ctx* ctx, hipStream_t st, FactorView F, RhsView V, int c0, int c1, int r0, int r1, int occ3 = 1) {
+  if (r1 <= r0) return 0;
+  GemmArgs g = mk(F.tile(r0, c0), F.ld, V.rows(c0), V.ld, V.rows(r0), V.ld, r1 - r0, V.mtl, (c1 - c0) * TILE, -1.0, 1.0, 0);
+  g.occ3 = occ3;
+  return launch_gemm(ctx, st, 0, 1, g, LPGP_K_GEMM);
+}
+
+// The panel step of the forward substitution: V[q0:q1] <- L[q0:q1, q0:q1]^{-1} V[q0:q1] (at most four tile rows where `fused`), as ONE
+// launch (panel_solve_kernel) or tile by tile with the rank-128 updates of the panel's own rows in between
+static int solve_panel(lpgp_ctx* ctx, hipStream_t st, FactorView F, RhsView V, int q0, int q1, bool fused) {
+  if (fused) return launch_trsv_panel(ctx, st, V.rows(q0), V.ld, F.inv(q0), F.diag(q0), F.ld, q1 - q0, V.mtl, LPGP_K_PANEL);
+  for (int jt = q0; jt < q1; ++jt) {
+    LPGP_TRY(launch_trsv_tile(ctx, st, V.rows(jt), V.ld, F.inv(jt), F.diag(jt), F.ld, V.mtl, LPGP_K_TRSM));
+    LPGP_TRY(rhs_update(ctx, st, F, V, jt, jt + 1, jt + 1, q1));
+  }
+  return 0;
 }
 
 // ---- ride-along forward substitution (round 5) -------------------------------------------------------------------
@@ -83,9 +102,7 @@ static inline int panel_trsm(lpgp_ctx* ctx, hipStream_t st, lpgp_mat* mat, int j
 // The kernels are the forward substitution's (trsm_lower_blocked), launch for launch; only the schedule differs.
 // (Reference: the same algebra as `BlockMatrix2x2.L_A_inv_B`, linops/_block.py:203-207, applied to K_Xx panel by panel.)
 struct Ride {
-  double* v = nullptr;       // K_Xx -> V, padded rows x m_pad, column-major
-  int64_t ldv = 0;
-  int mtl = 0;               // tile columns (m_pad / 128)
+  RhsView V{nullptr, 0, 0};  // K_Xx -> V, padded rows x m_pad, column-major
   hipStream_t stream = nullptr;     // the substitution's stream ...
   hipStream_t stream2 = nullptr;    // ... and, optionally, a second one: the right-hand side's columns are independent, so its two halves
                                     // run as two sequences of [panel chain, update]; while one half is in its latency-bound
@@ -111,14 +128,14 @@ struct Ride {
   std::vector<std::pair<int, int>> held;
   int64_t chain_launches0 = 0;   // resident chain launches before this factorisation (flag slots are recycled half a ring later)
 };
-static int ride_panel_now(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, Ride* rd, bool sync_first, bool resident = false);
+static int ride_panel_now(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ride* rd, bool sync_first, bool resident = false);
 
 // panel [p0, p1) of the factor is final on the panel stream from here on: enqueue its substitution step(s)
 // (resident: the panel's chain was the resident kernel, launched last on the panel stream -- the step may follow it flag by flag)
-static int ride_panel(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, Ride* rd, bool old_panel = false, bool resident = false) {
+static int ride_panel(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ride* rd, bool old_panel = false, bool resident = false) {
   // (steps of OLD panels -- a block append pushes its rows through them before it factors anything -- may pass the gate: they fill
   //  the start-up of the append, the first panel chain on an otherwise idle chip; ride_old_ungated)
-  if (!rd->open && old_panel && ctx->ride_old_ungated && rd->held.empty()) return ride_panel_now(ctx, mat, T, p0, p1, rd, true);
+  if (!rd->open && old_panel && ctx->ride_old_ungated && rd->held.empty()) return ride_panel_now(ctx, F, T, p0, p1, rd, true);
   if (!rd->open) {
     if ((int64_t)(T - p1) * 100 > (int64_t)rd->gate_pct * T && p1 < T) {
       rd->held.emplace_back(p0, p1);
@@ -127,20 +144,18 @@ static int ride_panel(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, Ride*
     rd->open = true;
     bool first = true;
     for (auto& h : rd->held) {
-      LPGP_TRY(ride_panel_now(ctx, mat, T, h.first, h.second, rd, first));
+      LPGP_TRY(ride_panel_now(ctx, F, T, h.first, h.second, rd, first));
       first = false;
     }
     const bool none_held = rd->held.empty();
     rd->held.clear();
-    return ride_panel_now(ctx, mat, T, p0, p1, rd, true, resident && none_held);
+    return ride_panel_now(ctx, F, T, p0, p1, rd, true, resident && none_held);
   }
-  return ride_panel_now(ctx, mat, T, p0, p1, rd, true, resident);
+  return ride_panel_now(ctx, F, T, p0, p1, rd, true, resident);
 }
 
-static int ride_panel_now(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, Ride* rd, bool sync_first, bool resident) {
-  const int64_t ld = mat->cap, tb = TILE;
-  const double* a = mat->a;
-  const bool two = rd->stream2 != nullptr && rd->stream2 != rd->stream && rd->mtl >= 8;
+static int ride_panel_now(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ride* rd, bool sync_first, bool resident) {
+  const bool two = rd->stream2 != nullptr && rd->stream2 != rd->stream && rd->V.mtl >= 8;
   // A panel of the RESIDENT chain, a right-hand side of few columns: the panel step does not wait for the chain kernel to end
   // -- it follows the factor workgroup through the chain's own flags (chain.hip: panel_chain_v_kernel) and ends one tile solve
   // after it.  Its workgroups wait on the chip, one per CU, hence the bound on their number; the flag slot is recycled 32 chain
@@ -149,7 +164,7 @@ static int ride_panel_now(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, R
   //  in the way of -- made the step 0.5 ms slower, 50.7-50.9 against 50.2-50.3: by then the substitution lags the chain anyway,
   //  and 32 columns per workgroup is the slower panel step of the two when nothing is left to overlap with.)
   const bool vchain = resident && sync_first && !two && ctx->fused_solve && p1 - p0 == 4 && ctx->ride_vchain_max_wgs > 0 &&
-                      rd->mtl * 4 <= ctx->ride_vchain_max_wgs && ctx->chain_last_p0 == p0 && ctx->chain_launches - rd->chain_launches0 <= 24;
+                      rd->V.mtl * 4 <= ctx->ride_vchain_max_wgs && ctx->chain_last_p0 == p0 && ctx->chain_launches - rd->chain_launches0 <= 24;
   // ... and are not dispatched before the chain kernel itself can be (everything in front of it on the panel stream is done):
   // they would only hold their CUs waiting.  (Under a profiler that SERIALISES kernels -- rocprofv3 --pmc -- a follower that is
   // picked before its chain kernel waits out its poll limit and the step fails with a negative status: LPGP_RIDE_VCHAIN=0 there.)
@@ -157,7 +172,7 @@ static int ride_panel_now(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, R
   if (vchain) ++ctx->route.ride_vchain;
   if (two) ++ctx->route.ride_two;
   if (vchain)
-    LPGP_TRY(launch_panel_chain_v(ctx, rd->stream, mat, p0, rd->v + (int64_t)p0 * tb, rd->ldv, (int64_t)rd->mtl * tb, ctx->d_info_cur));
+    LPGP_TRY(launch_panel_chain_v(ctx, rd->stream, F, p0, rd->V.rows(p0), rd->V.ld, (int64_t)rd->V.mtl * TILE, ctx->d_info_cur));
   if (sync_first && (rd->stream != ctx->s_main || two)) {
     hipEvent_t ev = rd->ev[rd->it++ & 1];
     LPGP_HIP(hipEventRecord(ev, ctx->s_main));
@@ -183,39 +198,14 @@ static int ride_panel_now(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, R
     }
     for (int h = 0; h < halves; ++h) {
       hipStream_t sV = h == 0 ? rd->stream : rd->stream2;
-      const int c0 = (h == 0) ? 0 : rd->mtl / 2, c1 = (two && h == 0) ? rd->mtl / 2 : rd->mtl;       // tile columns of this half
-      double* vh = rd->v + (int64_t)c0 * tb * rd->ldv;
-      const int mtl = c1 - c0;
-      double* Vq = vh + (int64_t)q0 * tb;
-      if (vchain) {
-        // (done by panel_chain_v_kernel above)
-      } else if (ctx->fused_solve) {
-        LPGP_TRY(launch_trsv_panel(ctx, sV, Vq, rd->ldv, mat->linv + (int64_t)q0 * tb * tb, a + (int64_t)q0 * tb * (ld + 1), ld, q1 - q0, mtl,
-                                   LPGP_K_PANEL));
-      } else {
-        for (int jt = q0; jt < q1; ++jt) {
-          double* Vj = vh + (int64_t)jt * tb;
-          LPGP_TRY(launch_trsv_tile(ctx, sV, Vj, rd->ldv, mat->linv + (int64_t)jt * tb * tb, a + (int64_t)jt * tb * (ld + 1), ld, mtl, LPGP_K_TRSM));
-          if (jt + 1 < q1)
-            LPGP_TRY(launch_gemm(ctx, sV, 0, 1,
-                                 mk(a + (int64_t)(jt + 1) * tb + (int64_t)jt * tb * ld, ld, Vj, rd->ldv, vh + (int64_t)(jt + 1) * tb, rd->ldv,
-                                    q1 - jt - 1, mtl, TILE, -1.0, 1.0, 0),
-                                 LPGP_K_GEMM));
-        }
-      }
-      if (q1 < lim) {
-        GemmArgs g = mk(a + (int64_t)q1 * tb + (int64_t)q0 * tb * ld, ld, Vq, rd->ldv, vh + (int64_t)q1 * tb, rd->ldv, lim - q1, mtl,
-                        (q1 - q0) * TILE, -1.0, 1.0, 0);
-        g.occ3 = ctx->ride_occ3;
-        LPGP_TRY(launch_gemm(ctx, sV, 0, 1, g, LPGP_K_GEMM));
-      }
+      const int c0 = (h == 0) ? 0 : rd->V.mtl / 2, c1 = (two && h == 0) ? rd->V.mtl / 2 : rd->V.mtl;       // tile columns of this half
+      const RhsView V = rd->V.cols(c0, c1);
+      if (!vchain) LPGP_TRY(solve_panel(ctx, sV, F, V, q0, q1, ctx->fused_solve));      // (vchain: done by panel_chain_v_kernel above)
+      LPGP_TRY(rhs_update(ctx, sV, F, V, q0, q1, q1, lim, ctx->ride_occ3));
       if (outer_from >= 0 && outer_from < T) {
         // the outer block [outer_q0, q1) is solved: everything from its margin on in ONE update with K = its height
         if (h == 0) ++ctx->route.ride_outer;
-        GemmArgs g = mk(a + (int64_t)outer_from * tb + (int64_t)outer_q0 * tb * ld, ld, vh + (int64_t)outer_q0 * tb, rd->ldv,
-                        vh + (int64_t)outer_from * tb, rd->ldv, T - outer_from, mtl, (q1 - outer_q0) * TILE, -1.0, 1.0, 0);
-        g.occ3 = ctx->ride_occ3;
-        LPGP_TRY(launch_gemm(ctx, sV, 0, 1, g, LPGP_K_GEMM));
+        LPGP_TRY(rhs_update(ctx, sV, F, V, outer_q0, q1, outer_from, T, ctx->ride_occ3));
       }
     }
   }
@@ -229,11 +219,8 @@ static int ride_panel_now(lpgp_ctx* ctx, lpgp_mat* mat, int T, int p0, int p1, R
 // On return the panel stream is behind every update of the call.
 // TR >= T: the matrix has TR tile ROWS (rows beyond tile T belong to a block that is solved and updated but never factored: the
 // augmented form of potrf_predict_blocked); T stays the limit of the COLUMNS.
-static int factor_columns(lpgp_ctx* ctx, lpgp_mat* mat, int T, int c0, int cl, hipStream_t sU, hipEvent_t dep, Ride* ride, int TR) {
-  const int64_t ld = mat->cap;
-  double* a = mat->a;
+static int factor_columns(lpgp_ctx* ctx, FactorView F, int T, int c0, int cl, hipStream_t sU, hipEvent_t dep, Ride* ride, int TR) {
   const int nbt = (int)(ctx->nb / TILE);
-  const int64_t tb = TILE;
   hipStream_t sP = ctx->s_main;
   bool dep_pending_p = dep != nullptr, dep_pending_u = dep != nullptr;
   // Panel width schedule: while the trailing matrix is large the pipeline is bound by the
@@ -264,7 +251,7 @@ static int factor_columns(lpgp_ctx* ctx, lpgp_mat* mat, int T, int c0, int cl, h
     LPGP_CHECK(!ahead || resident, "factor_columns: a look-ahead update was left to a chain kernel that is not launched");
     if (resident) {
       if (ride && ride->stream != sP && ctx->ride_vchain_pre) LPGP_HIP(hipEventRecord(ctx->ev_chain_pre, sP));      // (see ride_panel_now: the step that follows the chain's flags)
-      LPGP_TRY(launch_panel_chain(ctx, sP, mat, p0, TR, ctx->d_info_cur, true, ahead));
+      LPGP_TRY(launch_panel_chain(ctx, sP, F, p0, TR, ctx->d_info_cur, true, ahead));
     }
     // ... a WIDER panel as two launches (round 6): the factor workgroup and the in-block rows (13 workgroups of 152 KB: thirteen CUs)
     // here, the rows below -- 16 per workgroup, 68 KB, two per CU -- on the outer-update stream, which is idle at these sizes and
@@ -276,39 +263,29 @@ static int factor_columns(lpgp_ctx* ctx, lpgp_mat* mat, int T, int c0, int cl, h
                            TR - p1 <= ctx->chain_resident2_max_rows && !ctx->distributed() && !ctx->single_stream && sR && sR != sP && ctx->ev_chain_rows;
     if (resident2) {
       LPGP_HIP(hipEventRecord(ctx->ev_chain_pre, sP));
-      LPGP_TRY(launch_panel_chain(ctx, sP, mat, p0, TR, ctx->d_info_cur, false));
+      LPGP_TRY(launch_panel_chain(ctx, sP, F, p0, TR, ctx->d_info_cur, false));
       LPGP_HIP(hipStreamWaitEvent(sR, ctx->ev_chain_pre, 0));
-      LPGP_TRY(launch_panel_chain_rows(ctx, sR, mat, p0, TR, ctx->d_info_cur));
+      LPGP_TRY(launch_panel_chain_rows(ctx, sR, F, p0, TR, ctx->d_info_cur));
       LPGP_HIP(hipEventRecord(ctx->ev_chain_rows, sR));
       LPGP_HIP(hipStreamWaitEvent(sP, ctx->ev_chain_rows, 0));
     }
     // ... else tile by tile
     for (int jt = p0; jt < p1 && !resident && !resident2; ++jt) {
-      double* dj = a + (int64_t)jt * tb * (ld + 1);
-      double* linv = mat->linv + (int64_t)jt * tb * tb;
-      LPGP_TRY(launch_potrf_tile(ctx, sP, dj, ld, linv, ctx->d_info_cur, jt * TILE));
+      LPGP_TRY(launch_potrf_tile(ctx, sP, F.diag(jt), F.ld, F.inv(jt), ctx->d_info_cur, jt * TILE));
       if (jt + 1 < TR) {
-        double* X = dj + tb;     // rows below, same tile column
-        LPGP_TRY(panel_trsm(ctx, sP, mat, jt, X, TR - jt - 1));
-        if (jt + 1 < p1)
-          LPGP_TRY(launch_gemm(ctx, sP, 0, 0,
-                               mk(X, ld, X, ld, a + (int64_t)(jt + 1) * tb * (ld + 1), ld, TR - jt - 1,
-                                  p1 - jt - 1, TILE, -1.0, 1.0, 2),
-                               LPGP_K_SYRK_PANEL));
+        LPGP_TRY(panel_trsm(ctx, sP, F, jt, F.tile(jt + 1, jt), TR - jt - 1));      // rows below, same tile column
+        if (jt + 1 < p1) LPGP_TRY(trailing_update(ctx, sP, F, jt, jt + 1, jt + 1, p1, TR, 2, LPGP_K_SYRK_PANEL));
       }
     }
-    if (ride) LPGP_TRY(ride_panel(ctx, mat, T, p0, p1, ride, false, resident));          // columns [p0, p1) are final: their substitution step follows on the ride stream
+    if (ride) LPGP_TRY(ride_panel(ctx, F, T, p0, p1, ride, false, resident));          // columns [p0, p1) are final: their substitution step follows on the ride stream
     if (p1 >= cl) break;
     const int K = (p1 - p0) * TILE;
-    const double* P = a + (int64_t)p1 * tb + (int64_t)p0 * tb * ld;      // panel rows below
     if (dep_pending_p) {
       LPGP_HIP(hipStreamWaitEvent(sP, dep, 0));
       dep_pending_p = false;
     }
     if (!la) {
-      LPGP_TRY(launch_gemm(ctx, sP, 0, 0,
-                           mk(P, ld, P, ld, a + (int64_t)p1 * tb * (ld + 1), ld, TR - p1, cl - p1, K, -1.0, 1.0, 1),
-                           LPGP_K_SYRK));
+      LPGP_TRY(trailing_update(ctx, sP, F, p0, p1, p1, cl, TR, 1, LPGP_K_SYRK));
       p0 = p1;
       continue;
     }
@@ -340,9 +317,7 @@ static int factor_columns(lpgp_ctx* ctx, lpgp_mat* mat, int T, int c0, int cl, h
     if (fuse_next) {
       ahead_next = true;
     } else {
-      LPGP_TRY(launch_gemm(ctx, sP, 0, 0,
-                           mk(P, ld, P, ld, a + (int64_t)p1 * tb * (ld + 1), ld, TR - p1, p2 - p1, K, -1.0, 1.0, 3),
-                           LPGP_K_SYRK_AHEAD));
+      LPGP_TRY(trailing_update(ctx, sP, F, p0, p1, p1, p2, TR, 3, LPGP_K_SYRK_AHEAD));
       if (chain_bound) LPGP_HIP(hipEventRecord(evp, sP));
     }
     // (b) remainder on an update stream.  Once its estimated duration even on the narrow stream
@@ -363,11 +338,9 @@ static int factor_columns(lpgp_ctx* ctx, lpgp_mat* mat, int T, int c0, int cl, h
         LPGP_HIP(hipStreamWaitEvent(sB, dep, 0));
         dep_pending_u = false;
       }
-      const double* P2 = a + (int64_t)p2 * tb + (int64_t)p0 * tb * ld;
       LPGP_HIP(hipStreamWaitEvent(sB, evp, 0));
-      GemmArgs gb = mk(P2, ld, P2, ld, a + (int64_t)p2 * tb * (ld + 1), ld, TR - p2, cl - p2, K, -1.0, 1.0, 1);
-      gb.occ3 = t_b_us > ctx->gemm3_margin * t_chain_us;       // (with gemm3_fact: three workgroups per CU only while the chain beside it has slack)
-      LPGP_TRY(launch_gemm(ctx, sB, 0, 0, gb, LPGP_K_SYRK));
+      const int occ3 = t_b_us > ctx->gemm3_margin * t_chain_us;       // (with gemm3_fact: three workgroups per CU only while the chain beside it has slack)
+      LPGP_TRY(trailing_update(ctx, sB, F, p0, p1, p2, cl, TR, 1, LPGP_K_SYRK, occ3));
       LPGP_HIP(hipEventRecord(ctx->ev_upd[it & 1], sB));
       have_upd_event = 1;
       last_upd = ctx->ev_upd[it & 1];
@@ -382,9 +355,11 @@ static int factor_columns(lpgp_ctx* ctx, lpgp_mat* mat, int T, int c0, int cl, h
 }
 
 // Factor tile columns [t_done, T) of the padded matrix; columns [0, t_done) already hold L.
-static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, int64_t T64, int32_t* info, Ride* ride, int TR = 0);
+static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, FactorView F, int64_t t_done64, int64_t T64, int32_t* info, Ride* ride, int TR = 0);
 int potrf_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, int64_t T64, int32_t* info) {
-  return potrf_blocked_impl(ctx, mat, t_done64, T64, info, nullptr);
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
+  return potrf_blocked_impl(ctx, mat, F, t_done64, T64, info, nullptr);
 }
 
 // dst[c + r * ldd] = src[r + c * lds] for r < rows, c < cols (both multiples of 32): 32 x 32 tiles through LDS
@@ -411,8 +386,10 @@ static int transpose(hipStream_t st, double* dst, int64_t ldd, const double* src
 // dimension ldv) riding inside it: on return (everything enqueued, the panel stream behind all of it) v holds L^{-1} v for
 // the WHOLE factor, old panels included.  Status as with info == nullptr: the matrix's sticky word.
 int potrf_predict_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t T, double* v, int64_t ldv, int64_t m_pad) {
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
   Ride rd;
-  rd.v = v; rd.ldv = ldv; rd.mtl = (int)(m_pad / TILE);
+  rd.V = RhsView{v, ldv, (int)(m_pad / TILE)};
   rd.chain_launches0 = ctx->chain_launches;
   // the ride streams: update streams that are idle during a factorisation of this size (HIP multiplexes a process's
   // streams over four hardware queues: no new stream).  ride_stream = first + 8 * second (second 7: none):
@@ -440,19 +417,19 @@ int potrf_predict_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t 
   if (t_done >= T) {
     // nothing left to factor: the plain substitution
     ++ctx->route.ride_done;
-    return trsm_lower_blocked(ctx, mat, T, v, ldv, m_pad);
+    return trsm_lower_blocked(ctx, F, T, v, ldv, m_pad);
   }
-  if (ctx->ride_aug && (T + rd.mtl) * (int64_t)TILE <= mat->cap && !ctx->single_stream) {
+  if (ctx->ride_aug && (T + rd.V.mtl) * (int64_t)TILE <= mat->cap && !ctx->single_stream) {
     // AUGMENTED form (round 6, option ride_aug): V^T = K_xX L^{-T} are ROWS of the matrix being factored -- the Cholesky of
     // [G; K_xX] without its last diagonal block (BlockMatrix2x2.L_A_inv_B, linops/_block.py:203-207, read row-wise).  The
     // substitution's updates then are tiles of the factorisation's own trailing-update launches (ONE grid, no second claimant
     // of the chip) and its panel steps rows of the panel chain's tile solves.  K_Xx is transposed into the free rows below the
     // matrix's blocks and back: 2 x 8 N M bytes through HBM.
     ++ctx->route.ride_aug;
-    double* vt = mat->a + T * (int64_t)TILE;
-    LPGP_TRY(transpose(ctx->s_main, vt, mat->cap, v, ldv, T * (int64_t)TILE, m_pad));
-    LPGP_TRY(potrf_blocked_impl(ctx, mat, t_done, T, nullptr, nullptr, (int)T + rd.mtl));
-    return transpose(ctx->s_main, v, ldv, vt, mat->cap, m_pad, T * (int64_t)TILE);
+    double* vt = F.tile((int)T, 0);
+    LPGP_TRY(transpose(ctx->s_main, vt, F.ld, v, ldv, T * (int64_t)TILE, m_pad));
+    LPGP_TRY(potrf_blocked_impl(ctx, mat, F, t_done, T, nullptr, nullptr, (int)T + rd.V.mtl));
+    return transpose(ctx->s_main, v, ldv, vt, F.ld, m_pad, T * (int64_t)TILE);
   }
   if (T >= ctx->ride_max_tiles) {
     // very large factors: the two pipelines back to back (no host synchronisation in between).  At c4 (520 tile rows, 129 tile
@@ -460,11 +437,11 @@ int potrf_predict_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t 
     // the chip to themselves for seconds and the chain-bound parts are a per-cent effect; riding inside costs 1.8 % there
     // (2 718 against 2 670 ms) where it gains 6 % at c3, 13 % at c2 and 3 % at c5.
     ++ctx->route.ride_b2b;
-    LPGP_TRY(potrf_blocked_impl(ctx, mat, t_done, T, nullptr, nullptr));
-    return trsm_lower_blocked(ctx, mat, T, v, ldv, m_pad);
+    LPGP_TRY(potrf_blocked_impl(ctx, mat, F, t_done, T, nullptr, nullptr));
+    return trsm_lower_blocked(ctx, F, T, v, ldv, m_pad);
   }
   ++ctx->route.ride;
-  LPGP_TRY(potrf_blocked_impl(ctx, mat, t_done, T, nullptr, &rd));
+  LPGP_TRY(potrf_blocked_impl(ctx, mat, F, t_done, T, nullptr, &rd));
   if (rd.stream != ctx->s_main) {
     LPGP_HIP(hipEventRecord(ctx->ev_ride[2], rd.stream));
     LPGP_HIP(hipStreamWaitEvent(ctx->s_main, ctx->ev_ride[2], 0));
@@ -476,13 +453,11 @@ int potrf_predict_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t 
   return 0;
 }
 
-static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, int64_t T64, int32_t* info, Ride* ride, int TR) {
+static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, FactorView F, int64_t t_done64, int64_t T64, int32_t* info, Ride* ride, int TR) {
   const int T = (int)T64, t_done = (int)t_done64;
   if (TR < T) TR = T;                                 // (TR > T: rows beyond the columns being factored, see factor_columns)
-  const int64_t ld = mat->cap;
-  double* a = mat->a;
+  const int64_t ld = F.ld;
   const int nbt = (int)(ctx->nb / TILE);
-  const int64_t tb = TILE;
   hipStream_t sP = ctx->s_main, sU = ctx->s_upd;
   // info != nullptr: the status is read back at the end (one host synchronisation); nullptr (lpgp_potrf_enqueue): it
   // accumulates in the matrix's own sticky word and is read by lpgp_mat_check
@@ -492,31 +467,25 @@ static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, in
   // ---- phase A (append): push the new rows through the already factored columns ----
   hipEvent_t append_dep = nullptr;
   if (t_done > 0 && T > t_done) {
-    const int mnew = TR - t_done;
-    double* rows = a + (int64_t)t_done * tb;          // row offset of the new rows
+    const int mnew = TR - t_done;                     // the new rows: tile rows [t_done, TR)
     for (int p0 = 0; p0 < t_done; p0 += nbt) {
       const int p1 = (p0 + nbt < t_done) ? p0 + nbt : t_done;
       if (ctx->fused_solve && p1 - p0 <= 4) {
         // the old panel's diagonal block is final: the chain of the new rows through it in one launch (panel_solve_kernel)
-        LPGP_TRY(launch_trsm_panel(ctx, sP, rows + (int64_t)p0 * tb * ld, ld, mat->linv + (int64_t)p0 * tb * tb,
-                                   a + (int64_t)p0 * tb * (ld + 1), ld, p1 - p0, mnew, LPGP_K_PANEL));
+        LPGP_TRY(launch_trsm_panel(ctx, sP, F.tile(t_done, p0), ld, F.inv(p0), F.diag(p0), ld, p1 - p0, mnew, LPGP_K_PANEL));
       } else
       for (int jt = p0; jt < p1; ++jt) {
-        double* X = rows + (int64_t)jt * tb * ld;
-        LPGP_TRY(panel_trsm(ctx, sP, mat, jt, X, mnew));
+        double* X = F.tile(t_done, jt);
+        LPGP_TRY(panel_trsm(ctx, sP, F, jt, X, mnew));
         if (jt + 1 < p1)
           LPGP_TRY(launch_gemm(ctx, sP, 0, 0,
-                               mk(X, ld, a + (int64_t)(jt + 1) * tb + (int64_t)jt * tb * ld, ld,
-                                  rows + (int64_t)(jt + 1) * tb * ld, ld, mnew, p1 - jt - 1, TILE, -1.0, 1.0, 0),
+                               mk(X, ld, F.tile(jt + 1, jt), ld, F.tile(t_done, jt + 1), ld, mnew, p1 - jt - 1, TILE, -1.0, 1.0, 0),
                                LPGP_K_GEMM));
       }
-      if (ride) LPGP_TRY(ride_panel(ctx, mat, T, p0, p1, ride, true));  // the old panel's columns, new rows included, are final
-      const int K = (p1 - p0) * TILE;
-      double* Xp = rows + (int64_t)p0 * tb * ld;
+      if (ride) LPGP_TRY(ride_panel(ctx, F, T, p0, p1, ride, true));  // the old panel's columns, new rows included, are final
       if (p1 < t_done)
         LPGP_TRY(launch_gemm(ctx, sP, 0, 0,
-                             mk(Xp, ld, a + (int64_t)p1 * tb + (int64_t)p0 * tb * ld, ld,
-                                rows + (int64_t)p1 * tb * ld, ld, mnew, t_done - p1, K, -1.0, 1.0, 0),
+                             mk(F.tile(t_done, p0), ld, F.tile(p1, p0), ld, F.tile(t_done, p1), ld, mnew, t_done - p1, (p1 - p0) * TILE, -1.0, 1.0, 0),
                              LPGP_K_GEMM));
       // Round 6: the update of the new block by the LAST old panel with the look-ahead split every other trailing update has -- the first
       // new panel's columns on the panel stream, its chain right behind them, the remainder on the update stream underneath that
@@ -525,20 +494,13 @@ static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, in
       const bool split = ctx->lookahead != 0 && ctx->append_split && p1 == t_done && (T - t_done) > nbt && mnew >= ctx->append_split_min_tiles &&
                          sU != sP && ctx->ev_append[0] && ctx->ev_append[1];
       if (!split) {
-        LPGP_TRY(launch_gemm(ctx, sP, 0, 0,
-                             mk(Xp, ld, Xp, ld, rows + (int64_t)t_done * tb * ld, ld, mnew, T - t_done, K, -1.0, 1.0, 1),
-                             LPGP_K_SYRK));
+        LPGP_TRY(trailing_update(ctx, sP, F, p0, p1, t_done, T, TR, 1, LPGP_K_SYRK));
       } else {
         const int c1 = t_done + nbt;
         LPGP_HIP(hipEventRecord(ctx->ev_append[0], sP));                   // the new rows are solved against the old panel
-        LPGP_TRY(launch_gemm(ctx, sP, 0, 0,
-                             mk(Xp, ld, Xp, ld, rows + (int64_t)t_done * tb * ld, ld, mnew, nbt, K, -1.0, 1.0, 3),
-                             LPGP_K_SYRK_AHEAD));
+        LPGP_TRY(trailing_update(ctx, sP, F, p0, p1, t_done, c1, TR, 3, LPGP_K_SYRK_AHEAD));
         LPGP_HIP(hipStreamWaitEvent(sU, ctx->ev_append[0], 0));
-        const double* Xq = Xp + (int64_t)nbt * tb;                           // rows from the second new panel on
-        LPGP_TRY(launch_gemm(ctx, sU, 0, 0,
-                             mk(Xq, ld, Xq, ld, a + (int64_t)c1 * tb * (ld + 1), ld, TR - c1, T - c1, K, -1.0, 1.0, 1),
-                             LPGP_K_SYRK));
+        LPGP_TRY(trailing_update(ctx, sU, F, p0, p1, c1, T, TR, 1, LPGP_K_SYRK));      // rows from the second new panel on
         LPGP_HIP(hipEventRecord(ctx->ev_append[1], sU));
         append_dep = ctx->ev_append[1];
       }
@@ -570,36 +532,26 @@ static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, in
   for (int q0 = t_done; q0 < T; ++oit) {
     const bool outer = la && NBt > nbt && (T - q0) > ctx->nb_outer_min_tiles && (T - q0) > NBt;
     const int q1 = outer ? q0 + NBt : T;
-    LPGP_TRY(factor_columns(ctx, mat, T, q0, q1, sU, ev_a1, ride, TR));
+    LPGP_TRY(factor_columns(ctx, F, T, q0, q1, sU, ev_a1, ride, TR));
     if (q1 >= T) break;
     hipEvent_t ev_fact = ctx->ev_outer_fact[oit & 1];
     LPGP_HIP(hipEventRecord(ev_fact, sP));             // outer panel [q0, q1) is final (factor_columns joins its updates into sP)
-    const int K = (q1 - q0) * TILE;
     const bool next_outer = (T - q1) > ctx->nb_outer_min_tiles && (T - q1) > NBt;
     const int q2 = next_outer ? q1 + NBt : T;
     const int qa = (q1 + nbt < q2) ? q1 + nbt : q2;    // end of the next outer panel's first inner panel
     // (a0) on the panel stream; its columns were last written by the previous (b)
     if (ev_b) LPGP_HIP(hipStreamWaitEvent(sP, ev_b, 0));
-    const double* P = a + (int64_t)q1 * tb + (int64_t)q0 * tb * ld;
-    LPGP_TRY(launch_gemm(ctx, sP, 0, 0,
-                         mk(P, ld, P, ld, a + (int64_t)q1 * tb * (ld + 1), ld, TR - q1, qa - q1, K, -1.0, 1.0, 3),
-                         LPGP_K_SYRK_AHEAD));
+    LPGP_TRY(trailing_update(ctx, sP, F, q0, q1, q1, qa, TR, 3, LPGP_K_SYRK_AHEAD));
     LPGP_HIP(hipStreamWaitEvent(sO, ev_fact, 0));
     ev_a1 = nullptr;
     if (qa < q2) {                                     // (a1): columns [qa, q2), rows [qa, T)
-      const double* Pa = a + (int64_t)qa * tb + (int64_t)q0 * tb * ld;
-      LPGP_TRY(launch_gemm(ctx, sO, 0, 0,
-                           mk(Pa, ld, Pa, ld, a + (int64_t)qa * tb * (ld + 1), ld, TR - qa, q2 - qa, K, -1.0, 1.0, 1),
-                           LPGP_K_SYRK));
+      LPGP_TRY(trailing_update(ctx, sO, F, q0, q1, qa, q2, TR, 1, LPGP_K_SYRK));
       ev_a1 = ctx->ev_outer_a1[oit & 1];
       LPGP_HIP(hipEventRecord(ev_a1, sO));
     }
     ev_b = nullptr;
     if (q2 < T) {                                      // (b): columns [q2, T)
-      const double* Pb = a + (int64_t)q2 * tb + (int64_t)q0 * tb * ld;
-      LPGP_TRY(launch_gemm(ctx, sO, 0, 0,
-                           mk(Pb, ld, Pb, ld, a + (int64_t)q2 * tb * (ld + 1), ld, TR - q2, T - q2, K, -1.0, 1.0, 1),
-                           LPGP_K_SYRK));
+      LPGP_TRY(trailing_update(ctx, sO, F, q0, q1, q2, T, TR, 1, LPGP_K_SYRK));
       ev_b = ctx->ev_outer[oit & 1];
       LPGP_HIP(hipEventRecord(ev_b, sO));
     }
@@ -654,16 +606,9 @@ int copy2d(hipStream_t st, double* dst, int64_t ldd, const double* src, int64_t 
 // 1063 ms; c5 (263) 80.2 / 78.8 / 80.9 / - ms; c3 (132) 22.9 / 22.7 / 23.6 / - ms; c2 (65) 2.80 / 2.69 / 2.87 / - ms: the
 // outer updates do run at the long-K rate, but with few outer blocks the inner work of the first block and the tail are not
 // hidden, and (a), (b) and the inner launches share one chip.  Used from 384 tile rows on, with blocks of 4096 rows.
-static int trsm_lower_two_level(lpgp_ctx* ctx, lpgp_mat* mat, int T, double* v, int64_t ldv, int mtl, int nbt, int NBt) {
-  const int64_t ld = mat->cap, tb = TILE;
-  const double* a = mat->a;
+static int trsm_lower_two_level(lpgp_ctx* ctx, FactorView F, int T, RhsView V, int nbt, int NBt) {
+  const int mtl = V.mtl;
   hipStream_t sP = ctx->s_main, sU = ctx->s_upd_all;
-  auto upd = [&](hipStream_t st, int c0, int c1, int r0, int r1) -> int {        // rows [r0, r1) -= L[rows, c0:c1] V[c0:c1]
-    if (r1 <= r0) return 0;
-    GemmArgs g = mk(a + (int64_t)r0 * tb + (int64_t)c0 * tb * ld, ld, v + (int64_t)c0 * tb, ldv, v + (int64_t)r0 * tb, ldv, r1 - r0, mtl,
-                    (c1 - c0) * TILE, -1.0, 1.0, 0);
-    return launch_gemm(ctx, st, 0, 1, g, LPGP_K_GEMM);
-  };
   bool have_upd_event = false;
   int it = 0;
   struct PadGuard { lpgp_ctx* c; ~PadGuard() { c->panel_lds_extra = 0; } } pad_guard{ctx};
@@ -673,9 +618,8 @@ static int trsm_lower_two_level(lpgp_ctx* ctx, lpgp_mat* mat, int T, double* v, 
     // inner: the block's own rows, right-looking by fused panels
     for (int p0 = q0; p0 < q1; p0 += nbt) {
       const int p1 = (p0 + nbt < q1) ? p0 + nbt : q1;
-      LPGP_TRY(launch_trsv_panel(ctx, sP, v + (int64_t)p0 * tb, ldv, mat->linv + (int64_t)p0 * tb * tb, a + (int64_t)p0 * tb * (ld + 1), ld,
-                                 p1 - p0, mtl, LPGP_K_PANEL));
-      LPGP_TRY(upd(sP, p0, p1, p1, q1));
+      LPGP_TRY(solve_panel(ctx, sP, F, V, p0, p1, true));
+      LPGP_TRY(rhs_update(ctx, sP, F, V, p0, p1, p1, q1));
     }
     if (q1 >= T) break;
     const int q2 = (q1 + NBt < T) ? q1 + NBt : T;
@@ -689,11 +633,11 @@ static int trsm_lower_two_level(lpgp_ctx* ctx, lpgp_mat* mat, int T, double* v, 
     hipEvent_t evp = ctx->ev_panel[it & 1];
     if (!chain_bound) LPGP_HIP(hipEventRecord(evp, sP));
     if (have_upd_event) LPGP_HIP(hipStreamWaitEvent(sP, ctx->ev_upd[(it + 1) & 1], 0));      // (a)'s rows: last written by the previous (b)
-    LPGP_TRY(upd(sP, q0, q1, q1, q2));
+    LPGP_TRY(rhs_update(ctx, sP, F, V, q0, q1, q1, q2));
     if (chain_bound) LPGP_HIP(hipEventRecord(evp, sP));
     if (q2 < T) {
       LPGP_HIP(hipStreamWaitEvent(sU, evp, 0));
-      LPGP_TRY(upd(sU, q0, q1, q2, T));
+      LPGP_TRY(rhs_update(ctx, sU, F, V, q0, q1, q2, T));
       LPGP_HIP(hipEventRecord(ctx->ev_upd[it & 1], sU));
       have_upd_event = true;
     } else {
@@ -709,10 +653,10 @@ static int trsm_lower_two_level(lpgp_ctx* ctx, lpgp_mat* mat, int T, double* v, 
 // Right-looking by panels with the same look-ahead as the factorisation: the latency-bound
 // tile steps of panel p+1 (products with tile inverses, K = 128) run on the panel stream while
 // the update stream still applies panel p to the rows below.
-int trsm_lower_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int64_t ldv, int64_t m_pad) {
+int trsm_lower_blocked(lpgp_ctx* ctx, FactorView F, int64_t T64, double* v, int64_t ldv, int64_t m_pad) {
   const int T = (int)T64;
-  const int64_t ld = mat->cap, tb = TILE;
   const int mtl = (int)(m_pad / TILE);
+  const RhsView V{v, ldv, mtl};
   // panel width of the substitution: its chain has no tile Cholesky, so wider panels (longer K in the
   // updates) pay earlier than in the factorisation.  Measured (nb_solve = 512 / 768 / 1024 / 2048):
   // c2 (65 tile rows) 9.57 / - / 9.74 / - ms, c3 (132) 55.5 / 55.1 / 56.1 / - ms, c4 (520) 2702 / - / 2671 /
@@ -724,13 +668,12 @@ int trsm_lower_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int
   const int64_t nb_auto = T >= 384 ? 2048 : ((ctx->fused_solve && T <= 192) ? 512 : (T >= 96 ? 768 : ctx->nb));
   const int nbt = (int)((ctx->nb_solve > 0 ? ctx->nb_solve : nb_auto) / TILE);
   const bool fused = ctx->fused_solve && nbt <= 4;
-  const double* a = mat->a;
   const bool la = ctx->lookahead != 0 && mtl >= 8;       // worth it only for wide right-hand sides
   {
     const int NBt = (int)(ctx->nb_outer_solve / TILE), nbi = (int)(ctx->nb / TILE);
     if (la && ctx->fused_solve && ctx->nb_solve == 0 && nbi <= 4 && NBt > nbi && NBt % nbi == 0 && T >= ctx->nb_outer_solve_min_tiles && T >= 2 * NBt) {
       ++ctx->route.solve_two_level;
-      return trsm_lower_two_level(ctx, mat, T, v, ldv, mtl, nbi, NBt);
+      return trsm_lower_two_level(ctx, F, T, V, nbi, NBt);
     }
   }
   hipStream_t sP = ctx->s_main, sU = la ? ctx->s_upd_all : ctx->s_main;
@@ -747,33 +690,28 @@ int trsm_lower_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int
   ctx->panel_lds_extra = pad_blocked;
   const bool ahead_ok = fused && la && nbt == 4 && ctx->fused_ahead != 0;
   bool solved = false;                      // the panel at the top of the loop has been solved by the previous iteration's fused launch
+  // (b): the remainder update by panel [p0, p1) -- rows [p2, T) -- on the update stream, behind `evp`
+  auto release_b = [&](int p0, int p1, int p2, double t_b_us, hipEvent_t evp) -> int {
+    have_upd_event = p2 < T;
+    if (p2 >= T) return 0;
+    LPGP_HIP(hipStreamWaitEvent(sU, evp, 0));
+    const int occ3 = t_b_us > ctx->gemm3_margin * (ctx->solve_chain_us_tile * (double)(p2 - p1) + ctx->chain_us_fixed);
+    LPGP_TRY(rhs_update(ctx, sU, F, V, p0, p1, p2, T, occ3));
+    LPGP_HIP(hipEventRecord(ctx->ev_upd[it & 1], sU));
+    return 0;
+  };
   for (int p0 = 0; p0 < T; p0 += nbt, ++it) {
     const int p1 = (p0 + nbt < T) ? p0 + nbt : T;
-    if (solved)
+    if (solved) {
       solved = false;
-    else if (fused)
-      LPGP_TRY(launch_trsv_panel(ctx, sP, v + (int64_t)p0 * tb, ldv, mat->linv + (int64_t)p0 * tb * tb, a + (int64_t)p0 * tb * (ld + 1), ld,
-                                 p1 - p0, mtl, LPGP_K_PANEL));
-    else
-    for (int jt = p0; jt < p1; ++jt) {
-      if (jt == p0) ++ctx->route.solve_tiles;
-      double* Vj = v + (int64_t)jt * tb;
-      LPGP_TRY(launch_trsv_tile(ctx, sP, Vj, ldv, mat->linv + (int64_t)jt * tb * tb, a + (int64_t)jt * tb * (ld + 1), ld, mtl,
-                                LPGP_K_TRSM));
-      if (jt + 1 < p1)
-        LPGP_TRY(launch_gemm(ctx, sP, 0, 1,
-                             mk(a + (int64_t)(jt + 1) * tb + (int64_t)jt * tb * ld, ld, Vj, ldv,
-                                v + (int64_t)(jt + 1) * tb, ldv, p1 - jt - 1, mtl, TILE, -1.0, 1.0, 0),
-                             LPGP_K_GEMM));
+    } else {
+      if (!fused) ++ctx->route.solve_tiles;
+      LPGP_TRY(solve_panel(ctx, sP, F, V, p0, p1, fused));
     }
     if (p1 >= T) break;
     const int K = (p1 - p0) * TILE;
-    const double* Vp = v + (int64_t)p0 * tb;
     if (!la) {
-      LPGP_TRY(launch_gemm(ctx, sP, 0, 1,
-                           mk(a + (int64_t)p1 * tb + (int64_t)p0 * tb * ld, ld, Vp, ldv, v + (int64_t)p1 * tb, ldv,
-                              T - p1, mtl, K, -1.0, 1.0, 0),
-                           LPGP_K_GEMM));
+      LPGP_TRY(rhs_update(ctx, sP, F, V, p0, p1, p1, T));
       continue;
     }
     const int p2 = (p1 + nbt < T) ? p1 + nbt : T;
@@ -787,38 +725,16 @@ int trsm_lower_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int
       LPGP_HIP(hipEventRecord(evp, sP));                                                   // panel [p0, p1) is solved
       if (have_upd_event) LPGP_HIP(hipStreamWaitEvent(sP, ctx->ev_upd[(it + 1) & 1], 0));     // rows [p1, p2): last written by the previous remainder update
       ++ctx->route.solve_ahead;
-      LPGP_TRY(launch_trsv_panel_ahead(ctx, sP, v + (int64_t)p1 * tb, ldv, mat->linv + (int64_t)p1 * tb * tb, a + (int64_t)p1 * tb * (ld + 1),
-                                       a + (int64_t)p1 * tb + (int64_t)p0 * tb * ld, ld, p2 - p1, mtl, LPGP_K_PANEL));
+      LPGP_TRY(launch_trsv_panel_ahead(ctx, sP, V.rows(p1), V.ld, F.inv(p1), F.diag(p1), F.tile(p1, p0), F.ld, p2 - p1, mtl, LPGP_K_PANEL));
       solved = true;
-      if (p2 < T) {
-        LPGP_HIP(hipStreamWaitEvent(sU, evp, 0));
-        GemmArgs gb = mk(a + (int64_t)p2 * tb + (int64_t)p0 * tb * ld, ld, Vp, ldv, v + (int64_t)p2 * tb, ldv, T - p2, mtl, K, -1.0, 1.0, 0);
-        gb.occ3 = t_b_us > ctx->gemm3_margin * (ctx->solve_chain_us_tile * (double)(p2 - p1) + ctx->chain_us_fixed);
-        LPGP_TRY(launch_gemm(ctx, sU, 0, 1, gb, LPGP_K_GEMM));
-        LPGP_HIP(hipEventRecord(ctx->ev_upd[it & 1], sU));
-        have_upd_event = true;
-      } else {
-        have_upd_event = false;
-      }
+      LPGP_TRY(release_b(p0, p1, p2, t_b_us, evp));
       continue;
     }
     if (!chain_bound) LPGP_HIP(hipEventRecord(evp, sP));
     if (have_upd_event) LPGP_HIP(hipStreamWaitEvent(sP, ctx->ev_upd[(it + 1) & 1], 0));
-    LPGP_TRY(launch_gemm(ctx, sP, 0, 1,
-                         mk(a + (int64_t)p1 * tb + (int64_t)p0 * tb * ld, ld, Vp, ldv, v + (int64_t)p1 * tb, ldv,
-                            p2 - p1, mtl, K, -1.0, 1.0, 0),
-                         LPGP_K_GEMM));
+    LPGP_TRY(rhs_update(ctx, sP, F, V, p0, p1, p1, p2));
     if (chain_bound) LPGP_HIP(hipEventRecord(evp, sP));
-    if (p2 < T) {
-      LPGP_HIP(hipStreamWaitEvent(sU, evp, 0));
-      GemmArgs gb = mk(a + (int64_t)p2 * tb + (int64_t)p0 * tb * ld, ld, Vp, ldv, v + (int64_t)p2 * tb, ldv, T - p2, mtl, K, -1.0, 1.0, 0);
-      gb.occ3 = t_b_us > ctx->gemm3_margin * (ctx->solve_chain_us_tile * (double)(p2 - p1) + ctx->chain_us_fixed);
-      LPGP_TRY(launch_gemm(ctx, sU, 0, 1, gb, LPGP_K_GEMM));
-      LPGP_HIP(hipEventRecord(ctx->ev_upd[it & 1], sU));
-      have_upd_event = true;
-    } else {
-      have_upd_event = false;
-    }
+    LPGP_TRY(release_b(p0, p1, p2, t_b_us, evp));
   }
   if (la) {
     LPGP_HIP(hipEventRecord(ctx->ev_upd[0], sU));
@@ -828,12 +744,12 @@ int trsm_lower_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int
 }
 
 // V <- L^{-T} V (backward substitution), same layout.
-int trsm_lower_t_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, int64_t ldv, int64_t m_pad) {
+int trsm_lower_t_blocked(lpgp_ctx* ctx, FactorView F, int64_t T64, double* v, int64_t ldv, int64_t m_pad) {
   const int T = (int)T64;
-  const int64_t ld = mat->cap, tb = TILE;
+  const int64_t ld = F.ld, tb = TILE;
   const int mtl = (int)(m_pad / TILE);
+  const RhsView V{v, ldv, mtl};
   const int nbt = (int)(ctx->nb / TILE);
-  const double* a = mat->a;
   hipStream_t st = ctx->s_main;
   DevBuf sbuf;                                   // (reuse is stream-ordered)
   LPGP_TRY(DevBuf::pool(ctx, (size_t)TILE * (size_t)m_pad * sizeof(double), &sbuf));
@@ -841,26 +757,20 @@ int trsm_lower_t_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, i
   for (int p1 = T; p1 > 0;) {
     const int p0 = (p1 - nbt > 0) ? p1 - nbt : 0;
     for (int jt = p1 - 1; jt >= p0; --jt) {
-      double* Vj = v + (int64_t)jt * tb;
+      double* Vj = V.rows(jt);
       // x_jt = L_jj^{-T} y_jt with one refinement step (see tile_solve_kernel): S = Linv^T y;  y <- y - L^T S;
       // S <- S + Linv^T y;  y <- S.  (Not a hot path: `gram.solve(B)` / lpgp_potrs only.)
-      const double* linv = mat->linv + (int64_t)jt * tb * tb;
-      const double* Ljj = a + (int64_t)jt * tb * (ld + 1);
+      const double* linv = F.inv(jt);
+      const double* Ljj = F.diag(jt);
       LPGP_TRY(launch_gemm(ctx, st, 1, 1, mk(linv, tb, Vj, ldv, S, tb, 1, mtl, TILE, 1.0, 0.0, 0), LPGP_K_TRSM));
       LPGP_TRY(launch_gemm(ctx, st, 1, 1, mk(Ljj, ld, S, tb, Vj, ldv, 1, mtl, TILE, -1.0, 1.0, 0), LPGP_K_TRSM));
       LPGP_TRY(launch_gemm(ctx, st, 1, 1, mk(linv, tb, Vj, ldv, S, tb, 1, mtl, TILE, 1.0, 1.0, 0), LPGP_K_TRSM));
       LPGP_TRY(copy2d(st, Vj, ldv, S, tb, tb, m_pad));
       if (jt > p0)
-        LPGP_TRY(launch_gemm(ctx, st, 1, 1,
-                             mk(a + (int64_t)jt * tb + (int64_t)p0 * tb * ld, ld, Vj, ldv,
-                                v + (int64_t)p0 * tb, ldv, jt - p0, mtl, TILE, -1.0, 1.0, 0),
-                             LPGP_K_GEMM));
+        LPGP_TRY(launch_gemm(ctx, st, 1, 1, mk(F.tile(jt, p0), ld, Vj, ldv, V.rows(p0), ldv, jt - p0, mtl, TILE, -1.0, 1.0, 0), LPGP_K_GEMM));
     }
     if (p0 > 0)
-      LPGP_TRY(launch_gemm(ctx, st, 1, 1,
-                           mk(a + (int64_t)p0 * tb, ld, v + (int64_t)p0 * tb, ldv, v, ldv, p0, mtl,
-                              (p1 - p0) * TILE, -1.0, 1.0, 0),
-                           LPGP_K_GEMM));
+      LPGP_TRY(launch_gemm(ctx, st, 1, 1, mk(F.tile(p0, 0), ld, V.rows(p0), ldv, v, ldv, p0, mtl, (p1 - p0) * TILE, -1.0, 1.0, 0), LPGP_K_GEMM));
     p1 = p0;
   }
   return 0;
@@ -1014,35 +924,30 @@ __global__ __launch_bounds__(512) void trsv_bwd_step_kernel(const double* __rest
 }
 
 // x <- L^{-1} b on `st` (padded length T*128, device); b is consumed as the running right-hand side
-int solve_vec_fwd(lpgp_ctx* ctx, hipStream_t st, lpgp_mat* mat, int64_t T64, double* b, double* x) {
+int solve_vec_fwd(lpgp_ctx* ctx, hipStream_t st, FactorView F, int64_t T64, double* b, double* x) {
   const int T = (int)T64;
-  const int64_t ld = mat->cap;
-  const double* a = mat->a;
-  auto linv = [&](int k) { return (const double*)(mat->linv + (int64_t)k * TILE * TILE); };
-  hipLaunchKernelGGL(trsv_fwd_head_kernel, dim3(1), dim3(512), 0, st, linv(0), a, ld, (const double*)b, x);
+  const double* a = F.a;
+  hipLaunchKernelGGL(trsv_fwd_head_kernel, dim3(1), dim3(512), 0, st, (const double*)F.inv(0), a, F.ld, (const double*)b, x);
   for (int k = 0; k + 1 < T; ++k)
-    hipLaunchKernelGGL(trsv_fwd_step_kernel, dim3(T - k - 1), dim3(512), 0, st, a, ld, linv(k + 1), b, x,
+    hipLaunchKernelGGL(trsv_fwd_step_kernel, dim3(T - k - 1), dim3(512), 0, st, a, F.ld, (const double*)F.inv(k + 1), b, x,
                        (int64_t)k * TILE);
   LPGP_HIP(hipGetLastError());
   return 0;
 }
 
 // v (padded length T*128, device) <- G^{-1} v, using scratch vector `tmp` of the same length
-int solve_vec(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, double* tmp, int* info) {
-  if (ctx->trsv_resident) return solve_vec_resident(ctx, mat, T64, v, tmp, info);
+int solve_vec(lpgp_ctx* ctx, FactorView F, int64_t T64, double* v, double* tmp, int* info) {
+  if (ctx->trsv_resident) return solve_vec_resident(ctx, F, T64, v, tmp, info);
   const int T = (int)T64;
-  const int64_t ld = mat->cap;
   hipStream_t st = ctx->s_main;
-  const double* a = mat->a;
-  auto linv = [&](int k) { return (const double*)(mat->linv + (int64_t)k * TILE * TILE); };
+  const double* a = F.a;
   // forward: L tmp = v   (v is consumed as the running right-hand side)
-  int rc = solve_vec_fwd(ctx, st, mat, T64, v, tmp);
-  if (rc != 0) return rc;
+  LPGP_TRY(solve_vec_fwd(ctx, st, F, T64, v, tmp));
   // backward: L^T v = tmp  (tmp is consumed as the running right-hand side)
-  hipLaunchKernelGGL(trsv_bwd_head_kernel, dim3(1), dim3(512), 0, st, linv(T - 1), a + (int64_t)(T - 1) * TILE * (ld + 1), ld,
+  hipLaunchKernelGGL(trsv_bwd_head_kernel, dim3(1), dim3(512), 0, st, (const double*)F.inv(T - 1), (const double*)F.diag(T - 1), F.ld,
                      (const double*)(tmp + (int64_t)(T - 1) * TILE), v + (int64_t)(T - 1) * TILE);
   for (int k = T - 1; k >= 1; --k)
-    hipLaunchKernelGGL(trsv_bwd_step_kernel, dim3(k), dim3(512), 0, st, a, ld, linv(k - 1), tmp, v, (int64_t)k * TILE);
+    hipLaunchKernelGGL(trsv_bwd_step_kernel, dim3(k), dim3(512), 0, st, a, F.ld, (const double*)F.inv(k - 1), tmp, v, (int64_t)k * TILE);
   LPGP_HIP(hipGetLastError());
   return 0;
 }

@@ -247,6 +247,8 @@ int lpgp_test_solve_vec_fwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, 
   LPGP_CHECK(!mat->unchecked, "lpgp_test_solve_vec_fwd: the status of an enqueued factorisation has not been read (lpgp_mat_check)");
   const int64_t pn = mat->pn, T = pn / TILE;
   hipStream_t st = ctx->s_main;
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
   std::vector<double> h((size_t)pn, 0.0);
   int info = 0;
   for (const auto& b : mat->blocks) std::memcpy(h.data() + b.poff, r_host + b.off, (size_t)b.n * sizeof(double));
@@ -257,8 +259,8 @@ int lpgp_test_solve_vec_fwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, 
   StreamDrain drain{st};                         // (the staging vector, the status word and the caller's array are borrowed by the copies)
   LPGP_HIP(hipMemcpyAsync(d, h.data(), (size_t)pn * sizeof(double), hipMemcpyHostToDevice, st));
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
-  if (ctx->trsv_resident) LPGP_TRY(solve_vec_fwd_resident(ctx, mat, T, d, d + pn, ctx->d_info));
-  else LPGP_TRY(solve_vec_fwd(ctx, st, mat, T, d, d + pn));
+  if (ctx->trsv_resident) LPGP_TRY(solve_vec_fwd_resident(ctx, F, T, d, d + pn, ctx->d_info));
+  else LPGP_TRY(solve_vec_fwd(ctx, st, F, T, d, d + pn));
   LPGP_HIP(hipMemcpyAsync(z_host_padded, d + pn, (size_t)pn * sizeof(double), hipMemcpyDeviceToHost, st));
   LPGP_HIP(hipMemcpyAsync(&info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, st));
   LPGP_TRY(drain.wait());

@@ -297,9 +297,9 @@ __global__ __launch_bounds__(512, 1) void trsv_bwd_resident_kernel(TrsvArgs g) {
   if (t < TILE) trsv_st(g.x + (int64_t)i * TILE + t, xi);
 }
 
-static TrsvArgs trsv_args(const lpgp_mat* mat, int T, int* info) {
+static TrsvArgs trsv_args(FactorView F, int T, int* info) {
   TrsvArgs g;
-  g.L = mat->a; g.ld = mat->cap; g.linv = mat->linv; g.info = info; g.T = T;
+  g.L = F.a; g.ld = F.ld; g.linv = F.linv; g.info = info; g.T = T;
   static const int dbg_flags = [] { const char* e = std::getenv("LPGP_TRSV_FLAGS"); return e ? std::atoi(e) : 0; }();
   g.flags = dbg_flags;
   return g;
@@ -307,10 +307,10 @@ static TrsvArgs trsv_args(const lpgp_mat* mat, int T, int* info) {
 
 // x <- L^{-1} b on the panel stream, the forward half alone (lpgp_mat_evidence: z = L^{-1} r); b is read only, x has
 // T * 128 + 1 doubles (the last one carries the ticket word).  `info` as below.
-int solve_vec_fwd_resident(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, const double* b, double* x, int* info) {
+int solve_vec_fwd_resident(lpgp_ctx* ctx, FactorView F, int64_t T64, const double* b, double* x, int* info) {
   const int T = (int)T64;
   hipStream_t st = ctx->s_main;
-  TrsvArgs g = trsv_args(mat, T, info);
+  TrsvArgs g = trsv_args(F, T, info);
   LPGP_HIP(hipMemsetAsync(x, 0xFF, ((size_t)T * TILE + 1) * sizeof(double), st));           // the sentinel, and the ticket at -1
   g.b = b; g.x = x; g.ticket = reinterpret_cast<int*>(x + (size_t)T * TILE);
   prof_begin(ctx, st, LPGP_K_TRSM, (double)T * TILE * (double)T * TILE, 4.0 * (double)T * TILE * (double)T * TILE);
@@ -322,11 +322,11 @@ int solve_vec_fwd_resident(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, const doub
 
 // v (padded length T * 128, device) <- G^{-1} v on the panel stream; tmp: T * 128 + 2 doubles of scratch (the intermediate
 // vector and the two ticket words).  `info`: device status word (zeroed by the caller), INT_MIN after a timed-out hand-over.
-int solve_vec_resident(lpgp_ctx* ctx, lpgp_mat* mat, int64_t T64, double* v, double* tmp, int* info) {
+int solve_vec_resident(lpgp_ctx* ctx, FactorView F, int64_t T64, double* v, double* tmp, int* info) {
   const int T = (int)T64;
   hipStream_t st = ctx->s_main;
   const size_t nb = (size_t)T * TILE * sizeof(double);
-  TrsvArgs g = trsv_args(mat, T, info);
+  TrsvArgs g = trsv_args(F, T, info);
   // forward: L tmp = v
   LPGP_HIP(hipMemsetAsync(tmp, 0xFF, nb + 2 * sizeof(double), st));           // the sentinel, and both tickets at -1
   g.b = v; g.x = tmp; g.ticket = reinterpret_cast<int*>(tmp + (size_t)T * TILE);
