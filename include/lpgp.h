@@ -112,7 +112,8 @@ int  lpgp_sync(lpgp_ctx* ctx);                       /* hipDeviceSynchronize */
  * (read by lpgp_init), its default and the values it accepts.  get reads every row, and also the read-only state
  * "live_mats" and "route_*" (route counters of the forward substitution); set refuses the rows read at init only
  * (reserve_cus, reserve_narrow, single_stream).  Beside the table: "inverse_diag_panel" (get / set; lpgp_mat_inverse_diag)
- * and the read-only byte counters "evidence_h2d_bytes" / "evidence_d2h_bytes".                                     */
+ * and "cv_fold_batch" (get / set; lpgp_mat_cv), and the read-only byte counters "evidence_h2d_bytes" /
+ * "evidence_d2h_bytes".                                                                                              */
 int  lpgp_set_option(lpgp_ctx* ctx, const char* key, int64_t value);
 int  lpgp_get_option(lpgp_ctx* ctx, const char* key, int64_t* value);
 
@@ -468,6 +469,30 @@ int  lpgp_mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, 
  * goes through lpgp_mat_add_dense into a scratch matrix and lpgp_mat_evidence_grad.                                         */
 int  lpgp_mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, int32_t bi, const double* v_host, double scalar,
                                  const double* r_host, double out_host[2]);
+
+/* ---- leave-fold-out cross-validation from the resident factor (csrc/evidence_cv.hip): the predictive distribution of a whole
+ *      fold B of observations given all the others (GPML section 5.4.2, the block form of eqs. 5.10 - 5.12).  With
+ *      P = G^{-1} (ginv), w = G^{-1} r, S = P[B, B] (b x b, b = |B|):
+ *        mean_B = y_B - S^{-1} w_B,   Sigma_B = S^{-1},   log p(y_B | y_-B) = -1/2 w_B^T S^{-1} w_B + 1/2 log det S - b/2 log 2 pi
+ *      (Sigma_B is the covariance of the noisy y_B, as in lpgp_mat_loo).  b = 1 is lpgp_mat_loo, B = all rows the log marginal
+ *      likelihood; no fold costs a conditioning.  A fully factored matrix or view, single GPU, the refusals of lpgp_mat_loo;
+ *      refused besides, with the matrix untouched: a ginv of another layout, a fold_of entry out of range, an empty fold.
+ *      w is solved on the device as lpgp_mat_loo does; the resident weights and residual of the matrix are not touched.
+ *      Folds of at most 128 rows: S gathered into a 128 x 128 scratch tile (identity tail), factored and inverted by the tile
+ *      Cholesky of the factorisation, one workgroup per fold, and reduced by an epilogue kernel -- three launches for a whole
+ *      batch of folds (option "cv_fold_batch", get / set, 1 .. 65 535, default 512: 256 KiB of scratch per fold).  A larger fold:
+ *      S gathered into a scratch matrix of one block and handed to lpgp_potrf (per-tile launches, the resident panel chain off:
+ *      both paths factor S with the Newton sign in the tile Cholesky's pivot correction, csrc/potrf_tile.h), lpgp_mat_evidence's reduction, the single-vector
+ *      solve, lpgp_mat_inverse_diag's panels and (for the covariance) lpgp_mat_inverse, one fold at a time.  A fold whose S has
+ *      a pivot that is not positive fails the call with an error that names the fold; the outputs are written only on success.
+ *      The same bits on every call (every sum in a fixed order, the total over the folds in fold order, no atomics); O(n)
+ *      numbers cross the bus, and the covariances if asked for (counted in "evidence_h2d_bytes" / "evidence_d2h_bytes").        */
+/* fold_of[i] in -1 .. nfolds-1 for every LOGICAL row i (Gram order); -1: the row is in no fold.  Every fold non-empty.
+ * ginv: lpgp_mat_inverse(mat) (same block layout; checked).  mean_host / var_host: n doubles (rows in no fold: NaN).
+ * logp_host: nfolds + 1 doubles, [nfolds] = sum over the folds in fold order.  cov_host: NULL, or the fold covariances
+ * one after another in fold order, b_f x b_f C-order each, rows of a fold in increasing Gram order.                  */
+int  lpgp_mat_cv(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const double* r_host, const double* y_host,
+                 const int32_t* fold_of, int32_t nfolds, double* mean_host, double* var_host, double* logp_host, double* cov_host);
 
 /* diag of sum_g (kd[g])(x, x): a constant for the stationary kernels supported here     */
 int  lpgp_kernel_diag(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, double* out_value);

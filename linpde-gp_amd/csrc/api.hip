@@ -507,10 +507,11 @@ static const struct { const char* key; int64_t lpgp_ctx::RouteCounts::*count; } 
     ROUTE(ride_done), ROUTE(ride_aug), ROUTE(ride_b2b), ROUTE(ride), ROUTE(ride_vchain), ROUTE(ride_two), ROUTE(ride_outer),
     ROUTE(solve_two_level), ROUTE(solve_ahead), ROUTE(solve_tiles)};
 #undef ROUTE
-// the context state of evidence.hip, beside the option table like the rows above: the panel width of the inverse diagonal (the
-// one key of these that lpgp_set_option takes) and the byte counters of its copies
+// the context state of evidence.hip and evidence_cv.hip, beside the option table like the rows above: the panel width of the inverse
+// diagonal and the fold batch of the cross-validation (the two keys of these that lpgp_set_option takes), the byte counters of their copies
 static const struct { const char* key; int64_t lpgp_ctx::*field; } kEvidence[] = {
-    {"inverse_diag_panel", &lpgp_ctx::inverse_diag_panel}, {"evidence_h2d_bytes", &lpgp_ctx::evidence_h2d_bytes}, {"evidence_d2h_bytes", &lpgp_ctx::evidence_d2h_bytes}};
+    {"inverse_diag_panel", &lpgp_ctx::inverse_diag_panel}, {"cv_fold_batch", &lpgp_ctx::cv_fold_batch},
+    {"evidence_h2d_bytes", &lpgp_ctx::evidence_h2d_bytes}, {"evidence_d2h_bytes", &lpgp_ctx::evidence_d2h_bytes}};
 
 int lpgp_get_option(lpgp_ctx* ctx, const char* key, int64_t* value) {
   LPGP_CHECK(ctx && key && value, "lpgp_get_option: null argument");
@@ -538,6 +539,11 @@ int lpgp_set_option(lpgp_ctx* ctx, const char* key, int64_t value) {
   if (key && std::strcmp(key, kEvidence[0].key) == 0) {
     LPGP_CHECK(value >= TILE && value <= 4096 && value % TILE == 0, "inverse_diag_panel must be a multiple of %d in %d .. 4096", TILE, TILE);
     ctx->inverse_diag_panel = value;
+    return 0;
+  }
+  if (key && std::strcmp(key, kEvidence[1].key) == 0) {
+    LPGP_CHECK(value >= 1 && value <= 65535, "cv_fold_batch must lie in 1 .. 65535 (folds per launch, 256 KiB of scratch each)");
+    ctx->cv_fold_batch = value;
     return 0;
   }
   return option_set(*ctx, key, value);
@@ -1865,6 +1871,15 @@ int lpgp_mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* gi
   LPGP_CHECK(bi >= 0 && bi < (int32_t)mat->blocks.size(), "lpgp_mat_evidence_grad_diag: bad block %d", bi);
   LPGP_TRY(evidence_grad_layout(mat, ginv, "lpgp_mat_evidence_grad_diag", "the inverse"));
   return mat_evidence_grad_diag(ctx, mat, ginv, bi, v_host, scalar, r_host, out_host);
+}
+
+int lpgp_mat_cv(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const double* r_host, const double* y_host, const int32_t* fold_of, int32_t nfolds,
+                double* mean_host, double* var_host, double* logp_host, double* cov_host) {
+  LPGP_CHECK(ctx && mat && ginv && r_host && y_host && fold_of && mean_host && var_host && logp_host, "lpgp_mat_cv: null argument");
+  LPGP_EVIDENCE_READY("lpgp_mat_cv");
+  LPGP_CHECK(nfolds >= 1, "lpgp_mat_cv: %d folds", nfolds);
+  LPGP_TRY(evidence_grad_layout(mat, ginv, "lpgp_mat_cv", "the inverse"));
+  return mat_cv(ctx, mat, ginv, r_host, y_host, fold_of, nfolds, mean_host, var_host, logp_host, cov_host);
 }
 #undef LPGP_EVIDENCE_READY
 

@@ -149,7 +149,7 @@ static int ev_check_status(double v, const char* fn) {
 
 // the host staging of a call: nvec logical vectors scattered into the padded layout (zeros in the padding rows), behind them the
 // map padded row -> logical row (-1: padding) as pn int32
-static void ev_stage(const lpgp_mat* mat, const double* const* vecs, int nvec, std::vector<double>* h) {
+void ev_stage(const lpgp_mat* mat, const double* const* vecs, int nvec, std::vector<double>* h) {
   const int64_t pn = mat->pn;
   h->assign((size_t)(nvec * pn + (pn + 1) / 2), 0.0);
   int32_t* lrow = reinterpret_cast<int32_t*>(h->data() + (size_t)nvec * pn);
@@ -160,12 +160,12 @@ static void ev_stage(const lpgp_mat* mat, const double* const* vecs, int nvec, s
   }
 }
 
-static int ev_upload(lpgp_ctx* ctx, double* dst, const std::vector<double>& h) {
+int ev_upload(lpgp_ctx* ctx, double* dst, const std::vector<double>& h) {
   LPGP_HIP(hipMemcpyAsync(dst, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
   ctx->evidence_h2d_bytes += (int64_t)(h.size() * sizeof(double));
   return 0;
 }
-static int ev_download(lpgp_ctx* ctx, double* dst, const double* src, size_t doubles) {
+int ev_download(lpgp_ctx* ctx, double* dst, const double* src, size_t doubles) {
   LPGP_HIP(hipMemcpyAsync(dst, src, doubles * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
   ctx->evidence_d2h_bytes += (int64_t)(doubles * sizeof(double));
   return 0;
@@ -201,7 +201,7 @@ int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_
 }
 
 // d_diag (pn doubles, device) <- diag(G^{-1}) in the padded layout, on the panel stream
-static int inverse_diag_device(lpgp_ctx* ctx, lpgp_mat* mat, double* d_diag) {
+int inverse_diag_device(lpgp_ctx* ctx, lpgp_mat* mat, double* d_diag) {
   const int64_t pn = mat->pn, panel = std::min<int64_t>(ctx->inverse_diag_panel, pn);
   hipStream_t st = ctx->s_main;
   FactorView F;

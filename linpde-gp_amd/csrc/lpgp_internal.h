@@ -117,7 +117,12 @@ struct lpgp_ctx : lpgp::Options {     // tuning options: options.h
   // right-hand side takes 8 n x this many bytes), and the bytes these entry points and lpgp_mat_evidence have copied up and down --
   // option "inverse_diag_panel" and the read-only keys "evidence_h2d_bytes" / "evidence_d2h_bytes" of lpgp_get_option
   int64_t inverse_diag_panel = 4096;
+  int64_t cv_fold_batch = 512;     // lpgp_mat_cv (evidence_cv.hip): folds of at most 128 rows per launch, 256 KiB of scratch each -- option "cv_fold_batch"
   int64_t evidence_h2d_bytes = 0, evidence_d2h_bytes = 0;
+  // set by lpgp_mat_cv around the factorisation of a large fold's scratch matrix (evidence_cv.hip: LargeFoldFactor), never by a caller:
+  // launch_potrf_tile launches the tile Cholesky with the Newton sign (potrf_tile.h).  The resident panel chain has no such form, so
+  // the same scope keeps it off (chain_resident_max_rows = -1) and every diagonal tile goes through launch_potrf_tile.
+  int tile_newton_inv = 0;
   int panel_lds_extra = 0;         // bytes of LDS a fused panel launch asks for beyond its own 69 632 (set by the two-level forward substitution around its launches)
   // workspace
   // descriptor ring: an assembly launch copies its lowered descriptor into a pinned host slot,
@@ -486,6 +491,15 @@ int solve_vec_fwd_resident(lpgp_ctx* ctx, FactorView F, int64_t T, const double*
 int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]);
 int mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host);
 int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host, double* logp_host);
+// ... and their pieces that evidence_cv.hip shares: the host staging of nvec logical vectors into the padded layout (behind them the map
+// padded row -> logical row as pn int32), the counted copies, diag(G^{-1}) into a device vector of pn doubles
+void ev_stage(const lpgp_mat* mat, const double* const* vecs, int nvec, std::vector<double>* h);
+int ev_upload(lpgp_ctx* ctx, double* dst, const std::vector<double>& h);
+int ev_download(lpgp_ctx* ctx, double* dst, const double* src, size_t doubles);
+int inverse_diag_device(lpgp_ctx* ctx, lpgp_mat* mat, double* d_diag);
+// evidence_cv.hip: leave-fold-out cross-validation from the dense inverse (lpgp_mat_cv)
+int mat_cv(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const double* r_host, const double* y_host, const int32_t* fold_of, int32_t nfolds,
+           double* mean_host, double* var_host, double* logp_host, double* cov_host);
 // evidence_grad.hip: the dense inverse W^T W, W = L^{-1}, into the lower triangle of `out` (same block layout, not factored), and the
 // pair (w^T dG w, tr(G^{-1} dG)) of GPML eq. 5.9 for an assembled dG / for dG = diag(v) + scalar I on block bi
 int mat_inverse_into(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat* out);

@@ -30,6 +30,15 @@ __global__ __launch_bounds__(TILE_WAVES * 64) void potrf_tile_kernel(double* __r
   potrf_tile_body(a, lda, linv, info, info_base, sm);
 }
 
+// the same with the Newton sign in the last correction of a pivot's reciprocal square root (potrf_tile.h): the factorisations of
+// lpgp_mat_cv's large folds, whose results are read off S^{-1} (lpgp_ctx::tile_newton_inv)
+__global__ __launch_bounds__(TILE_WAVES * 64) void potrf_tile_newton_kernel(double* __restrict__ a, int64_t lda,
+                                                                 double* __restrict__ linv, int* __restrict__ info,
+                                                                 int info_base) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  potrf_tile_body<true>(a, lda, linv, info, info_base, sm);
+}
+
 int debug_tile_xcc(int32_t* out8, int reset) {
   int h[8];
   LPGP_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile_xcc_hist), sizeof(h)));
@@ -44,9 +53,10 @@ int debug_tile_xcc(int32_t* out8, int reset) {
 int launch_potrf_tile(lpgp_ctx* ctx, hipStream_t stream, double* a, int64_t lda, double* linv,
                       int* d_info, int info_base) {
   const size_t shmem = (size_t)TILE_LDS_DOUBLES * sizeof(double);
-  LPGP_TRY_RC(ensure_lds_attr(ctx, reinterpret_cast<const void*>(&potrf_tile_kernel), shmem));
+  void (*kfn)(double*, int64_t, double*, int*, int) = ctx->tile_newton_inv ? potrf_tile_newton_kernel : potrf_tile_kernel;
+  LPGP_TRY_RC(ensure_lds_attr(ctx, reinterpret_cast<const void*>(kfn), shmem));
   prof_begin(ctx, stream, LPGP_K_POTRF_TILE, (double)TILE * TILE * TILE / 3.0, 0.0);
-  hipLaunchKernelGGL(potrf_tile_kernel, dim3(1), dim3(TILE_WAVES * 64), shmem, stream, a, lda, linv, d_info, info_base);
+  hipLaunchKernelGGL(kfn, dim3(1), dim3(TILE_WAVES * 64), shmem, stream, a, lda, linv, d_info, info_base);
   prof_end(ctx, stream);
   LPGP_HIP(hipGetLastError());
   return 0;

@@ -44,6 +44,10 @@ __device__ __forceinline__ double bcast16(double v) {
 static __device__ int g_tile_xcc_hist[8];
 
 // (a device function since round 5: the tile Cholesky kernel below and the factor role of the resident panel chain, chain.hip)
+// NEWTON_INV: the sign of the last correction of a pivot's reciprocal square root (see there).  false: the factorisation as it has
+// always run; true: lpgp_mat_cv, whose results are read off S^{-1} -- the fold kernel of evidence_cv.hip and, for its large folds,
+// potrf_tile_newton_kernel (potrf.hip).
+template <bool NEWTON_INV = false>
 __device__ __forceinline__ void potrf_tile_body(double* __restrict__ a, int64_t lda, double* __restrict__ linv, int* __restrict__ info,
                                                 int info_base, double* sm) {
   double* s = sm;                       // s[c*TL + r]
@@ -194,7 +198,13 @@ __device__ __forceinline__ void potrf_tile_body(double* __restrict__ a, int64_t 
         double l = piv * inv;
         const double res = fma(-l, l, piv);
         l = fma(0.5 * inv, res, l);
-        inv = fma(inv, -0.5 * inv * inv * res, inv);       // keep inv consistent with the refined l
+        // inv once more, from the residual of l: the Newton step is inv (1 + 1/2 inv^2 res) (res = piv - l^2 = piv (1 - piv inv^2)).  The
+        // factorisation has carried the OTHER sign since round 3, which doubles the error the first step left instead of removing it: with
+        // the hardware estimate good to d that is 3 d^2 in inv, tens of u for d = 2^-25, and with it in every entry of the column and of
+        // the tile inverse (the diagonal entry l is refined on its own and is good to 1 u) -- the tile Cholesky's backward error of 12 - 24 u
+        // against LAPACK's 3 u on the fold matrices of tests/test_gpu_cv.py.  The sign is kept where the bits of every factorisation, the
+        // golden vectors and the measured accuracy tables depend on it (NEWTON_INV = false); switching it there is a change of its own.
+        inv = fma(inv, (NEWTON_INV ? 0.5 : -0.5) * inv * inv * res, inv);
         row[j] = (i == j) ? l : row[j] * inv;
         x[j] = x[j] * inv;                                  // (delta_jc - sum_{k<j} L[j][k] x[k]) / L[j][j]; exactly 0 for j < c
         static_for<j + 1, 16>([&](auto K_) {

@@ -531,6 +531,31 @@ class GramMatrix:
                                               as_pd(r), as_pd(out)), "lpgp_mat_evidence_grad_diag")
         return float(out[0]), float(out[1])
 
+    def cv(self, ginv: "GramMatrix", r: np.ndarray, y: np.ndarray, fold_of: np.ndarray, nfolds: int, return_cov: bool = False):
+        """Leave-fold-out predictive distributions (`lpgp_mat_cv`, csrc/evidence_cv.hip): `fold_of[i]` in -1 .. nfolds - 1 per row in
+        Gram order (-1: in no fold), `ginv` = `inverse()`, `r` and `y` as `loo` takes them.  Returns (mean, var, log predictive
+        density per fold, their sum, covariances or None); mean and var are NaN for the rows in no fold, the covariances one
+        (b, b) array per fold, rows in increasing Gram order."""
+        n = self.n
+        r = np.ascontiguousarray(r, dtype=np.double)
+        y = np.ascontiguousarray(y, dtype=np.double)
+        fold_of = np.ascontiguousarray(fold_of, dtype=np.int32)
+        if r.shape != (n,) or y.shape != (n,) or fold_of.shape != (n,):
+            raise ValueError(f"residual, observations and fold map must have shape ({n},), got {r.shape}, {y.shape} and {fold_of.shape}")
+        nfolds = int(nfolds)
+        mean, var, logp = np.empty(n), np.empty(n), np.empty(nfolds + 1)
+        cov = None
+        if return_cov:
+            sizes = np.bincount(fold_of[fold_of >= 0], minlength=max(nfolds, 0)).astype(np.int64)
+            cov = np.empty(int(np.sum(sizes * sizes)))
+        check(lib.lpgp_mat_cv(self.ctx._h, self._h, ginv._h, as_pd(r), as_pd(y), fold_of.ctypes.data_as(C.POINTER(C.c_int32)), nfolds,
+                              as_pd(mean), as_pd(var), as_pd(logp), as_pd(cov) if cov is not None else None), "lpgp_mat_cv")
+        covs = None
+        if cov is not None:
+            ends = np.cumsum(sizes * sizes)
+            covs = tuple(cov[e - b * b:e].reshape(b, b).copy() for b, e in zip(sizes.tolist(), ends.tolist()))
+        return mean, var, logp[:nfolds].copy(), float(logp[nfolds]), covs
+
     def potrf_enqueue(self) -> None:
         """The factorisation enqueued, no host synchronisation (`lpgp_potrf_enqueue`): its status is read by `check`."""
         check(lib.lpgp_potrf_enqueue(self.ctx._h, self._h), "lpgp_potrf_enqueue")

@@ -152,6 +152,7 @@ def _load() -> C.CDLL:
     sig("lpgp_mat_inverse", C.c_int, vp, vp, C.POINTER(vp))
     sig("lpgp_mat_evidence_grad", C.c_int, vp, vp, vp, vp, pd, pd)
     sig("lpgp_mat_evidence_grad_diag", C.c_int, vp, vp, vp, i32, pd, dbl, pd, pd)
+    sig("lpgp_mat_cv", C.c_int, vp, vp, vp, pd, pd, C.POINTER(i32), i32, pd, pd, pd, pd)
     sig("lpgp_rhs_matmul", C.c_int, vp, vp, pd, C.c_int64, C.POINTER(vp))
     sig("lpgp_gemm_host", C.c_int, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_double, pd, pd, C.c_double, pd)
     sig("lpgp_rhs_to_host", C.c_int, vp, vp, vp, pd)
@@ -177,7 +178,7 @@ EXPORTED = [
     "lpgp_gram_assemble", "lpgp_gram_assemble_weighted", "lpgp_cross_assemble_weighted", "lpgp_mat_add_diag", "lpgp_mat_add_dense", "lpgp_mat_to_host", "lpgp_mat_factor_diag",
     "lpgp_potrf", "lpgp_potrf_enqueue", "lpgp_mat_condition", "lpgp_mat_check", "lpgp_mat_truncate", "lpgp_potrs", "lpgp_solve_weights", "lpgp_mat_set_residual", "lpgp_rhs_create", "lpgp_rhs_destroy",
     "lpgp_cross_assemble", "lpgp_cross_assemble_row", "lpgp_predict", "lpgp_potrf_predict", "lpgp_trsm_lower", "lpgp_rhs_inner", "lpgp_rhs_matmul", "lpgp_gemm_host", "lpgp_mat_sub_inner", "lpgp_mat_factor_matmul",
-    "lpgp_mat_evidence", "lpgp_mat_inverse_diag", "lpgp_mat_loo", "lpgp_mat_inverse", "lpgp_mat_evidence_grad", "lpgp_mat_evidence_grad_diag",
+    "lpgp_mat_evidence", "lpgp_mat_inverse_diag", "lpgp_mat_loo", "lpgp_mat_inverse", "lpgp_mat_evidence_grad", "lpgp_mat_evidence_grad_diag", "lpgp_mat_cv",
     "lpgp_dvec_create", "lpgp_dvec_destroy", "lpgp_dvec_set", "lpgp_dvec_get", "lpgp_dvec_axpby", "lpgp_dvec_scale_rows_add", "lpgp_kernel_matvec_dev",
     "lpgp_pcg_create", "lpgp_pcg_destroy", "lpgp_pcg_start", "lpgp_pcg_step",
     "lpgp_rhs_to_host", "lpgp_kernel_diag", "lpgp_kernel_matrix", "lpgp_kernel_matvec", "lpgp_gram_assemble_grid", "lpgp_kron_fits", "lpgp_profile_enable", "lpgp_profile_reset",

@@ -319,6 +319,9 @@ class RemoteConditionalGaussianProcess:
     def leave_one_out(self):
         raise NotImplementedError("`leave_one_out` is not available through the `lp.spawn` multi-GPU front (single GPU only)")
 
+    def cross_validate(self, folds, *, return_cov=False):
+        raise NotImplementedError("`cross_validate` is not available through the `lp.spawn` multi-GPU front (single GPU only)")
+
     def log_marginal_likelihood_gradient(self):
         raise NotImplementedError("`log_marginal_likelihood_gradient` is not available through the `lp.spawn` multi-GPU front (single GPU only)")
 

@@ -491,6 +491,74 @@ class LeaveOneOut:
         return f"LeaveOneOut(n={self.mean.size}, total={self.total:.6g})"
 
 
+def _normalise_folds(folds, block_sizes):
+    """(fold_of, folds) of `ConditionalGaussianProcess.cross_validate`: `fold_of[i]` = the fold of row i in Gram order (int32, -1: in
+    no fold) and the folds as a tuple of sorted int64 index arrays.  `folds`: "blocks" (one fold per observation block), an int k
+    with 2 <= k <= n (row i goes to fold i % k), or a sequence of 1-D integer arrays, disjoint, each non-empty; they need not cover
+    all rows.  `block_sizes`: the rows of the observation blocks.  Needs no device.  `ValueError` on anything else."""
+    sizes = [int(b) for b in block_sizes]
+    n = sum(sizes)
+    if isinstance(folds, str):
+        if folds != "blocks":
+            raise ValueError(f'`folds` must be "blocks", an int or a sequence of index arrays, got {folds!r}')
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        return (np.repeat(np.arange(len(sizes), dtype=np.int32), sizes),
+                tuple(np.arange(offs[b], offs[b + 1], dtype=np.int64) for b in range(len(sizes))))
+    if isinstance(folds, (int, np.integer)) and not isinstance(folds, (bool, np.bool_)):
+        k = int(folds)
+        if not 2 <= k <= n:
+            raise ValueError(f"a number of strided folds must lie in 2 .. {n} (the number of observations), got {k}")
+        rows = np.arange(n, dtype=np.int64)
+        if k == n:
+            return rows.astype(np.int32), tuple(rows.reshape(n, 1))
+        return (rows % k).astype(np.int32), tuple(rows[f::k] for f in range(k))
+    else:
+        try:
+            raw = [np.asarray(f) for f in folds]
+        except TypeError:
+            raise ValueError(f'`folds` must be "blocks", an int or a sequence of index arrays, got {folds!r}') from None
+        lists = []
+        for f, a in enumerate(raw):
+            if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+                raise ValueError(f"fold {f} must be a 1-D array of integer row indices, got shape {a.shape} and dtype {a.dtype}")
+            lists.append(a.astype(np.int64))
+    if not lists:
+        raise ValueError("no folds")
+    fold_of = np.full(n, -1, dtype=np.int32)
+    out = []
+    for f, idx in enumerate(lists):
+        if idx.size == 0:
+            raise ValueError(f"fold {f} is empty")
+        if idx.min() < 0 or idx.max() >= n:
+            raise ValueError(f"fold {f} has a row index outside 0 .. {n - 1}")
+        idx = np.sort(idx)
+        if np.any(idx[1:] == idx[:-1]) or np.any(fold_of[idx] >= 0):
+            raise ValueError(f"fold {f} overlaps an earlier fold or names a row twice: the folds must be disjoint")
+        fold_of[idx] = f
+        out.append(idx)
+    return fold_of, tuple(out)
+
+
+class FoldPredictions:
+    """Result of `ConditionalGaussianProcess.cross_validate()`: `folds`, the row indices (Gram order, sorted) of every fold; per
+    observation the predictive distribution of the NOISY observation given all observations OUTSIDE its fold -- `mean`, `var`
+    (the observation's own `b` variance included), `std`, NaN for a row in no fold; per fold the joint log density of its
+    observations at the observed values, `log_predictive_density`, and `total`, their sum in fold order; `cov`, the joint (b, b)
+    predictive covariance of every fold (rows as in `folds`), or None if it was not asked for."""
+
+    __slots__ = ("folds", "mean", "var", "log_predictive_density", "total", "cov")
+
+    def __init__(self, folds, mean, var, log_predictive_density, total, cov=None):
+        self.folds, self.mean, self.var, self.log_predictive_density, self.total, self.cov = folds, mean, var, log_predictive_density, float(total), cov
+
+    @property
+    def std(self) -> np.ndarray:
+        return np.sqrt(np.maximum(self.var, 0.0))
+
+    def __repr__(self):
+        return f"FoldPredictions(n={self.mean.size}, folds={len(self.folds)}, total={self.total:.6g})"
+
+
 class EvidenceGradient:
     """Result of `ConditionalGaussianProcess.log_marginal_likelihood_gradient()`: `value`, the log marginal likelihood itself, and
     its derivatives with respect to the LOGARITHMS of the hyperparameters (every entry 1/2 w^T dG w - 1/2 tr(G^{-1} dG), GPML eq. 5.9):
@@ -974,6 +1042,31 @@ class ConditionalGaussianProcess(GaussianProcess):
         _evidence_context("leave_one_out")
         self._check_current()
         return LeaveOneOut(*self._state.mat.loo(self._residual(), np.concatenate([ob.Y for ob in self._blocks])))
+
+    def cross_validate(self, folds, *, return_cov: bool = False) -> "FoldPredictions":
+        """Leave-fold-out cross-validation (`FoldPredictions`): the predictive distribution of every fold B of observations given
+        all the others, mean_B = y_B - S^{-1} w_B, Sigma_B = S^{-1}, log p(y_B | y_-B) = -1/2 w_B^T S^{-1} w_B + 1/2 log det S
+        - |B|/2 log 2 pi with S = G^{-1}[B, B] and w = G^{-1} r (GPML section 5.4.2) -- "leave this boundary edge out", "leave every
+        8th collocation point out together" without a conditioning per fold.  `folds`: "blocks" (one fold per observation block of
+        the chain), an int k (row i of the Gram order goes to fold i % k) or a sequence of disjoint 1-D index arrays in Gram order
+        that need not cover all rows (`_normalise_folds`).  G^{-1} is formed once on the device from the resident factor
+        (`lpgp_mat_inverse`) and released at the end; the folds are reduced there (`lpgp_mat_cv`, csrc/evidence_cv.hip), O(n)
+        numbers cross the bus, and the covariances with `return_cov`.  Singleton folds are `leave_one_out()`, one fold of all rows
+        is `log_marginal_likelihood()`.  An earlier posterior of a chain answers for its own blocks; flushes, verifies and raises
+        as `leave_one_out`."""
+        if not self._blocks:
+            raise ValueError("`cross_validate` needs observations: this process has been conditioned on none")
+        fold_of, lists = _normalise_folds(folds, [ob.points.n for ob in self._blocks])
+        _evidence_context("cross_validate")
+        self._check_current()
+        mat = self._state.mat
+        r, y = self._residual(), np.concatenate([ob.Y for ob in self._blocks])
+        ginv = mat.inverse()
+        try:
+            mean, var, logp, total, cov = mat.cv(ginv, r, y, fold_of, len(lists), return_cov=bool(return_cov))
+        finally:
+            del ginv
+        return FoldPredictions(lists, mean, var, logp, total, cov)
 
     def log_marginal_likelihood_gradient(self) -> "EvidenceGradient":
         """The log marginal likelihood and its gradient by the log hyperparameters of the prior covariance and of the noise

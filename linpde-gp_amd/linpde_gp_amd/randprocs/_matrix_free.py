@@ -444,6 +444,9 @@ class MatrixFreeConditionalGaussianProcess:
     def leave_one_out(self):
         raise NotImplementedError("`leave_one_out` needs the dense factorisation: a matrix-free posterior has no Cholesky factor to form diag(G^-1) with")
 
+    def cross_validate(self, folds, *, return_cov=False):
+        raise NotImplementedError("`cross_validate` needs the dense factorisation: a matrix-free posterior has no Cholesky factor to form G^-1 with")
+
     def log_marginal_likelihood_gradient(self):
         raise NotImplementedError("`log_marginal_likelihood_gradient` needs the dense factorisation: a matrix-free posterior has no Cholesky factor to form G^-1 with")
 
