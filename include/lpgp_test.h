@@ -19,6 +19,16 @@ extern "C" {
  * per list entry; returns the number of tiles (< 0: error).                                          */
 int  lpgp_test_stair_enumerate(int32_t pr, int32_t pc, int32_t my_r, int32_t my_c, int32_t nbt, int32_t T,
                                int32_t row_lo, int32_t col_lo, int32_t* out, int64_t cap);
+/* The distributed trailing update of ONE rank, in this process, on host buffers: rank (my_r, my_c) of a pr x pc grid (blocks of nbt
+ * tiles, T tile rows / columns in all) updates its local tiles whose global tile (gr, gc) has gr >= row_lo, col_lo <= gc < col_hi and
+ * gr >= gc:  C <- beta C + alpha P[gr - g0] P[gc - g0]^T.  The launch arguments come from the function the factorisation itself uses
+ * (update_args, csrc/dist.hip) and go through launch_gemm.  panel: rows of the global tiles g0 .. T - 1 (g0 <= row_lo, col_lo), k columns
+ * (a multiple of 128), column-major, leading dimension ldp >= (T - g0) * 128.  C: the rank's WHOLE local storage, cyc_before(rows, T) x
+ * cyc_before(cols, T) tiles, column-major, leading dimension ldc.  tri: 1 (remainder / whole update) or 3 (look-ahead half); occ3: the
+ * launch may use the three-workgroups-per-CU kernel.  A rank that owns nothing of the region returns 0 and touches nothing.         */
+int  lpgp_test_gemm_cyc(lpgp_ctx* ctx, int32_t pr, int32_t pc, int32_t my_r, int32_t my_c, int32_t nbt, int32_t T, int32_t row_lo,
+                        int32_t col_lo, int32_t col_hi, int32_t g0, int32_t k, int32_t tri, int32_t occ3, double alpha, double beta,
+                        const double* panel, int64_t ldp, double* C, int64_t ldc);
 /* C(m x n, col-major ldc) = beta*C + alpha * op(A) op(B); ta/tb: 0 => operand stored with
  * its non-contracted index fastest, 1 => contracted index (k) fastest.                  */
 int  lpgp_test_gemm(lpgp_ctx* ctx, int32_t ta, int32_t tb, int32_t lower_only,

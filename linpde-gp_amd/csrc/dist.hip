@@ -36,6 +36,7 @@
 // per link and never stored replicated.
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -634,15 +635,15 @@ static int panel_rows_solve(lpgp_ctx* ctx, hipStream_t st, lpgp_mat* mat, const 
   return 0;
 }
 
-// The update of this rank's tiles by a gathered panel: local tile rows [rt0, LTr) x local tile columns [ct0, ct1),
-// valid where global row tile >= global column tile; `panel` holds global tile rows g0 ... (leading dimension ldp)
-static GemmArgs update_args(lpgp_mat* mat, const Grid& G, const double* panel, int64_t ldp, int g0, int K128, int rt0, int rt1, int ct0,
-                            int ct1, int tri) {
-  const int64_t ld = mat->lr_cap;
-  GemmArgs g = mk(panel, ldp, panel, ldp, mat->a + (int64_t)rt0 * TILE + (int64_t)ct0 * TILE * ld, ld, rt1 - rt0, ct1 - ct0, K128, -1.0, 1.0,
-                  tri);
+// The update of a rank's tiles by a gathered panel: local tile rows [rt0, rt1) x local tile columns [ct0, ct1) of the rank's
+// storage `a` (leading dimension ld; R, C: its row / column membership), valid where global row tile >= global column tile;
+// `panel` holds global tile rows g0 ... (leading dimension ldp).  (Declared in lpgp_internal.h: the test hook
+// lpgp_test_gemm_cyc launches through the very arguments potrf_dist builds here.)
+GemmArgs update_args(double* a, int64_t ld, const Cyc& R, const Cyc& C, const double* panel, int64_t ldp, int g0, int K128, int rt0, int rt1,
+                     int ct0, int ct1, int tri) {
+  GemmArgs g = mk(panel, ldp, panel, ldp, a + (int64_t)rt0 * TILE + (int64_t)ct0 * TILE * ld, ld, rt1 - rt0, ct1 - ct0, K128, -1.0, 1.0, tri);
   g.cyc = 1;
-  g.rowc = G.R; g.colc = G.C;
+  g.rowc = R; g.colc = C;
   g.rt0 = rt0; g.ct0 = ct0; g.g0 = g0;
   return g;
 }
@@ -650,7 +651,7 @@ static int update_local(lpgp_ctx* ctx, hipStream_t st, lpgp_mat* mat, const Grid
                         int rt0, int rt1, int ct0, int ct1, int prof) {
   if (rt1 <= rt0 || ct1 <= ct0) return 0;
   // (the look-ahead half keeps its own kernel symbol and profiling slot, as on a single GPU)
-  return launch_gemm(ctx, st, 0, 0, update_args(mat, G, panel, ldp, g0, K128, rt0, rt1, ct0, ct1, prof == LPGP_K_SYRK_AHEAD ? 3 : 1), prof);
+  return launch_gemm(ctx, st, 0, 0, update_args(mat->a, mat->lr_cap, G.R, G.C, panel, ldp, g0, K128, rt0, rt1, ct0, ct1, prof == LPGP_K_SYRK_AHEAD ? 3 : 1), prof);
 }
 
 // Factor the diagonal block of panel [c0, c1) (owner only, in its local storage), copy it into the replicated
@@ -810,7 +811,7 @@ int potrf_dist(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, int64_t T64, int3
     // complete (launched together they share the chip by workgroup count and (a), which the next panel waits for, crawls);
     // (2) once (b) is shorter than the chain even on the narrow stream, it runs there and leaves a quarter of the CUs to the
     // chain's kernels.
-    const double t_b_us = (double)gemm_valid_tiles(update_args(mat, G, panel, ldp, p.c1, K128, rt0, LTr, ctb, LTc, 1)) *
+    const double t_b_us = (double)gemm_valid_tiles(update_args(mat->a, mat->lr_cap, G.R, G.C, panel, ldp, p.c1, K128, rt0, LTr, ctb, LTc, 1)) *
                           (2.0 * TILE * TILE * (double)K128 / 50e6);
     const double t_chain_us = ctx->chain_us_tile * (double)(q.c1 - q.c0) + ctx->chain_us_fixed + (ctx->world > 1 ? ctx->dist_chain_us_comm : 0.0);
     const bool chain_bound = t_b_us < t_chain_us;
@@ -825,7 +826,7 @@ int potrf_dist(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, int64_t T64, int3
     LPGP_HIP(hipStreamWaitEvent(sB, evp, 0));
     if (tail_pending[which]) LPGP_HIP(hipStreamWaitEvent(sB, ctx->ev_tail[which], 0));   // (b) reads every row of the panel
     {
-      GemmArgs gb = update_args(mat, G, panel, ldp, p.c1, K128, rt0, LTr, ctb, LTc, 1);
+      GemmArgs gb = update_args(mat->a, mat->lr_cap, G.R, G.C, panel, ldp, p.c1, K128, rt0, LTr, ctb, LTc, 1);
       gb.occ3 = t_b_us > ctx->gemm3_margin * t_chain_us;
       if (gb.mt > 0 && gb.nt > 0) LPGP_TRY(launch_gemm(ctx, sB, 0, 0, gb, LPGP_K_SYRK));
     }
@@ -839,9 +840,15 @@ int potrf_dist(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, int64_t T64, int3
   if (have_upd && last_upd) LPGP_HIP(hipStreamWaitEvent(sP, last_upd, 0));      // join: every update is behind the panel stream
   LPGP_HIP(hipMemcpyAsync(ctx->h_info_pinned + 1, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, sP));
   LPGP_TRY(sync_stream(ctx, sP));
-  int h_info = ctx->h_info_pinned[1];
-  LPGP_TRY(allreduce_max_int(ctx, sP, &h_info));        // a failed pivot is seen by the owner of its diagonal block only
-  if (info) *info = h_info;
+  // A failed pivot is seen by the owner of its diagonal block only -- and the blocks behind it, whose owners are other ranks, fail in
+  // their turn once its garbage reaches them: the job's status is the FIRST bad pivot, the smallest positive status of any rank.
+  // Agreed on as a maximum of INT_MAX - status.  The kernels launched here write 0 or a pivot's position (potrf_tile.h), never the
+  // negative status of a broken hand-over that the single-GPU chain knows; should a rank report one all the same, it outranks every
+  // pivot and comes back as -1: its value is not carried through the reduction.
+  const int h_local = ctx->h_info_pinned[1];
+  int key = h_local > 0 ? INT_MAX - h_local : (h_local < 0 ? INT_MAX : 0);
+  LPGP_TRY(allreduce_max_int(ctx, sP, &key));
+  if (info) *info = key == INT_MAX ? -1 : (key > 0 ? INT_MAX - key : 0);
   return 0;
 }
 

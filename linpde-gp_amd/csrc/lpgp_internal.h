@@ -444,6 +444,11 @@ inline GemmArgs mk(const double* A, int64_t lda, const double* B, int64_t ldb, d
 int launch_gemm(lpgp_ctx* ctx, hipStream_t stream, int ta, int tb, const GemmArgs& g, int prof_kernel);
 int stair_enumerate_host(const GemmArgs& g, int32_t* out, int64_t cap);
 int64_t gemm_valid_tiles(const GemmArgs& g);
+// dist.hip: the arguments of the distributed trailing update of one rank (potrf_dist; the test hook lpgp_test_gemm_cyc): local tile
+// rows [rt0, rt1) x local tile columns [ct0, ct1) of the storage `a` (leading dimension ld) of the member R x C of the grid, updated by
+// the gathered panel (first global tile row g0, leading dimension ldp, K128 columns): alpha = -1, beta = 1
+GemmArgs update_args(double* a, int64_t ld, const Cyc& R, const Cyc& C, const double* panel, int64_t ldp, int g0, int K128, int rt0, int rt1,
+                     int ct0, int ct1, int tri);
 // Tile solves with one step of iterative refinement (solve.hip: tile_solve_kernel); L = the 128 x 128 diagonal
 // tile of the factor (leading dimension ldl, zeros above the diagonal), linv its explicit inverse (ld 128):
 // X (mt*128 rows x 128, column-major ldx) <- X L^{-T} in place

@@ -101,6 +101,39 @@ int lpgp_test_stair_enumerate(int32_t pr, int32_t pc, int32_t my_r, int32_t my_c
   return n;
 }
 
+// The trailing update of rank (my_r, my_c) of a pr x pc grid as potrf_dist launches it, on host buffers: the arguments come from
+// update_args (dist.hip), the launch goes through launch_gemm.  Chost: the rank's whole local storage, cyc_before(rows, T) x
+// cyc_before(cols, T) tiles (leading dimension ldc); panel: rows of global tiles g0 ... T - 1, k columns (leading dimension ldp).
+int lpgp_test_gemm_cyc(lpgp_ctx* ctx, int32_t pr, int32_t pc, int32_t my_r, int32_t my_c, int32_t nbt, int32_t T, int32_t row_lo,
+                       int32_t col_lo, int32_t col_hi, int32_t g0, int32_t k, int32_t tri, int32_t occ3, double alpha, double beta,
+                       const double* panel, int64_t ldp, double* Chost, int64_t ldc) {
+  LPGP_CHECK(ctx && pr >= 1 && pc >= 1 && my_r >= 0 && my_r < pr && my_c >= 0 && my_c < pc && nbt >= 1 && T >= 1,
+             "lpgp_test_gemm_cyc: bad grid");
+  LPGP_CHECK(row_lo >= 0 && row_lo <= T && col_lo >= 0 && col_lo <= col_hi && col_hi <= T && g0 >= 0 && g0 <= row_lo && g0 <= col_lo,
+             "lpgp_test_gemm_cyc: bad region (0 <= g0 <= row_lo, col_lo; col_lo <= col_hi <= T)");
+  LPGP_CHECK((tri == 1 || tri == 3) && k > 0 && k % TILE == 0 && alpha != 0.0, "lpgp_test_gemm_cyc: tri is 1 or 3, k a multiple of 128, alpha != 0");
+  LPGP_DEVICE(ctx);
+  Cyc R, Cc;
+  R.P = pr; R.me = my_r; R.nbt = nbt;
+  Cc.P = pc; Cc.me = my_c; Cc.nbt = nbt;
+  const int LTr = cyc_before(R, T), LTc = cyc_before(Cc, T);
+  const int rt0 = cyc_before(R, row_lo), ct0 = cyc_before(Cc, col_lo), ct1 = cyc_before(Cc, col_hi);
+  if (LTr == 0 || LTc == 0 || LTr <= rt0 || ct1 <= ct0) return 0;       // nothing of the region on this rank (update_local)
+  LPGP_CHECK(panel && Chost && ldp >= (int64_t)(T - g0) * TILE && ldc >= (int64_t)LTr * TILE, "lpgp_test_gemm_cyc: a leading dimension is too small");
+  const size_t pbytes = (size_t)ldp * (size_t)k * sizeof(double), cbytes = (size_t)ldc * (size_t)LTc * TILE * sizeof(double);
+  DevBuf bP, bC;
+  LPGP_TRY(DevBuf::raw(pbytes, &bP));
+  LPGP_TRY(DevBuf::raw(cbytes, &bC));
+  LPGP_HIP(hipMemcpy(bP.as(), panel, pbytes, hipMemcpyHostToDevice));
+  LPGP_HIP(hipMemcpy(bC.as(), Chost, cbytes, hipMemcpyHostToDevice));
+  GemmArgs g = update_args(bC.as(), ldc, R, Cc, bP.as(), ldp, g0, k, rt0, LTr, ct0, ct1, tri);
+  g.alpha = alpha; g.beta = beta; g.occ3 = occ3;
+  LPGP_TRY(launch_gemm(ctx, ctx->s_main, 0, 0, g, -1));
+  LPGP_HIP(hipStreamSynchronize(ctx->s_main));
+  LPGP_HIP(hipMemcpy(Chost, bC.as(), cbytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int lpgp_test_potrf_tile(lpgp_ctx* ctx, double* T, double* Linv, int32_t* info) {
   LPGP_DEVICE(ctx);
   const size_t tbytes = (size_t)TILE * TILE * sizeof(double);

@@ -1,4 +1,4 @@
-"""Helpers shared by the backward-error suites (test_gpu_potrf_backward.py, test_gpu_predict_backward.py): long-double products
+"""Helpers shared by the backward-error suites (test_gpu_potrf_backward.py, test_gpu_predict_backward.py, test_gpu_dist_backward.py): long-double products
 in row slabs, the scaled backward error of a Cholesky factor, block rows appended as a conditioning builds them, and the
 restoring of schedule options.  A plain module the suites import, not a conftest."""
 import contextlib
@@ -52,6 +52,20 @@ def backward_error(A, L):
     AX = _cache[key]
     R = AX - s[:, None] * mv(L, mtv(L, s[:, None] * X))
     return float(np.max(np.abs(R)) / np.max(np.sqrt(np.sum(X * X, axis=0))))
+
+
+def solve_backward_error(A, x, b):
+    """Normwise backward error of x as a solution of A x = b, per the solve check of test_gpu_potrf_backward.py:
+    max |A x - b| / (||A||_inf max |x| + max |b|), the residual in long double."""
+    x, b = x.reshape(A.shape[0], -1), b.reshape(A.shape[0], -1)
+    r = mv(A, x.astype(LD)) - b.astype(LD)
+    nA = float(np.max(np.sum(np.abs(A), axis=1)))
+    return float(np.max(np.abs(r))) / (nA * float(np.max(np.abs(x))) + float(np.max(np.abs(b))))
+
+
+def row_scaled_distance(A, L1, L2):
+    """max |diag(A)^{-1/2} (L1 - L2)|: the distance of two factors of A that the append test of test_gpu_potrf_backward.py bounds."""
+    return float(np.max(np.abs((L1 - L2) * scale(A)[:, None])))
 
 
 def matern52(n, rng):

@@ -16,7 +16,7 @@ from linpde_gp_amd._lib import check
 
 HOOKS_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "liblpgp_testhooks.so")
 
-EXPORTED = ["lpgp_test_stair_enumerate", "lpgp_test_gemm", "lpgp_test_potrf_tile", "lpgp_test_tile_step", "lpgp_test_panel_solve",
+EXPORTED = ["lpgp_test_stair_enumerate", "lpgp_test_gemm", "lpgp_test_gemm_cyc", "lpgp_test_potrf_tile", "lpgp_test_tile_step", "lpgp_test_panel_solve",
             "lpgp_debug_tile_xcc", "lpgp_probe_mfma_f64", "lpgp_probe_hbm_write", "lpgp_test_force_status", "lpgp_test_solve_vec_fwd"]
 
 
@@ -34,6 +34,7 @@ def _load() -> C.CDLL:
 
     sig("lpgp_test_stair_enumerate", C.c_int, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), i64)
     sig("lpgp_test_gemm", C.c_int, vp, i32, i32, i32, i64, i64, i64, dbl, pd, i64, pd, i64, dbl, pd, i64, i32, pd)
+    sig("lpgp_test_gemm_cyc", C.c_int, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, dbl, dbl, pd, i64, pd, i64)
     sig("lpgp_test_potrf_tile", C.c_int, vp, pd, pd, C.POINTER(i32))
     sig("lpgp_debug_tile_xcc", C.c_int, vp, C.POINTER(i32), i32)
     sig("lpgp_test_tile_step", C.c_int, vp, i32, pd, i64, pd, pd, pd)
@@ -81,6 +82,21 @@ def test_gemm(ctx: Context, ta: int, tb: int, lower_only: int, alpha: float, A: 
                              A.ctypes.data_as(pd), A.shape[0], B.ctypes.data_as(pd), B.shape[0], beta,
                              Cm.ctypes.data_as(pd), Cm.shape[0], reps, C.byref(ms)), "lpgp_test_gemm")
     return Cm, ms.value
+
+
+def test_gemm_cyc(ctx: Context, grid, rank, nbt: int, T: int, row_lo: int, col_lo: int, col_hi: int, g0: int, k: int, tri: int, occ3: int,
+                  alpha: float, beta: float, panel: np.ndarray, Cm: np.ndarray) -> np.ndarray:
+    """The trailing update of rank `rank` = (my_r, my_c) of the process grid `grid` = (pr, pc) as `potrf_dist` launches it
+    (`lpgp_test_gemm_cyc`), in this process: `panel` (column-major, its row count is the leading dimension: rows below
+    (T - g0) * 128 are never read) against the rank's whole local storage `Cm` (column-major, likewise).  Returns the storage."""
+    panel = np.asfortranarray(panel, dtype=np.double)
+    Cm = np.asfortranarray(Cm, dtype=np.double).copy(order="F")
+    if panel.shape[1] != k:
+        raise ValueError("test_gemm_cyc: the panel must have k columns")
+    pd = C.POINTER(C.c_double)
+    check(lib.lpgp_test_gemm_cyc(ctx._h, grid[0], grid[1], rank[0], rank[1], nbt, T, row_lo, col_lo, col_hi, g0, k, tri, occ3, alpha, beta,
+                                 panel.ctypes.data_as(pd), panel.shape[0], Cm.ctypes.data_as(pd), Cm.shape[0]), "lpgp_test_gemm_cyc")
+    return Cm
 
 
 def test_tile_step(ctx: Context, which: int, XV: np.ndarray, L: np.ndarray, Linv: np.ndarray):
