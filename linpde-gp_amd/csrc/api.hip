@@ -282,7 +282,7 @@ static int mat_alloc(lpgp_ctx* ctx, lpgp_mat* mat, int64_t cap) {
   LPGP_TRY(DevBuf::pool(ctx, mat_bytes_w(cap), &bw));
   if (ctx->distributed()) LPGP_TRY(DevBuf::pool(ctx, mat_bytes_d(ctx, cap), &bd));
   double *const na = ba.as(), *const nl = bl.as(), *const nw = bw.as(), *const nd = bd.as();
-  const int64_t pn_all = mat->hidden.empty() ? mat->pn : mat->hidden.back().poff + mat->hidden.back().pn;
+  const int64_t pn_all = mat->padded_end(mat->total_blocks());
   if (mat->a && pn_all > 0) {
     const int64_t lru = local_rows(ctx, pn_all), lcu = local_cols(ctx, pn_all);
     if (lru > 0 && lcu > 0)
@@ -310,17 +310,8 @@ static int mat_alloc(lpgp_ctx* ctx, lpgp_mat* mat, int64_t cap) {
   mat->cap = cap;
   mat->lr_cap = lr;
   mat->lc_cap = lc;
-  mat->has_r = 0;            // the residual segment is addressed relative to cap
+  mat->storage_moved();
   return 0;
-}
-
-// logical (length mat->n) <-> padded (length mat->pn) host vectors
-static void scatter_padded(const lpgp_mat* mat, const double* logical, double* padded) {
-  std::memset(padded, 0, (size_t)mat->pn * sizeof(double));
-  for (const auto& b : mat->blocks) std::memcpy(padded + b.poff, logical + b.off, (size_t)b.n * sizeof(double));
-}
-static void gather_padded(const lpgp_mat* mat, const double* padded, double* logical) {
-  for (const auto& b : mat->blocks) std::memcpy(logical + b.off, padded + b.poff, (size_t)b.n * sizeof(double));
 }
 
 }  // namespace lpgp
@@ -785,11 +776,6 @@ int lpgp_mat_create(lpgp_ctx* ctx, int64_t capacity_hint, lpgp_mat** out) {
   LPGP_DEVICE(ctx);
   std::unique_ptr<lpgp_mat> m(new lpgp_mat());
   m->ctx = ctx;
-  m->cap = 0;
-  m->a = m->linv = m->w = nullptr;
-  m->n = m->pn = m->pn_fact = 0;
-  m->has_w = 0;
-  m->has_r = 0;
   int64_t cap = round_up(capacity_hint > 0 ? capacity_hint : 8 * TILE, TILE);      // (no hint: room for 1 024 rows, 8 MB -- the reference's own problem sizes start here)
   LPGP_TRY(mat_alloc(ctx, m.get(), cap));
   ++ctx->live_mats;
@@ -814,11 +800,7 @@ static int mat_add_block_impl(lpgp_ctx* ctx, lpgp_mat* mat, int64_t n, bool pad_
   LPGP_DEVICE(ctx);
   LPGP_MAT_ALIVE(mat, "lpgp_mat_add_block");
   LPGP_CHECK(mat->hidden.empty(), "lpgp_mat_add_block: a strict prefix of the blocks is in view (lpgp_mat_set_view); extend a clone instead");
-  lpgp_block b;
-  b.n = n;
-  b.off = mat->n;
-  b.poff = mat->pn;
-  b.pn = round_up(n, TILE);
+  const lpgp_block b = mat->next_block(n);
   if (b.poff + b.pn > mat->cap) {
     // grow geometrically while the matrix is small (a chain of small conditionings without `gram_capacity_hint` used to
     // re-allocate, copy and synchronise at EVERY block: 48 us of host time per add_block at N_tot = 1 152); a block that
@@ -840,53 +822,25 @@ static int mat_add_block_impl(lpgp_ctx* ctx, lpgp_mat* mat, int64_t n, bool pad_
     launch_pad_block(ctx->s_main, mat->a, mat->lr_cap, r0, pad, mat->cap, lay);
     LPGP_HIP(hipGetLastError());
   }
-  mat->blocks.push_back(b);
-  mat->n += n;
-  mat->pn += b.pn;
-  mat->has_w = 0;
-  mat->has_r = 0;
-  return (int)mat->blocks.size() - 1;
+  return mat->push_block(n);
 }
 
 int lpgp_mat_pop_block(lpgp_ctx* ctx, lpgp_mat* mat) {
   LPGP_CHECK(ctx && mat, "lpgp_mat_pop_block: null argument");
   LPGP_DEVICE(ctx);
-  LPGP_CHECK(mat->hidden.empty(), "lpgp_mat_pop_block: a strict prefix of the blocks is in view");
-  LPGP_CHECK(!mat->blocks.empty(), "lpgp_mat_pop_block: no block");
-  const lpgp_block b = mat->blocks.back();
-  LPGP_CHECK(b.poff >= mat->pn_fact, "lpgp_mat_pop_block: the last block is part of the factor");
+  std::string err;
+  LPGP_TRY(refused(mat->can_pop_block(&err), err));
   LPGP_TRY(sync_stream(ctx, ctx->s_main));          // nothing of a failed append still in flight (watched: an exchange with a dead peer may be pending)
-  mat->blocks.pop_back();
-  mat->n -= b.n;
-  mat->pn -= b.pn;
-  mat->has_w = 0;
-  mat->has_r = 0;
-  return 0;
+  return refused(mat->pop_block(&err), err);
 }
 
 int32_t lpgp_mat_num_blocks(const lpgp_mat* mat) { return mat ? (int32_t)mat->blocks.size() : -1; }
-int32_t lpgp_mat_num_blocks_total(const lpgp_mat* mat) { return mat ? (int32_t)(mat->blocks.size() + mat->hidden.size()) : -1; }
+int32_t lpgp_mat_num_blocks_total(const lpgp_mat* mat) { return mat ? (int32_t)mat->total_blocks() : -1; }
 
 int lpgp_mat_set_view(lpgp_ctx* ctx, lpgp_mat* mat, int32_t nblocks) {
   LPGP_CHECK(ctx && mat, "lpgp_mat_set_view: null argument");
-  const int total = (int)(mat->blocks.size() + mat->hidden.size());
-  if (nblocks < 0) nblocks = total;
-  LPGP_CHECK(nblocks >= 1 && nblocks <= total, "lpgp_mat_set_view: %d of %d blocks", nblocks, total);
-  if (nblocks == (int)mat->blocks.size()) return 0;
-  const int64_t fact_all = mat->hidden.empty() ? mat->pn_fact : mat->pn_fact_all;
-  std::vector<lpgp_block> all = mat->blocks;
-  all.insert(all.end(), mat->hidden.begin(), mat->hidden.end());
-  const lpgp_block& last = all[nblocks - 1];
-  LPGP_CHECK(nblocks == total || last.poff + last.pn <= fact_all, "lpgp_mat_set_view: block %d is not factored yet", nblocks - 1);
-  mat->blocks.assign(all.begin(), all.begin() + nblocks);
-  mat->hidden.assign(all.begin() + nblocks, all.end());
-  mat->n = last.off + last.n;
-  mat->pn = last.poff + last.pn;
-  mat->pn_fact_all = fact_all;
-  mat->pn_fact = fact_all < mat->pn ? fact_all : mat->pn;
-  mat->has_w = 0;                                    // resident weights / residual belong to the previous view
-  mat->has_r = 0;
-  return 0;
+  std::string err;
+  return refused(mat->set_view(nblocks, &err), err);
 }
 
 // deleter of a handle that is still under construction but already owns device memory and is counted in live_mats
@@ -900,13 +854,9 @@ int lpgp_mat_clone(lpgp_ctx* ctx, const lpgp_mat* src, int32_t nblocks, lpgp_mat
   LPGP_DEVICE(ctx);
   LPGP_MAT_ALIVE(src, "lpgp_mat_clone");
   LPGP_CHECK(!ctx->distributed(), "lpgp_mat_clone: not available in a multi-GPU job");
-  std::vector<lpgp_block> all = src->blocks;
-  all.insert(all.end(), src->hidden.begin(), src->hidden.end());
-  LPGP_CHECK(nblocks >= 1 && nblocks <= (int)all.size(), "lpgp_mat_clone: %d of %d blocks", nblocks, (int)all.size());
-  const int64_t fact_all = src->hidden.empty() ? src->pn_fact : src->pn_fact_all;
-  const lpgp_block& last = all[nblocks - 1];
-  const int64_t pn = last.poff + last.pn;
-  LPGP_CHECK(pn <= fact_all, "lpgp_mat_clone: block %d is not factored yet", nblocks - 1);
+  std::string err;
+  LPGP_TRY(refused(src->can_take_prefix("lpgp_mat_clone", nblocks, false, &err), err));
+  const int64_t pn = src->padded_end(nblocks);
   lpgp_mat* created = nullptr;
   LPGP_TRY(lpgp_mat_create(ctx, pn, &created));
   std::unique_ptr<lpgp_mat, Destroy> m(created);
@@ -914,10 +864,7 @@ int lpgp_mat_clone(lpgp_ctx* ctx, const lpgp_mat* src, int32_t nblocks, lpgp_mat
                             (size_t)pn * sizeof(double), (size_t)pn, hipMemcpyDeviceToDevice, ctx->s_main));
   LPGP_HIP(hipMemcpyAsync(m->linv, src->linv, (size_t)pn * TILE * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main));
   LPGP_HIP(hipStreamSynchronize(ctx->s_main));
-  m->blocks.assign(all.begin(), all.begin() + nblocks);
-  m->n = last.off + last.n;
-  m->pn = pn;
-  m->pn_fact = pn;
+  LPGP_TRY(refused(m->adopt_prefix(*src, nblocks, &err), err));
   *out = m.release();
   return 0;
 }
@@ -1124,8 +1071,7 @@ int lpgp_mat_factor_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host) {
     LPGP_HIP(hipMemcpy2D(tmp.data(), sizeof(double), mat->a, (size_t)(mat->lr_cap + 1) * sizeof(double), sizeof(double), (size_t)pn,
                          hipMemcpyDeviceToHost));
   }
-  for (const auto& b : mat->blocks)
-    for (int64_t i = 0; i < b.n; ++i) out_host[b.off + i] = tmp[(size_t)(b.poff + i)];
+  mat->gather_padded(tmp.data(), out_host);
   return 0;
 }
 
@@ -1143,13 +1089,11 @@ int lpgp_potrf(lpgp_ctx* ctx, lpgp_mat* mat, int32_t* info) {
                ? dist_fail(ctx, potrf_dist(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, &h))
                : potrf_blocked(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, &h);
   if (rc != 0) {
-    mat->poisoned = 1;               // (the matrix is partly overwritten in place, pn_fact unchanged: not a state to factor again from)
+    mat->poison();                   // (the matrix is partly overwritten in place, pn_fact unchanged: not a state to factor again from)
     return rc;
   }
   if (info) *info = h;
-  if (h == 0) mat->pn_fact = mat->pn;
-  mat->has_w = 0;
-  mat->has_r = 0;
+  mat->factored(h);
   return 0;
 }
 
@@ -1162,14 +1106,10 @@ int lpgp_potrf_enqueue(lpgp_ctx* ctx, lpgp_mat* mat) {
   LPGP_CHECK(!ctx->distributed(), "lpgp_potrf_enqueue: single GPU only (the multi-GPU factorisation agrees on its status collectively: lpgp_potrf)");
   int rc = potrf_blocked(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, nullptr);
   if (rc != 0) {
-    mat->poisoned = 1;
+    mat->poison();
     return rc;
   }
-  mat->pn_fact = mat->pn;          // provisionally: lpgp_mat_check / lpgp_mat_truncate take it back on failure
-  mat->unchecked = 1;
-  mat->status_known = 0;
-  mat->has_w = 0;
-  mat->has_r = 0;
+  mat->factor_enqueued(false);     // (provisionally: lpgp_mat_check / lpgp_mat_truncate take it back on failure)
   return 0;
 }
 
@@ -1306,17 +1246,10 @@ int lpgp_mat_check(lpgp_ctx* ctx, lpgp_mat* mat, int32_t* info, int32_t* block) 
     LPGP_HIP(hipMemcpyAsync(&h, mat->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->s_main));
     LPGP_HIP(hipStreamSynchronize(ctx->s_main));
   }
-  mat->status_known = 0;
-  mat->unchecked = 0;
-  if (h < 0) mat->poisoned = 1;      // (not a pivot: the panel's contents are undefined and the status word stays at INT_MIN, so no later pivot failure could be recorded either)
+  mat->take_status(h);               // (h < 0 poisons the matrix: the status word stays at INT_MIN)
   LPGP_CHECK(h >= 0, "resident panel chain: a hand-over between workgroups timed out (device status %d); set LPGP_CHAIN_RESIDENT=-1", h);
   *info = h;
-  if (h > 0 && block) {
-    std::vector<lpgp_block> all = mat->blocks;
-    all.insert(all.end(), mat->hidden.begin(), mat->hidden.end());
-    for (size_t b = 0; b < all.size(); ++b)
-      if ((int64_t)h - 1 >= all[b].poff && (int64_t)h - 1 < all[b].poff + all[b].pn) *block = (int32_t)b;
-  }
+  if (h > 0 && block) *block = mat->block_of_pivot(h);
   return 0;
 }
 
@@ -1327,15 +1260,8 @@ int lpgp_mat_truncate(lpgp_ctx* ctx, lpgp_mat* mat, int32_t nblocks) {
   LPGP_CHECK(nblocks >= 0 && nblocks <= (int32_t)mat->blocks.size(), "lpgp_mat_truncate: %d of %d blocks", nblocks, (int)mat->blocks.size());
   LPGP_CHECK(!ctx->distributed(), "lpgp_mat_truncate: single GPU only");
   LPGP_HIP(hipStreamSynchronize(ctx->s_main));        // nothing of the dropped blocks still in flight
-  mat->blocks.resize((size_t)nblocks);
-  mat->n = nblocks ? mat->blocks.back().off + mat->blocks.back().n : 0;
-  mat->pn = nblocks ? mat->blocks.back().poff + mat->blocks.back().pn : 0;
-  if (mat->pn_fact > mat->pn) mat->pn_fact = mat->pn;
   LPGP_HIP(hipMemset(mat->d_status, 0, sizeof(int)));
-  mat->unchecked = 0;
-  mat->status_known = 0;
-  mat->has_w = 0;
-  mat->has_r = 0;
+  mat->truncate(nblocks);
   return 0;
 }
 
@@ -1348,7 +1274,7 @@ int lpgp_potrs(lpgp_ctx* ctx, lpgp_mat* mat, double* b_host, int64_t nrhs) {
   std::vector<double> hp((size_t)pn * m_pad, 0.0);
   DevBuf dv;                                     // (released by hipFree, which waits for the device: behind hp, so in front of it on the way out)
   LPGP_TRY(DevBuf::raw(hp.size() * sizeof(double), &dv));
-  for (int64_t j = 0; j < nrhs; ++j) scatter_padded(mat, b_host + j * n, hp.data() + j * pn);
+  for (int64_t j = 0; j < nrhs; ++j) mat->scatter_padded(b_host + j * n, hp.data() + j * pn);
   LPGP_HIP(hipMemcpyAsync(dv.as(), hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
   LPGP_TRY(solve_lower(ctx, mat, dv.as(), pn, m_pad));
   LPGP_TRY(solve_lower_t(ctx, mat, dv.as(), pn, m_pad));
@@ -1357,7 +1283,7 @@ int lpgp_potrs(lpgp_ctx* ctx, lpgp_mat* mat, double* b_host, int64_t nrhs) {
   LPGP_TRY(sync_stream(ctx, ctx->s_main));
   LPGP_HIP(hipMemcpyAsync(hp.data(), dv.as(), hp.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
   LPGP_TRY(sync_stream(ctx, ctx->s_main));       // (behind a streamed solve: polls, so that a failed peer cannot block this rank)
-  for (int64_t j = 0; j < nrhs; ++j) gather_padded(mat, hp.data() + j * pn, b_host + j * n);
+  for (int64_t j = 0; j < nrhs; ++j) mat->gather_padded(hp.data() + j * pn, b_host + j * n);
   return 0;
 }
 
@@ -1388,7 +1314,7 @@ int lpgp_solve_weights(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, doubl
   LPGP_TRY(ensure_stage(ctx, pn));
   double* const hs = ctx->h_stage;
   int* const hinfo = ctx->h_info_pinned + 6;
-  scatter_padded(mat, r_host, hs);
+  mat->scatter_padded(r_host, hs);
   LPGP_HIP(hipMemcpyAsync(mat->w, hs, (size_t)pn * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
   if (ctx->distributed()) {
     LPGP_TRY(dist_fail(ctx, solve_weights_dist(ctx, mat)));     // (any failure: the peers are inside the streamed solve, or about to enter it)
@@ -1404,8 +1330,8 @@ int lpgp_solve_weights(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, doubl
   LPGP_HIP(hipMemcpyAsync(hs, mat->w, (size_t)pn * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
   LPGP_TRY(sync_stream(ctx, ctx->s_main));
   LPGP_CHECK(*hinfo >= 0, "resident single-vector solve: a hand-over between workgroups timed out (device status %d); set LPGP_TRSV_RESIDENT=0", *hinfo);
-  mat->has_w = 1;
-  if (w_host) gather_padded(mat, hs, w_host);
+  mat->weights_resident();
+  if (w_host) mat->gather_padded(hs, w_host);
   return 0;
 }
 
@@ -1432,15 +1358,15 @@ int lpgp_mat_set_residual(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host) {
     } else {
       LPGP_HIP(hipEventSynchronize(ctx->ev_stage_r));
     }
-    scatter_padded(mat, r_host, ctx->h_stage_r);
+    mat->scatter_padded(r_host, ctx->h_stage_r);
     LPGP_HIP(hipMemcpyAsync(mat->r(), ctx->h_stage_r, (size_t)mat->pn * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
     LPGP_HIP(hipEventRecord(ctx->ev_stage_r, ctx->s_main));
-    mat->has_r = 1;
+    mat->residual_resident();
     return 0;
   }
   LPGP_CHECK(mat->pn_fact == mat->pn, "lpgp_mat_set_residual: matrix is not factored");      // (this branch has no lpgp_potrf_predict to consume an unfactored one)
   std::vector<double> hp((size_t)mat->pn);
-  scatter_padded(mat, r_host, hp.data());
+  mat->scatter_padded(r_host, hp.data());
   // NOT on the panel stream: the residual's place in HBM is touched by no kernel of the factorisation, so the upload need
   // not queue behind an enqueued factorisation (lpgp_potrf_enqueue); it is complete when this call returns.  The update
   // stream of the blocked solves is idle whenever this is called (its work is joined into the panel stream at the end of
@@ -1449,7 +1375,7 @@ int lpgp_mat_set_residual(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host) {
   hipStream_t sc = (mat->unchecked && ctx->s_upd_all && !ctx->single_stream) ? ctx->s_upd_all : ctx->s_main;
   LPGP_HIP(hipMemcpyAsync(mat->r(), hp.data(), (size_t)mat->pn * sizeof(double), hipMemcpyHostToDevice, sc));
   LPGP_HIP(hipStreamSynchronize(sc));
-  mat->has_r = 1;
+  mat->residual_resident();
   return 0;
 }
 
@@ -1698,24 +1624,17 @@ int lpgp_potrf_predict(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_rhs* K, const double* 
   ctx->d_info_cur = mat->d_status;
   const int rc = potrf_predict_blocked(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, K->v, K->ld, K->m_pad);
   if (rc != 0) {
-    if (fresh) mat->poisoned = 1;    // (partly factored in place with pn_fact unchanged -- a retry would factor a half-factored matrix)
+    if (fresh) mat->poison();        // (partly factored in place with pn_fact unchanged -- a retry would factor a half-factored matrix)
     return rc;
   }
-  if (fresh) {
-    mat->pn_fact = mat->pn;          // provisionally, as lpgp_potrf_enqueue: lpgp_mat_check / lpgp_mat_truncate take it back on failure
-    mat->unchecked = 1;
-    mat->has_w = 0;
-  }
-  mat->status_known = 0;
+  if (fresh) mat->factor_enqueued(true);     // (provisionally, as lpgp_potrf_enqueue; the residual that rode along stays resident)
+  mat->status_stale();
   // mean, variance and the status word of the factorisation come back together: two asynchronous copies into pinned memory,
   // ONE wait (until round 5: two blocking copies into pageable memory here and a third in lpgp_mat_check, ~25 us each --
   // a tenth of a step of the reference's own problem sizes)
   int* const hinfo = ctx->h_info_pinned + 4;
   LPGP_TRY(reduce_read_back(ctx, mat, K, zcol, true, prior_mean_host, kxx_host, mean_host, var_host, hinfo));
-  if (mat->unchecked) {
-    mat->status_value = *hinfo;
-    mat->status_known = 1;
-  }
+  mat->status_read_back(*hinfo);
   return 0;
 }
 
@@ -1846,10 +1765,7 @@ int lpgp_mat_inverse(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat** out) {
   lpgp_mat* created = nullptr;
   LPGP_TRY(lpgp_mat_create(ctx, mat->pn, &created));
   std::unique_ptr<lpgp_mat, Destroy> m(created);
-  m->blocks = mat->blocks;
-  m->n = mat->n;
-  m->pn = mat->pn;
-  m->pn_fact = 0;                                // (a plain symmetric matrix in the lower triangle, not a factor)
+  m->adopt_layout(*mat);                         // (not factored: a plain symmetric matrix in the lower triangle)
   LPGP_TRY(mat_inverse_into(ctx, mat, m.get()));
   LPGP_HIP(hipStreamSynchronize(ctx->s_main));   // (a failure of the device work is reported here, with the handle still owned)
   *out = m.release();
@@ -1933,9 +1849,11 @@ int lpgp_rhs_to_host(lpgp_ctx* ctx, const lpgp_mat* mat, lpgp_rhs* rhs, double* 
   }
   LPGP_HIP(hipStreamSynchronize(ctx->s_main));       // assembly launches are asynchronous
   LPGP_HIP(hipMemcpy(h.data(), rhs->v, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (const auto& b : mat->blocks)
-    for (int64_t i = 0; i < b.n; ++i)
-      for (int64_t j = 0; j < rhs->m; ++j) out_host[(b.off + i) * rhs->m + j] = h[(size_t)(b.poff + i + j * rhs->ld)];
+  std::vector<double> col((size_t)mat->n);
+  for (int64_t j = 0; j < rhs->m; ++j) {
+    mat->gather_padded(h.data() + j * rhs->ld, col.data());
+    for (int64_t i = 0; i < mat->n; ++i) out_host[i * rhs->m + j] = col[(size_t)i];
+  }
   return 0;
 }
 

@@ -154,10 +154,8 @@ void ev_stage(const lpgp_mat* mat, const double* const* vecs, int nvec, std::vec
   h->assign((size_t)(nvec * pn + (pn + 1) / 2), 0.0);
   int32_t* lrow = reinterpret_cast<int32_t*>(h->data() + (size_t)nvec * pn);
   std::fill(lrow, lrow + pn, -1);
-  for (const auto& b : mat->blocks) {
-    for (int k = 0; k < nvec; ++k) std::memcpy(h->data() + (size_t)k * pn + b.poff, vecs[k] + b.off, (size_t)b.n * sizeof(double));
-    for (int64_t i = 0; i < b.n; ++i) lrow[b.poff + i] = (int32_t)(b.off + i);
-  }
+  for (int k = 0; k < nvec; ++k) mat->scatter_padded(vecs[k], h->data() + (size_t)k * pn);
+  mat->logical_of_padded(lrow);
 }
 
 int ev_upload(lpgp_ctx* ctx, double* dst, const std::vector<double>& h) {
@@ -231,7 +229,7 @@ int mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host) {
   LPGP_TRY(inverse_diag_device(ctx, mat, dd.as()));
   LPGP_TRY(ev_download(ctx, h.data(), dd.as(), (size_t)pn));      // the n numbers, once, at the end
   LPGP_TRY(drain.wait());
-  for (const auto& b : mat->blocks) std::memcpy(out_host + b.off, h.data() + b.poff, (size_t)b.n * sizeof(double));
+  mat->gather_padded(h.data(), out_host);
   return 0;
 }
 
@@ -263,11 +261,9 @@ int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_
   LPGP_TRY(ev_download(ctx, res.data(), d + o_res, res.size()));
   LPGP_TRY(drain.wait());
   LPGP_TRY(ev_check_status(res[(size_t)(3 * pn)], "lpgp_mat_loo"));
-  for (const auto& b : mat->blocks) {
-    std::memcpy(mean_host + b.off, res.data() + b.poff, (size_t)b.n * sizeof(double));
-    std::memcpy(var_host + b.off, res.data() + pn + b.poff, (size_t)b.n * sizeof(double));
-    std::memcpy(logp_host + b.off, res.data() + 2 * pn + b.poff, (size_t)b.n * sizeof(double));
-  }
+  mat->gather_padded(res.data(), mean_host);
+  mat->gather_padded(res.data() + pn, var_host);
+  mat->gather_padded(res.data() + 2 * pn, logp_host);
   logp_host[n] = res[(size_t)(3 * pn)];
   return 0;
 }

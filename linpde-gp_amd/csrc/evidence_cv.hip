@@ -260,12 +260,8 @@ int mat_cv(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const double* r_h
   const int64_t pn = mat->pn, n = mat->n, T = pn / TILE;
   hipStream_t st = ctx->s_main;
   FoldTable tab;
-  {
-    std::vector<FoldBlock> fb;
-    for (const auto& b : mat->blocks) fb.push_back(FoldBlock{b.n, b.off, b.poff});
-    std::string err;
-    LPGP_CHECK(fold_table_build(fb.data(), (int)fb.size(), fold_of, n, nfolds, &tab, &err) == 0, "lpgp_mat_cv: %s", err.c_str());
-  }
+  std::string err;
+  LPGP_CHECK(fold_table_build(mat->blocks.data(), (int)mat->blocks.size(), fold_of, n, nfolds, &tab, &err) == 0, "lpgp_mat_cv: %s", err.c_str());
   FactorView F;
   LPGP_TRY(factor_view(mat, &F));
   const int64_t m = tab.members(), ntile = (int64_t)tab.tile.size(), batch = std::min<int64_t>(ctx->cv_fold_batch, ntile);

@@ -153,23 +153,6 @@ int mat_inverse_into(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat* out) {
   return 0;        // asynchronous: consumers are ordered behind it on the main stream
 }
 
-// host staging as in evidence.hip: nvec logical vectors scattered into the padded layout (zeros in the padding rows), behind them the
-// map padded row -> logical row (-1: padding) as pn int32
-static void eg_stage(const lpgp_mat* mat, const double* const* vecs, const int64_t* offs, const int64_t* lens, int nvec, std::vector<double>* h) {
-  const int64_t pn = mat->pn;
-  h->assign((size_t)(nvec * pn + (pn + 1) / 2), 0.0);
-  int32_t* lrow = reinterpret_cast<int32_t*>(h->data() + (size_t)nvec * pn);
-  std::fill(lrow, lrow + pn, -1);
-  for (const auto& b : mat->blocks) {
-    for (int k = 0; k < nvec; ++k) {
-      // the part of vector k (logical rows [offs[k], offs[k] + lens[k])) that falls into this block
-      const int64_t lo = std::max(b.off, offs[k]), hi = std::min(b.off + b.n, offs[k] + lens[k]);
-      if (hi > lo) std::memcpy(h->data() + (size_t)k * pn + b.poff + (lo - b.off), vecs[k] + (lo - offs[k]), (size_t)(hi - lo) * sizeof(double));
-    }
-    for (int64_t i = 0; i < b.n; ++i) lrow[b.poff + i] = (int32_t)(b.off + i);
-  }
-}
-
 static int eg_finish(lpgp_ctx* ctx, hipStream_t st, double* d_part, int nwg, double* d_out, double out_host[2], StreamDrain* drain, const char* fn) {
   hipLaunchKernelGGL(evidence_grad_final_kernel, dim3(1), dim3(EG_THREADS), 0, st, (const double*)d_part, nwg, (const int*)ctx->d_info, d_out);
   LPGP_HIP(hipGetLastError());
@@ -189,8 +172,7 @@ int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const 
   FactorView F;
   LPGP_TRY(factor_view(mat, &F));
   std::vector<double> h;
-  const int64_t off0 = 0, len0 = mat->n;
-  eg_stage(mat, &r_host, &off0, &len0, 1, &h);
+  ev_stage(mat, &r_host, 1, &h);                 // (the host staging of evidence.hip)
   // [w (r on entry) | lrow] as staged, the scratch of the solve (+ 2 ticket words), the partials, the result
   const size_t o_tmp = h.size(), o_part = o_tmp + (size_t)pn + 2, o_out = o_part + 2 * EG_MAX_WGS;
   DevBuf buf;
@@ -216,11 +198,10 @@ int mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, i
   hipStream_t st = ctx->s_main;
   FactorView F;
   LPGP_TRY(factor_view(mat, &F));
-  std::vector<double> h, v((size_t)B.n, scalar);
-  if (v_host) for (int64_t i = 0; i < B.n; ++i) v[(size_t)i] += v_host[i];
+  std::vector<double> h, v((size_t)mat->n, 0.0);     // the diagonal of dG over all logical rows: zero outside block bi
+  for (int64_t i = 0; i < B.n; ++i) v[(size_t)(B.off + i)] = v_host ? scalar + v_host[i] : scalar;
   const double* vecs[2] = {r_host, v.data()};
-  const int64_t offs[2] = {0, B.off}, lens[2] = {mat->n, B.n};
-  eg_stage(mat, vecs, offs, lens, 2, &h);
+  ev_stage(mat, vecs, 2, &h);
   // [w (r on entry) | v | lrow] as staged, the scratch of the solve (+ 2 ticket words), the partials, the result
   const size_t o_tmp = h.size(), o_part = o_tmp + (size_t)pn + 2, o_out = o_part + 2 * EG_MAX_WGS;
   DevBuf buf;

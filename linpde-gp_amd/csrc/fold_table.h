@@ -7,12 +7,9 @@
 #include <string>
 #include <vector>
 
-namespace lpgp {
+#include "mat_state.h"
 
-// an observation block as the table needs it: logical rows, logical offset, padded offset (a multiple of 128)
-struct FoldBlock {
-  int64_t n, off, poff;
-};
+namespace lpgp {
 
 // The members of fold f are entries [start[f], start[f + 1]) of lrow / prow, in increasing Gram order (so in increasing padded
 // order too: the map logical -> padded row is monotone).  Folds of at most TB rows go through the tile kernels, many per launch;
@@ -33,7 +30,7 @@ struct FoldTable {
 
 // 0, or -2 with *err set: a block list that is not a partition of [0, n) into padded slots, an entry of fold_of outside
 // -1 .. nfolds - 1, an empty fold.  *out is written only on success.
-inline int fold_table_build(const FoldBlock* blocks, int nblocks, const int32_t* fold_of, int64_t n, int32_t nfolds, FoldTable* out, std::string* err) {
+inline int fold_table_build(const lpgp_block* blocks, int nblocks, const int32_t* fold_of, int64_t n, int32_t nfolds, FoldTable* out, std::string* err) {
   auto fail = [&](const std::string& msg) {
     if (err) *err = msg;
     return -2;
@@ -41,7 +38,7 @@ inline int fold_table_build(const FoldBlock* blocks, int nblocks, const int32_t*
   if (!blocks || nblocks < 1 || !fold_of || !out || n < 1 || nfolds < 1) return fail("fold table: bad argument");
   int64_t off = 0, poff = 0;
   for (int b = 0; b < nblocks; ++b) {
-    const FoldBlock& B = blocks[b];
+    const lpgp_block& B = blocks[b];
     if (B.n < 1 || B.off != off || B.poff < poff || B.poff % FoldTable::TB != 0)
       return fail("fold table: block " + std::to_string(b) + " does not continue the layout");
     off += B.n;

@@ -9,7 +9,6 @@
 
 #include "fold_table.h"
 
-using lpgp::FoldBlock;
 using lpgp::FoldTable;
 
 static int failures = 0;
@@ -21,11 +20,11 @@ static void expect(bool ok, const char* what, long long a = 0, long long b = 0) 
 }
 
 // blocks of the given sizes, each padded to the next multiple of 128, as lpgp_mat_add_block lays them out
-static std::vector<FoldBlock> layout(const std::vector<int64_t>& sizes) {
-  std::vector<FoldBlock> out;
+static std::vector<lpgp_block> layout(const std::vector<int64_t>& sizes) {
+  std::vector<lpgp_block> out;
   int64_t off = 0, poff = 0;
   for (int64_t n : sizes) {
-    out.push_back(FoldBlock{n, off, poff});
+    out.push_back(lpgp_block{n, off, poff, (n + 127) / 128 * 128});
     off += n;
     poff += (n + 127) / 128 * 128;
   }
@@ -33,14 +32,14 @@ static std::vector<FoldBlock> layout(const std::vector<int64_t>& sizes) {
 }
 
 // the literal formula, by a search for the block of logical row i
-static int64_t padded_row(const std::vector<FoldBlock>& blocks, int64_t i) {
-  for (const FoldBlock& b : blocks)
+static int64_t padded_row(const std::vector<lpgp_block>& blocks, int64_t i) {
+  for (const lpgp_block& b : blocks)
     if (i >= b.off && i < b.off + b.n) return b.poff + (i - b.off);
   return -1;
 }
 
 static void check_table(const std::vector<int64_t>& sizes, const std::vector<int32_t>& fold_of, int32_t nfolds) {
-  const std::vector<FoldBlock> blocks = layout(sizes);
+  const std::vector<lpgp_block> blocks = layout(sizes);
   const int64_t n = (int64_t)fold_of.size();
   FoldTable t;
   std::string err;
@@ -103,7 +102,7 @@ static void check_batches(int64_t ntile, int64_t batch) {
 }
 
 static void check_refusal(const std::vector<int64_t>& sizes, const std::vector<int32_t>& fold_of, int32_t nfolds, const char* needle) {
-  std::vector<FoldBlock> blocks = layout(sizes);
+  std::vector<lpgp_block> blocks = layout(sizes);
   FoldTable t;
   t.nfolds = -7;                                 // must stay as it is
   std::string err;

@@ -11,6 +11,7 @@
 #include "lpgp.h"
 #include "lpgp_desc.h"
 #include "factor_view.h"
+#include "mat_state.h"
 #include "options.h"
 
 namespace lpgp {
@@ -214,38 +215,19 @@ struct lpgp_pts {
   size_t bytes = 0;                // size of the allocation behind x
 };
 
-struct lpgp_block {
-  int64_t n;                       // logical rows
-  int64_t off;                     // logical offset
-  int64_t poff;                    // padded offset (multiple of TILE)
-  int64_t pn;                      // padded rows
-};
-
-struct lpgp_mat {
-  lpgp_ctx* ctx;
-  int64_t cap;                     // padded capacity of the GLOBAL matrix (multiple of TILE); single GPU: == leading dimension
+struct lpgp_mat : lpgp::MatState {  // block table and factor state: mat_state.h
+  lpgp_ctx* ctx = nullptr;
+  int64_t cap = 0;                 // padded capacity of the GLOBAL matrix (multiple of TILE); single GPU: == leading dimension
   int64_t lr_cap = 0, lc_cap = 0;  // rows / columns of this rank's share (== cap on a single GPU); lr_cap is the leading dimension of a
   double* dblk = nullptr;          // multi-GPU only: the nb x nb diagonal blocks of the factor, replicated on every rank:
                                    //   block K at dblk + K * nb * nb, column-major, leading dimension nb
-  double* a;                       // device lr_cap x lc_cap column-major (lower part meaningful): this rank's tiles
-  double* linv;                    // device (cap/TILE) tiles of TILE x TILE: inverse of each diagonal tile of L
-  double* w;                       // device 2*cap: [representer weights | residual r] (padded layout)
-  std::vector<lpgp_block> blocks;  // blocks of the current VIEW (lpgp_mat_set_view): a leading run of the observation blocks
-  std::vector<lpgp_block> hidden;  // blocks behind the view (appended by later conditionings; their part of the factor stays in place)
-  int64_t n;                       // logical size (of the view)
-  int64_t pn;                      // padded size in use (of the view)
-  int64_t pn_fact;                 // padded columns factored so far (of the view)
-  int64_t pn_fact_all = 0;         // the same over view + hidden blocks (meaningful while hidden is non-empty)
-  int has_w;
-  int has_r;                       // residual resident (lpgp_mat_set_residual)
+  double* a = nullptr;             // device lr_cap x lc_cap column-major (lower part meaningful): this rank's tiles
+  double* linv = nullptr;          // device (cap/TILE) tiles of TILE x TILE: inverse of each diagonal tile of L
+  double* w = nullptr;             // device 2*cap: [representer weights | residual r] (padded layout)
   int* d_status = nullptr;         // device word: first non-positive pivot of the factorisations enqueued since the last lpgp_mat_check (sticky)
-  int unchecked = 0;               // a factorisation was enqueued (lpgp_potrf_enqueue) and its status not read yet
-  int status_known = 0;            // lpgp_potrf_predict read the status word back with its results: lpgp_mat_check needs no copy
-  int status_value = 0;
-  int poisoned = 0;                // a factorisation of this matrix ended undefined -- a hand-over of a resident kernel timed out (device status < 0), or a
-                                   // launch failed half way through the in-place factorisation: every entry point that reads or extends the factor fails from then on
   double* r() const { return w + cap; }
 };
+static_assert(lpgp::MatState::TB == lpgp::TILE, "the tile edge");
 
 struct lpgp_rhs {
   lpgp_ctx* ctx;
@@ -268,6 +250,12 @@ namespace lpgp {
     LPGP_CHECK((ctx) != nullptr, "null context handle");        \
     LPGP_HIP(hipSetDevice((ctx)->device));                      \
   } while (0)
+
+// a transition of mat_state.h that refused (rc != 0): its text becomes the error
+inline int refused(int rc, const std::string& err) {
+  if (rc != 0) set_error("%s", err.c_str());
+  return rc;
+}
 
 // The factor of a single-GPU matrix as the drivers of potrf.hip, chain.hip and trsv.hip take it.  The leading dimension is that of
 // this rank's share, lr_cap; the drivers address GLOBAL tiles with it, which is right only where the share is the whole matrix:

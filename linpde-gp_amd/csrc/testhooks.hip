@@ -263,8 +263,7 @@ int lpgp_test_force_status(lpgp_ctx* ctx, lpgp_mat* mat, int32_t value) {
   LPGP_DEVICE(ctx);
   LPGP_HIP(hipStreamSynchronize(ctx->s_main));
   LPGP_HIP(hipMemcpy(mat->d_status, &value, sizeof(int), hipMemcpyHostToDevice));
-  mat->unchecked = 1;
-  mat->status_known = 0;
+  mat->status_pending();
   return 0;
 }
 
@@ -282,9 +281,9 @@ int lpgp_test_solve_vec_fwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, 
   hipStream_t st = ctx->s_main;
   FactorView F;
   LPGP_TRY(factor_view(mat, &F));
-  std::vector<double> h((size_t)pn, 0.0);
+  std::vector<double> h((size_t)pn);
   int info = 0;
-  for (const auto& b : mat->blocks) std::memcpy(h.data() + b.poff, r_host + b.off, (size_t)b.n * sizeof(double));
+  mat->scatter_padded(r_host, h.data());
   // [r as staged | z + the ticket word of the resident solve]
   DevBuf buf;
   LPGP_TRY(DevBuf::raw((size_t)(2 * pn + 2) * sizeof(double), &buf));

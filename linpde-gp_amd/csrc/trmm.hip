@@ -127,8 +127,7 @@ int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s,
   const int64_t nchunks = count_chunks(kc);
   // integer tables: [logical row of padded row p, or -1 | first chunk of tile row i (T + 1) | tile row of chunk | first tile of chunk]
   std::vector<int32_t> tab((size_t)(pn + T + 1 + 2 * nchunks), -1);
-  for (const auto& b : mat->blocks)
-    for (int64_t r = 0; r < b.n; ++r) tab[(size_t)(b.poff + r)] = (int32_t)(b.off + r);
+  mat->logical_of_padded(tab.data());
   int32_t* h_chunk0 = tab.data() + pn;
   int32_t* h_row = h_chunk0 + T + 1;
   int32_t* h_j0 = h_row + nchunks;
@@ -143,11 +142,11 @@ int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s,
   // Z as the kernel reads it: [column tile][padded row][16], zeros in the padding rows and columns; the shift behind it
   const size_t zdoubles = (size_t)nct * pn * TR_ST;
   std::vector<double> hz(zdoubles + (size_t)n, 0.0);
-  for (const auto& b : mat->blocks)
-    for (int64_t r = 0; r < b.n; ++r) {
-      const double* zr = Z_host + (b.off + r) * s;
-      for (int64_t c = 0; c < s; ++c) hz[((size_t)(c / TR_ST) * pn + (size_t)(b.poff + r)) * TR_ST + (size_t)(c % TR_ST)] = zr[c];
-    }
+  for (int64_t p = 0; p < pn; ++p) {
+    if (tab[(size_t)p] < 0) continue;
+    const double* zr = Z_host + (int64_t)tab[(size_t)p] * s;
+    for (int64_t c = 0; c < s; ++c) hz[((size_t)(c / TR_ST) * pn + (size_t)p) * TR_ST + (size_t)(c % TR_ST)] = zr[c];
+  }
   if (shift_host) std::memcpy(hz.data() + zdoubles, shift_host, (size_t)n * sizeof(double));
   const size_t bz = hz.size() * sizeof(double), bt = tab.size() * sizeof(int32_t);
   const size_t bp = (size_t)nchunks * nct * TILE * TR_ST * sizeof(double), bo = (size_t)n * s * sizeof(double);

@@ -1,0 +1,30 @@
+"""The host bookkeeping of a matrix handle (`csrc/mat_state.h`: the block table and the factor state `lpgp_mat` derives from), on
+the host: a stand-alone program (`csrc/hosttest/mat_state_check.cpp`) built with AddressSanitizer + UBSan and run as a subprocess
+walks the transitions the entry points of api.hip drive -- layout of ragged blocks and the logical <-> padded copies, eager and
+enqueued factorisations, the status a prediction reads back, `lpgp_mat_check` with a pivot in a hidden block and with a timed-out
+hand-over, views and clones of a prefix, rollback -- against literal values.  tests/test_gpu_mat_lifecycle.py pins the same walk
+through the C ABI on the device."""
+import os
+import shutil
+import subprocess
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(os.path.dirname(HERE), "linpde-gp_amd", "csrc")
+
+
+def test_mat_state_transitions_under_sanitizers(tmp_path):
+    gxx = shutil.which(os.environ.get("CXX", "g++"))
+    assert gxx is not None, "no host C++ compiler"
+    exe = str(tmp_path / "mat_state_check")
+    # the sanitizer runtimes are linked INTO the program, so that it does not care what else the environment loads before it
+    clang = "clang" in subprocess.run([gxx, "--version"], capture_output=True, text=True).stdout
+    static_rt = ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]
+    subprocess.run([gxx, "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    *static_rt, "-Wall", "-Wextra", "-I" + CSRC, os.path.join(CSRC, "hosttest", "mat_state_check.cpp"), "-o", exe],
+                   check=True, capture_output=True, text=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    res = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=120)
+    print(res.stdout[-3000:])
+    assert res.returncode == 0, res.stdout[-3000:] + "\n" + res.stderr[-4000:]
+    assert "mat_state_check: all checks passed" in res.stdout
+    assert "ERROR: AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr
