@@ -68,6 +68,14 @@ int  lpgp_test_force_status(lpgp_ctx* ctx, lpgp_mat* mat, int32_t value);
  * trsv_resident selects (1: the resident kernel of trsv.hip, 0: one launch per tile row, potrf.hip), and z comes back in the
  * PADDED layout (lpgp_mat_padded_size doubles).  A negative status word (a timed-out hand-over) is returned as an error.  */
 int  lpgp_test_solve_vec_fwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double* z_host_padded);
+/* the backward half of the single-vector solve alone, x = L^{-T} y, by the functions lpgp_solve_weights, lpgp_mat_loo, lpgp_mat_cv and
+ * the evidence gradients run it through (the form the option trsv_resident selects).  y and x are in the PADDED layout
+ * (lpgp_mat_padded_size doubles each); y is taken as given, padding entries included.  Same refusals and status handling as above. */
+int  lpgp_test_solve_vec_bwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* y_host_padded, double* x_host_padded);
+/* the multi-column backward substitution of lpgp_potrs alone (trsm_lower_t_blocked), V <- L^{-T} V in place on a host block of
+ * lpgp_mat_padded_size rows x m_pad columns, column-major with the padded size as leading dimension; m_pad a multiple of 128.
+ * Single GPU, fully factored, status read.                                                                          */
+int  lpgp_test_trsm_lower_t(lpgp_ctx* ctx, lpgp_mat* mat, double* v_host_padded, int64_t m_pad);
 
 #ifdef __cplusplus
 }

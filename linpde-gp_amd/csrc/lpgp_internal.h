@@ -480,6 +480,10 @@ int solve_vec(lpgp_ctx* ctx, FactorView F, int64_t T, double* v, double* tmp, in
 int solve_vec_resident(lpgp_ctx* ctx, FactorView F, int64_t T, double* v, double* tmp, int* info);      // trsv.hip
 int solve_vec_fwd(lpgp_ctx* ctx, hipStream_t st, FactorView F, int64_t T, double* b, double* x);
 int solve_vec_fwd_resident(lpgp_ctx* ctx, FactorView F, int64_t T, const double* b, double* x, int* info);   // trsv.hip: the forward half alone
+// the backward half alone, x <- L^{-T} y.  Per tile row (potrf.hip): y is consumed as the running right-hand side.  Resident (trsv.hip):
+// the entries of y are read only; y has T * 128 + 2 doubles, of which the LAST (y + T * 128 + 1) is the ticket word, at -1 (all bits set) on entry
+int solve_vec_bwd(lpgp_ctx* ctx, hipStream_t st, FactorView F, int64_t T, double* y, double* x);
+int solve_vec_bwd_resident(lpgp_ctx* ctx, FactorView F, int64_t T, double* y, double* x, int* info);
 // evidence.hip: the quantities read off the factor of a fully factored single-GPU matrix (lpgp_mat_evidence, lpgp_mat_inverse_diag, lpgp_mat_loo)
 int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]);
 int mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host);

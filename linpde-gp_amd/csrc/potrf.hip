@@ -945,21 +945,26 @@ int solve_vec_fwd(lpgp_ctx* ctx, hipStream_t st, FactorView F, int64_t T64, doub
   return 0;
 }
 
+// x <- L^{-T} y on `st` (padded length T*128, device); y is consumed as the running right-hand side
+int solve_vec_bwd(lpgp_ctx* ctx, hipStream_t st, FactorView F, int64_t T64, double* y, double* x) {
+  const int T = (int)T64;
+  const double* a = F.a;
+  hipLaunchKernelGGL(trsv_bwd_head_kernel, dim3(1), dim3(512), 0, st, (const double*)F.inv(T - 1), (const double*)F.diag(T - 1), F.ld,
+                     (const double*)(y + (int64_t)(T - 1) * TILE), x + (int64_t)(T - 1) * TILE);
+  for (int k = T - 1; k >= 1; --k)
+    hipLaunchKernelGGL(trsv_bwd_step_kernel, dim3(k), dim3(512), 0, st, a, F.ld, (const double*)F.inv(k - 1), y, x, (int64_t)k * TILE);
+  LPGP_HIP(hipGetLastError());
+  return 0;
+}
+
 // v (padded length T*128, device) <- G^{-1} v, using scratch vector `tmp` of the same length
 int solve_vec(lpgp_ctx* ctx, FactorView F, int64_t T64, double* v, double* tmp, int* info) {
   if (ctx->trsv_resident) return solve_vec_resident(ctx, F, T64, v, tmp, info);
-  const int T = (int)T64;
   hipStream_t st = ctx->s_main;
-  const double* a = F.a;
   // forward: L tmp = v   (v is consumed as the running right-hand side)
   LPGP_TRY(solve_vec_fwd(ctx, st, F, T64, v, tmp));
   // backward: L^T v = tmp  (tmp is consumed as the running right-hand side)
-  hipLaunchKernelGGL(trsv_bwd_head_kernel, dim3(1), dim3(512), 0, st, (const double*)F.inv(T - 1), (const double*)F.diag(T - 1), F.ld,
-                     (const double*)(tmp + (int64_t)(T - 1) * TILE), v + (int64_t)(T - 1) * TILE);
-  for (int k = T - 1; k >= 1; --k)
-    hipLaunchKernelGGL(trsv_bwd_step_kernel, dim3(k), dim3(512), 0, st, a, F.ld, (const double*)F.inv(k - 1), tmp, v, (int64_t)k * TILE);
-  LPGP_HIP(hipGetLastError());
-  return 0;
+  return solve_vec_bwd(ctx, st, F, T64, tmp, v);
 }
 
 }  // namespace lpgp

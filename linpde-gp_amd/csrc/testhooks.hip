@@ -267,16 +267,22 @@ int lpgp_test_force_status(lpgp_ctx* ctx, lpgp_mat* mat, int32_t value) {
   return 0;
 }
 
+// the refusals the hooks on a factor share: single GPU, fully factored, status read
+#define LPGP_TEST_FACTORED(ctx, mat, who)                                                                                          \
+  do {                                                                                                                             \
+    LPGP_MAT_ALIVE(mat, who);                                                                                                      \
+    LPGP_CHECK(!(ctx)->distributed(), who ": single GPU only");                                                                    \
+    LPGP_CHECK((mat)->pn > 0 && (mat)->pn_fact == (mat)->pn, who ": matrix is not (fully) factored");                              \
+    LPGP_CHECK(!(mat)->unchecked, who ": the status of an enqueued factorisation has not been read (lpgp_mat_check)");             \
+  } while (0)
+
 // z = L^{-1} r, the forward half of the single-vector solve alone, as lpgp_mat_evidence runs it: r scattered into the padded layout
 // (zeros in the padding rows), the dispatch on ctx->trsv_resident (trsv.hip solve_vec_fwd_resident, else potrf.hip solve_vec_fwd),
 // z back in the padded layout (mat->pn doubles).  A negative status word (a timed-out hand-over) is a library error.
 int lpgp_test_solve_vec_fwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double* z_host_padded) {
   LPGP_CHECK(ctx && mat && r_host && z_host_padded, "lpgp_test_solve_vec_fwd: null argument");
   LPGP_DEVICE(ctx);
-  LPGP_MAT_ALIVE(mat, "lpgp_test_solve_vec_fwd");
-  LPGP_CHECK(!ctx->distributed(), "lpgp_test_solve_vec_fwd: single GPU only");
-  LPGP_CHECK(mat->pn > 0 && mat->pn_fact == mat->pn, "lpgp_test_solve_vec_fwd: matrix is not (fully) factored");
-  LPGP_CHECK(!mat->unchecked, "lpgp_test_solve_vec_fwd: the status of an enqueued factorisation has not been read (lpgp_mat_check)");
+  LPGP_TEST_FACTORED(ctx, mat, "lpgp_test_solve_vec_fwd");
   const int64_t pn = mat->pn, T = pn / TILE;
   hipStream_t st = ctx->s_main;
   FactorView F;
@@ -297,6 +303,56 @@ int lpgp_test_solve_vec_fwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, 
   LPGP_HIP(hipMemcpyAsync(&info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, st));
   LPGP_TRY(drain.wait());
   LPGP_CHECK(info >= 0, "lpgp_test_solve_vec_fwd: resident single-vector solve: a hand-over between workgroups timed out (status %d)", info);
+  return 0;
+}
+
+// x = L^{-T} y, the backward half of the single-vector solve alone, by the functions solve_vec / solve_vec_resident call for it
+// (potrf.hip solve_vec_bwd, trsv.hip solve_vec_bwd_resident; the dispatch on ctx->trsv_resident is solve_vec's).  y is taken as
+// given, padding entries included; both vectors in the padded layout (mat->pn doubles).  A negative status word is a library error.
+int lpgp_test_solve_vec_bwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* y_host_padded, double* x_host_padded) {
+  LPGP_CHECK(ctx && mat && y_host_padded && x_host_padded, "lpgp_test_solve_vec_bwd: null argument");
+  LPGP_DEVICE(ctx);
+  LPGP_TEST_FACTORED(ctx, mat, "lpgp_test_solve_vec_bwd");
+  const int64_t pn = mat->pn, T = pn / TILE;
+  hipStream_t st = ctx->s_main;
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
+  int info = 0;
+  // [x | y + the two ticket words of the resident solve: the backward half counts the second one up from -1]
+  DevBuf buf;
+  LPGP_TRY(DevBuf::raw((size_t)(2 * pn + 2) * sizeof(double), &buf));
+  double *const x = buf.as(), *const y = x + pn;
+  StreamDrain drain{st};                         // (the status word and the caller's arrays are borrowed by the copies)
+  LPGP_HIP(hipMemcpyAsync(y, y_host_padded, (size_t)pn * sizeof(double), hipMemcpyHostToDevice, st));
+  LPGP_HIP(hipMemsetAsync(y + pn, 0xFF, 2 * sizeof(double), st));
+  LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
+  if (ctx->trsv_resident) LPGP_TRY(solve_vec_bwd_resident(ctx, F, T, y, x, ctx->d_info));
+  else LPGP_TRY(solve_vec_bwd(ctx, st, F, T, y, x));
+  LPGP_HIP(hipMemcpyAsync(x_host_padded, x, (size_t)pn * sizeof(double), hipMemcpyDeviceToHost, st));
+  LPGP_HIP(hipMemcpyAsync(&info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, st));
+  LPGP_TRY(drain.wait());
+  LPGP_CHECK(info >= 0, "lpgp_test_solve_vec_bwd: resident single-vector solve: a hand-over between workgroups timed out (status %d)", info);
+  return 0;
+}
+
+// V <- L^{-T} V by trsm_lower_t_blocked alone (the backward half of lpgp_potrs), in place on a host block of pn x m_pad doubles,
+// column-major with leading dimension pn, m_pad a multiple of 128; the FactorView is the one solve_lower_t (api.hip) builds.
+int lpgp_test_trsm_lower_t(lpgp_ctx* ctx, lpgp_mat* mat, double* v_host, int64_t m_pad) {
+  LPGP_CHECK(ctx && mat && v_host && m_pad > 0 && m_pad % TILE == 0, "lpgp_test_trsm_lower_t: bad argument (m_pad a positive multiple of 128)");
+  LPGP_DEVICE(ctx);
+  LPGP_TEST_FACTORED(ctx, mat, "lpgp_test_trsm_lower_t");
+  const int64_t pn = mat->pn;
+  const size_t bytes = (size_t)pn * (size_t)m_pad * sizeof(double);
+  hipStream_t st = ctx->s_main;
+  FactorView F;
+  LPGP_TRY(factor_view(mat, &F));
+  DevBuf dv;
+  LPGP_TRY(DevBuf::raw(bytes, &dv));
+  StreamDrain drain{st};                         // (the caller's array is borrowed by the copies)
+  LPGP_HIP(hipMemcpyAsync(dv.as(), v_host, bytes, hipMemcpyHostToDevice, st));
+  LPGP_TRY(trsm_lower_t_blocked(ctx, F, pn / TILE, dv.as(), pn, m_pad));
+  LPGP_HIP(hipMemcpyAsync(v_host, dv.as(), bytes, hipMemcpyDeviceToHost, st));
+  LPGP_TRY(drain.wait());
   return 0;
 }
 

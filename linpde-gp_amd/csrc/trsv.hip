@@ -334,8 +334,18 @@ int solve_vec_resident(lpgp_ctx* ctx, FactorView F, int64_t T64, double* v, doub
   hipLaunchKernelGGL(trsv_fwd_resident_kernel, dim3((unsigned)T), dim3(512), 0, st, g);
   prof_end(ctx, st);
   // backward: L^T v = tmp
-  LPGP_HIP(hipMemsetAsync(v, 0xFF, nb, st));
-  g.b = tmp; g.x = v; g.ticket = reinterpret_cast<int*>(tmp + (size_t)T * TILE + 1);
+  return solve_vec_bwd_resident(ctx, F, T64, tmp, v, info);
+}
+
+// x <- L^{-T} y on the panel stream, the backward half alone; the T * 128 entries of y are read only, and y has T * 128 + 2 doubles:
+// the LAST one carries this half's ticket word, which is at -1 on entry (solve_vec_resident sets it together with the forward
+// half's) and counted up by the kernel.  `info` as above.
+int solve_vec_bwd_resident(lpgp_ctx* ctx, FactorView F, int64_t T64, double* y, double* x, int* info) {
+  const int T = (int)T64;
+  hipStream_t st = ctx->s_main;
+  TrsvArgs g = trsv_args(F, T, info);
+  LPGP_HIP(hipMemsetAsync(x, 0xFF, (size_t)T * TILE * sizeof(double), st));
+  g.b = y; g.x = x; g.ticket = reinterpret_cast<int*>(y + (size_t)T * TILE + 1);
   prof_begin(ctx, st, LPGP_K_TRSM, (double)T * TILE * (double)T * TILE, 4.0 * (double)T * TILE * (double)T * TILE);
   hipLaunchKernelGGL(trsv_bwd_resident_kernel, dim3((unsigned)T), dim3(512), 0, st, g);
   prof_end(ctx, st);

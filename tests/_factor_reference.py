@@ -1,7 +1,8 @@
 """Long-double references computed from a GIVEN lower-triangular factor L (float64 in, `np.longdouble` inside), for the suite
 that holds csrc/evidence.hip and the forward half of the single-vector solve to the device's own factor
 (test_gpu_evidence_backward.py): with L shared between the device and the reference the cond-bound error of the factorisation
-drops out and a measure sees the solve, the column sums, the reductions and the epilogue alone.  Checked against 50-digit
+drops out and a measure sees the solve, the column sums, the reductions and the epilogue alone; lower_tmv() and backward_error_t()
+are the transposed forms for the backward substitutions (test_gpu_solve_t_backward.py).  Checked against 50-digit
 mpmath in test_factor_reference.py.  A plain module the suites import, not a conftest."""
 import numpy as np
 
@@ -80,3 +81,29 @@ def relative_error(got, ref):
     zero = ref == 0
     assert not np.any(err[zero] != 0), "a nonzero value where the reference is exactly zero"
     return float(np.max(np.where(zero, LD(0), err / np.where(zero, LD(1), np.abs(ref)))))
+
+
+def lower_tmv(L, x, absolute=False):
+    """L^T x (absolute: |L|^T |x|) in long double for a vector or the columns of a matrix x, by row slabs of L: only the columns
+    left of a slab's end take part."""
+    xl = np.asarray(x).astype(LD)
+    if absolute:
+        xl = np.abs(xl)
+    out = np.zeros(xl.shape, dtype=LD)
+    for i in range(0, L.shape[0], 512):
+        e = min(i + 512, L.shape[0])
+        blk = L[i:e, :e].astype(LD)
+        out[:e] += (np.abs(blk) if absolute else blk).T @ xl[i:e]
+    return out
+
+
+def backward_error_t(L, x, y):
+    """Componentwise backward error of L^T x = y: max_i |y - L^T x|_i / (|L^T| |x| + |y|)_i with the residual in long double, the
+    conventions of backward_error(); for matrices x, y the maximum is taken per column and an array comes back."""
+    yl = np.asarray(y).astype(LD)
+    res = np.abs(yl - lower_tmv(L, x))
+    den = lower_tmv(L, x, absolute=True) + np.abs(yl)
+    zero = den == 0
+    assert not np.any(res[zero] != 0), "a nonzero residual where |L^T||x| + |y| is zero"
+    e = np.max(np.where(zero, LD(0), res / np.where(zero, LD(1), den)), axis=0)
+    return float(e) if e.ndim == 0 else e.astype(np.float64)

@@ -17,7 +17,8 @@ from linpde_gp_amd._lib import check
 HOOKS_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "liblpgp_testhooks.so")
 
 EXPORTED = ["lpgp_test_stair_enumerate", "lpgp_test_gemm", "lpgp_test_gemm_cyc", "lpgp_test_potrf_tile", "lpgp_test_tile_step", "lpgp_test_panel_solve",
-            "lpgp_debug_tile_xcc", "lpgp_probe_mfma_f64", "lpgp_probe_hbm_write", "lpgp_test_force_status", "lpgp_test_solve_vec_fwd"]
+            "lpgp_debug_tile_xcc", "lpgp_probe_mfma_f64", "lpgp_probe_hbm_write", "lpgp_test_force_status", "lpgp_test_solve_vec_fwd", "lpgp_test_solve_vec_bwd",
+            "lpgp_test_trsm_lower_t"]
 
 
 def _load() -> C.CDLL:
@@ -43,6 +44,8 @@ def _load() -> C.CDLL:
     sig("lpgp_probe_hbm_write", C.c_int, vp, i64, pd)
     sig("lpgp_test_force_status", C.c_int, vp, vp, i32)
     sig("lpgp_test_solve_vec_fwd", C.c_int, vp, vp, pd, pd)
+    sig("lpgp_test_solve_vec_bwd", C.c_int, vp, vp, pd, pd)
+    sig("lpgp_test_trsm_lower_t", C.c_int, vp, vp, pd, i64)
     return lib
 
 
@@ -152,6 +155,28 @@ def solve_vec_fwd(ctx: Context, mat, r: np.ndarray) -> np.ndarray:
     pd = C.POINTER(C.c_double)
     check(lib.lpgp_test_solve_vec_fwd(ctx._h, mat._h, r.ctypes.data_as(pd), z.ctypes.data_as(pd)), "lpgp_test_solve_vec_fwd")
     return z
+
+
+def solve_vec_bwd(ctx: Context, mat, y: np.ndarray) -> np.ndarray:
+    """x = L^{-T} y by the backward half of the single-vector solve as `solve_weights` runs it (`lpgp_test_solve_vec_bwd`; the option
+    trsv_resident selects the form).  `y` and x in the PADDED layout (`mat.padded_n` doubles); the padding of `y` is taken as given."""
+    y = np.ascontiguousarray(y, dtype=np.double)
+    if y.shape != (mat.padded_n,):
+        raise ValueError(f"right-hand side must have shape ({mat.padded_n},), got {y.shape}")
+    x = np.full(mat.padded_n, np.nan)
+    pd = C.POINTER(C.c_double)
+    check(lib.lpgp_test_solve_vec_bwd(ctx._h, mat._h, y.ctypes.data_as(pd), x.ctypes.data_as(pd)), "lpgp_test_solve_vec_bwd")
+    return x
+
+
+def trsm_lower_t(ctx: Context, mat, V: np.ndarray) -> np.ndarray:
+    """L^{-T} V by the multi-column backward substitution of `potrs` alone (`lpgp_test_trsm_lower_t`).  `V`: `mat.padded_n` rows
+    (PADDED layout) x a multiple of 128 columns; returns a new column-major array."""
+    V = np.array(V, dtype=np.double, order="F")
+    if V.ndim != 2 or V.shape[0] != mat.padded_n or V.shape[1] == 0 or V.shape[1] % 128:
+        raise ValueError(f"block must have {mat.padded_n} rows and a multiple of 128 columns, got {V.shape}")
+    check(lib.lpgp_test_trsm_lower_t(ctx._h, mat._h, V.ctypes.data_as(C.POINTER(C.c_double)), V.shape[1]), "lpgp_test_trsm_lower_t")
+    return V
 
 
 def force_status(ctx: Context, mat, value: int) -> None:

@@ -1,5 +1,5 @@
-"""tests/_factor_reference.py (the long-double references of test_gpu_evidence_backward.py) against 50-digit mpmath at n = 40, and
-LAPACK's own distance from those references on the matrices the GPU suite uses.  No GPU.
+"""tests/_factor_reference.py (the long-double references of test_gpu_evidence_backward.py and test_gpu_solve_t_backward.py)
+against 50-digit mpmath at n = 40, and LAPACK's own distance from those references on the matrices the GPU suite uses.  No GPU.
 
 The references must be good to a small fraction of one u = 2^-53 on the cases where a double result is a few u off, or a
 measure "in units of u" means nothing: against mpmath every reference is held to REF_TOL = u / 64 in the measure the GPU suite
@@ -192,3 +192,76 @@ def test_lapack_stays_within_the_caps(kind, n):
     assert el <= CAP_LOG
     if kind == "s":
         assert span >= 8.0
+
+
+# ---- the transposed product and its backward error (test_gpu_solve_t_backward.py) ------------------------------------------
+def mp_backward_error_t(L, x, y):
+    """max_i |y - L^T x|_i / (|L^T||x| + |y|)_i in mpmath; x, y doubles or long doubles."""
+    n = L.shape[0]
+    xm, ym = [as_mp(v) for v in x], [as_mp(v) for v in y]
+    worst = mpmath.mpf(0)
+    for i in range(n):
+        col = [mpmath.mpf(float(L[j, i])) * xm[j] for j in range(i, n)]
+        den = mpmath.fsum(abs(v) for v in col) + abs(ym[i])
+        res = abs(ym[i] - mpmath.fsum(col))
+        assert den != 0 or res == 0
+        if den != 0:
+            worst = max(worst, res / den)
+    return float(worst)
+
+
+@pytest.mark.parametrize("case", ["straddle", "decades"])
+def test_transposed_references_against_mpmath(case):
+    L, r, y = small_factor(case)
+    with mpmath.workdps(DPS):
+        # L^T x itself, relative to |L|^T |x| (a sum that may cancel has no relative error in any precision)
+        got, scale = fr.lower_tmv(L, r), fr.lower_tmv(L, r, absolute=True)
+        want = [mpmath.fsum(mpmath.mpf(float(L[j, i])) * mpmath.mpf(float(r[j])) for j in range(i, 40)) for i in range(40)]
+        wabs = [mpmath.fsum(abs(mpmath.mpf(float(L[j, i])) * mpmath.mpf(float(r[j]))) for j in range(i, 40)) for i in range(40)]
+        e = max(float(abs(as_mp(g) - w) / a) for g, w, a in zip(got, want, wabs))
+        print(f"\n[{case}] L^T x: {e / U:.2e} u of |L|^T |x|")
+        assert e <= REF_TOL and rel_ld(scale, wabs) <= REF_TOL
+        # backward_error_t of LAPACK's double solution: the same measure in mpmath
+        for rhs in (r, y):
+            xd = scipy.linalg.solve_triangular(L, rhs, lower=True, trans="T")
+            be, want = fr.backward_error_t(L, xd, rhs), mp_backward_error_t(L, xd, rhs)
+            print(f"[{case}] backward error of solve_triangular(trans='T') {be / U:.3f} u (mpmath {want / U:.3f} u)")
+            assert abs(be - want) <= REF_TOL and 0 < want <= CAP_Z
+        # columns of a matrix are measured one by one
+        X = np.stack([scipy.linalg.solve_triangular(L, v, lower=True, trans="T") for v in (r, y)], axis=1)
+        per_col = fr.backward_error_t(L, X, np.stack([r, y], axis=1))
+        assert per_col.shape == (2,) and per_col[0] == fr.backward_error_t(L, X[:, 0], r) and per_col[1] == fr.backward_error_t(L, X[:, 1], y)
+
+
+def test_transposed_product_across_row_slabs():
+    """Above 512 rows lower_tmv() adds the slabs' contributions up: at n = 600 (slabs of 512 and 88 rows) against mpmath on the
+    columns a slab boundary cuts, at the a-priori bound of a long-double sum of n terms, n 2^-64 of |L|^T |x| (= 0.29 u at
+    n = 600: what a measure "in u" of the GPU suite can be off by at that size; the error measured here is far smaller)."""
+    n = 600
+    L = np.linalg.cholesky(matern52_gram("b", n))
+    x = np.random.default_rng(n).standard_normal(n)
+    got, scale = fr.lower_tmv(L, x), fr.lower_tmv(L, x, absolute=True)
+    with mpmath.workdps(DPS):
+        worst = 0.0
+        for i in (0, 1, 255, 510, 511, 512, 513, 598, 599):
+            want = mpmath.fsum(mpmath.mpf(float(L[j, i])) * mpmath.mpf(float(x[j])) for j in range(i, n))
+            worst = max(worst, float(abs(as_mp(got[i]) - want) / as_mp(scale[i])))
+    print(f"\nL^T x at n = {n}: {worst / U:.2e} u of |L|^T |x|")
+    assert worst <= n * 2.0 ** -64
+    assert np.all(np.triu(L, 1) == 0)
+
+
+def test_backward_error_t_conventions():
+    L = np.array([[2.0, 0.0, 0.0], [1.0, 4.0, 0.0], [0.0, 0.0, 1.0]])
+    x = np.array([1.0, 0.5, 0.0])
+    y = L.T @ x
+    assert fr.backward_error_t(L, x, y) == 0.0                             # the last row: 0 / 0 counts 0
+    y2 = y.copy()
+    y2[0] += 2.5 * 2.0 ** -50                                              # (y_0 = 2.5: |L^T||x| + |y| = 5 + a rounding)
+    assert abs(fr.backward_error_t(L, x, y2) - 2.5 * 2.0 ** -50 / 5.0) <= 1e-28
+    Lz = np.array([[0.0, 0.0], [0.0, 1.0]])                                # column 0 of L is zero: |L^T||x| + |y| = 0 in row 0
+    assert fr.backward_error_t(Lz, np.array([5.0, 0.0]), np.zeros(2)) == 0.0
+    xbad = x.copy()
+    xbad[2] = 1e-300                                                       # a nonzero over a nonzero denominator: a number
+    assert fr.backward_error_t(L, xbad, y) == 1.0
+    assert np.isnan(fr.backward_error_t(L, np.array([1.0, np.nan, 0.0]), y))  # a NaN stays a NaN: no bar is met by it
