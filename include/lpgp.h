@@ -537,6 +537,46 @@ int  lpgp_pcg_start(lpgp_ctx* ctx, lpgp_pcg* p, const lpgp_dvec* R, lpgp_dvec* Z
 /* Q = G P on entry; X += alpha P, R -= alpha Q, Z = M^{-1} R, P = Z + beta P (columns already below rtol are left alone) */
 int  lpgp_pcg_step(lpgp_ctx* ctx, lpgp_pcg* p, lpgp_dvec* X, lpgp_dvec* R, lpgp_dvec* Z, lpgp_dvec* P, const lpgp_dvec* Q, double rtol, double* rel_host);
 
+/* ---- greedy pivoted Cholesky  G ~ L^T L  of a Gram OPERATOR, built and kept on the device (csrc/pivchol.hip) ----------------
+ * The low-rank factor behind the preconditioner above, without the host: the rows of G are evaluated on the fly by the assembly
+ * kernels, L (rank x n, row-major: the layout lpgp_pcg reads) stays in HBM, the host drives the loop and reads 16 bytes per
+ * pivot.  The rules are those of `randprocs/_matrix_free.PivotedCholeskyPreconditioner`:
+ *   pivot   the FIRST index of the largest remaining diagonal entry d; none (-1) once `max_rank` or n rows are committed or the
+ *           largest entry is <= rtol * d0, d0 = max of the diagonal handed to lpgp_pivchol_create
+ *   commit  L[k] = (row_p + noise_pp e_p - L[:k, p] @ L[:k]) / sqrt(d[p]) with the RUNNING d[p] (sum in the order t = 0 .. k-1, fma);
+ *           d = max(d - L[k]^2, 0), d[p] = 0
+ *   finish  delta = max(mean(d), delta_floor * d0);  S = delta I + L L^T, exactly symmetric
+ * One loop:  lpgp_pivchol_pivot -> one lpgp_pivchol_row per block of columns (any order) -> lpgp_pivchol_commit -> ... ->
+ * lpgp_pivchol_finish.  Plain launches on the panel stream, no atomics, every sum in a fixed order: the same bits on every call.
+ * A NaN in the remaining diagonal is an error of lpgp_pivchol_pivot / lpgp_pivchol_finish, not a pivot.
+ * Refused, with the object untouched: a commit with no pivot pending; a row piece that leaves [0, n) or overlaps an earlier piece
+ * of the same row (refused by lpgp_pivchol_row, nothing is launched) and a commit whose pieces leave a gap (a new
+ * lpgp_pivchol_pivot drops the pieces collected so far); l outside X_i; a dimension mismatch; pivot, row or commit after finish;
+ * a second finish; a handle of another context; a context inside a multi-GPU job; max_rank above LPGP_PIVCHOL_MAX_RANK.  Single GPU. */
+#define LPGP_PIVCHOL_MAX_RANK 2048   /* the commit kernel stages the k <= max_rank values L[t, p] in LDS once per workgroup: 16 KiB  */
+typedef struct lpgp_pivchol lpgp_pivchol;
+/* diag_host: the n diagonal entries of G, noise included (borrowed for the call).  Room for min(max_rank, n) rows.      */
+int  lpgp_pivchol_create(lpgp_ctx* ctx, int64_t n, int32_t max_rank, const double* diag_host, double rtol, lpgp_pivchol** out);
+/* two-stage argmax over the remaining diagonal; reads {pivot, d[pivot]} back.  *value is returned either way.           */
+int  lpgp_pivchol_pivot(lpgp_ctx* ctx, lpgp_pivchol* pc, int64_t* pivot, double* value);
+/* row[col_off : col_off + n_j] = [sum_g (kd[g])(X_i[l], X_j)]: the bits lpgp_kernel_matrix returns for that one point (the same
+ * launch on a one-point set gathered on the device).  The noise entry is NOT part of it (lpgp_pivchol_commit).  Launches only. */
+int  lpgp_pivchol_row(lpgp_ctx* ctx, lpgp_pivchol* pc, const lpgp_kdesc* kd, int32_t ngroups, const lpgp_pts* X_i, int64_t l,
+                      const lpgp_pts* X_j, int64_t col_off);
+/* noise_pp: the noise variance of the pivot's own observation (0: none).  Launches only; the rank grows by one.          */
+int  lpgp_pivchol_commit(lpgp_ctx* ctx, lpgp_pivchol* pc, double noise_pp);
+/* closes the object.  S_host: rank x rank (may be NULL at rank 0).                                                       */
+int  lpgp_pivchol_finish(lpgp_ctx* ctx, lpgp_pivchol* pc, double delta_floor, double* delta, double* S_host);
+/* rank so far, d0, the committed pivots in their order (any pointer may be NULL)                                         */
+int  lpgp_pivchol_info(const lpgp_pivchol* pc, int32_t* rank, double* d0, int64_t* pivots_host);
+/* what = 0: L, rank x n, C-order;  1: the remaining diagonal (n);  2: the row buffer (n)                                 */
+int  lpgp_pivchol_to_host(lpgp_ctx* ctx, lpgp_pivchol* pc, int32_t what, double* out_host);
+/* refused while an lpgp_pcg borrows the factor                                                                          */
+int  lpgp_pivchol_destroy(lpgp_pivchol* pc);
+/* lpgp_pcg_create on the factor of a FINISHED factorisation (its n, rank and delta): L is BORROWED, read where it lies -- only
+ * Sinv_host (rank x rank, symmetric) comes up.  lpgp_pcg_destroy frees what the handle owns and gives the factor back.     */
+int  lpgp_pcg_create_pivchol(lpgp_ctx* ctx, lpgp_pivchol* pc, int64_t m, const double* Sinv_host, lpgp_pcg** out);
+
 /* ---- measurement: HIP-event timing of the hot kernels on their own streams ---------- */
 enum lpgp_kernel_id { LPGP_K_ASSEMBLE = 0, LPGP_K_SYRK = 1 /* rank-nb trailing update */, LPGP_K_GEMM = 2,
                       LPGP_K_POTRF_TILE = 3, LPGP_K_TRSM = 4,

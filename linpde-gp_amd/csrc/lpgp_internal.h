@@ -12,6 +12,7 @@
 #include "lpgp_desc.h"
 #include "factor_view.h"
 #include "mat_state.h"
+#include "pivchol_state.h"
 #include "options.h"
 
 namespace lpgp {
@@ -236,6 +237,22 @@ struct lpgp_rhs {
   int64_t m_pad;                   // multiple of TILE, > m: column m is spare (carries the residual through the solve)
   double* v;                       // device ld x m_pad column-major
   std::vector<char> assembled;     // per observation block: rows written by lpgp_cross_assemble (the others are cleared on first use)
+};
+
+// A pivoted Cholesky G ~ L^T L of a Gram OPERATOR, resident (pivchol.hip).  The loop state and the column coverage of the pending row
+// are PivcholState's (pivchol_state.h); the buffers below are written by the kernels of pivchol.hip only.  An lpgp_pcg created by
+// lpgp_pcg_create_pivchol reads L in place (pcg.hip).
+struct lpgp_pivchol : lpgp::PivcholState {
+  lpgp_ctx* ctx = nullptr;
+  double* L = nullptr;             // device max_rank x n, row-major: the layout pcg_lr_kernel / pcg_z_kernel read
+  size_t L_bytes = 0;
+  double* work = nullptr;          // device: d[n] | row[2 n] | one point[LPGP_MAXD * 64] | partials[3 * 256] | slot[4]
+  size_t work_bytes = 0;
+  double* d() const { return work; }
+  double* row() const { return work + n; }       // entry j at row()[2 j]: the leading dimension lpgp_kernel_matrix gives one point
+  double* one() const { return work + 3 * n; }   // a one-point set, padded to 64 as lpgp_pts_create pads it
+  double* part() const { return one() + LPGP_MAXD * 64; }
+  double* slot() const { return part() + 3 * 256; }   // {pivot (int64; -2: a NaN in d), d[pivot], sum of d}
 };
 
 namespace lpgp {

@@ -37,6 +37,8 @@ struct lpgp_pcg {
   double* Sinv = nullptr;     // rank x rank, symmetric: (delta I + L L^T)^{-1}
   double* work = nullptr;     // scalars and partial sums, see offsets below
   size_t L_bytes = 0, work_bytes = 0;
+  lpgp_pivchol* lender = nullptr;   // lpgp_pcg_create_pivchol: L is the lender's (read in place, not freed here); Sinv is an allocation of its own
+  size_t Sinv_bytes = 0;
   int32_t G = 128;            // workgroups of a column dot (first stage)
   // work layout (doubles): part[3][m][G] | rz[m] | pq[m] | alpha[m] | beta[m] | rr[m] | bn[m] | rel[m] | active[m] | T[rank][m] | U[rank][m]
   __host__ __device__ double* part() const { return work; }
@@ -287,9 +289,46 @@ int lpgp_pcg_create(lpgp_ctx* ctx, int64_t n, int64_t m, int32_t rank, const dou
 int lpgp_pcg_destroy(lpgp_pcg* p) {
   if (!p) return 0;
   (void)hipSetDevice(p->ctx->device);
-  pool_free(p->ctx, p->L, p->L_bytes);
+  if (p->lender) {                                 // (frees only what it owns: the factor goes back to its owner)
+    p->lender->give_back();
+    pool_free(p->ctx, p->Sinv, p->Sinv_bytes);
+  } else {
+    pool_free(p->ctx, p->L, p->L_bytes);
+  }
   pool_free(p->ctx, p->work, p->work_bytes);
   delete p;
+  return 0;
+}
+// The same iteration state on the factor of a finished lpgp_pivchol, read where it lies: no copy of L, only Sinv (rank x rank)
+// comes up.  n, rank and delta are the factorisation's.
+int lpgp_pcg_create_pivchol(lpgp_ctx* ctx, lpgp_pivchol* pc, int64_t m, const double* Sinv_host /* rank x rank */, lpgp_pcg** out) {
+  LPGP_CHECK(ctx && pc && out && m >= 1 && m <= 256, "lpgp_pcg_create_pivchol: bad argument");
+  LPGP_DEVICE(ctx);
+  LPGP_CHECK(!ctx->distributed(), "lpgp_pcg_create_pivchol: single GPU only (this context has joined a multi-GPU job)");
+  LPGP_CHECK(pc->ctx == ctx, "lpgp_pcg_create_pivchol: the factorisation belongs to another context");
+  LPGP_CHECK(pc->finished && pc->delta > 0.0, "lpgp_pcg_create_pivchol: the factorisation is not finished with a positive delta (lpgp_pivchol_finish first)");
+  const int32_t rank = pc->rank;
+  LPGP_CHECK(rank == 0 || Sinv_host, "lpgp_pcg_create_pivchol: null Sinv for rank %d", rank);
+  std::unique_ptr<lpgp_pcg> p(new lpgp_pcg());
+  p->ctx = ctx; p->n = pc->n; p->m = m; p->rank = rank; p->delta = pc->delta; p->G = PCG_G;
+  p->Sinv_bytes = ((size_t)rank * rank + 8) * sizeof(double);
+  p->work_bytes = ((size_t)3 * m * PCG_G + (size_t)8 * m + (size_t)2 * rank * m + 8) * sizeof(double);
+  DevBuf Sinv, work;
+  LPGP_TRY(DevBuf::pool(ctx, p->Sinv_bytes, &Sinv));
+  LPGP_TRY(DevBuf::pool(ctx, p->work_bytes, &work));
+  {
+    StreamDrain drain{ctx->s_main};                // (the caller's array is borrowed by the copy)
+    LPGP_HIP(hipMemsetAsync(work.as(), 0, p->work_bytes, ctx->s_main));
+    if (rank > 0) LPGP_HIP(hipMemcpyAsync(Sinv.as(), Sinv_host, (size_t)rank * rank * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
+    LPGP_TRY(drain.wait());
+  }
+  std::string err;
+  LPGP_TRY(refused(pc->borrow(&err), err));
+  p->lender = pc;
+  p->L = pc->L;
+  p->Sinv = (double*)Sinv.release();
+  p->work = (double*)work.release();
+  *out = p.release();
   return 0;
 }
 static int pcg_precond(lpgp_pcg* p, const lpgp_dvec* R, lpgp_dvec* Z) {

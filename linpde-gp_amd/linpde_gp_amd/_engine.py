@@ -748,6 +748,82 @@ def kernel_matvec_dev(ctx: Context, kdesc, X0: Points, X1: Points, V: DeviceVect
           "lpgp_kernel_matvec_dev")
 
 
+class DevicePivotedCholesky:
+    """Greedy pivoted Cholesky `G ~ L^T L` of a Gram operator, built and kept on the device (`lpgp_pivchol_*`, csrc/pivchol.hip).
+    The caller drives the loop: `pivot()` -> one `row(...)` per block of columns -> `commit(noise)` -> ... -> `finish(floor)`."""
+
+    def __init__(self, ctx: Context, n: int, max_rank: int, diag: np.ndarray, rtol: float):
+        self.ctx, self.n = ctx, int(n)
+        d = np.ascontiguousarray(diag, dtype=np.double).reshape(-1)
+        if d.size != self.n:
+            raise ValueError(f"the diagonal has {d.size} entries, the operator {self.n} rows")
+        h = C.c_void_p()
+        check(lib.lpgp_pivchol_create(ctx._h, self.n, int(max_rank), as_pd(d), float(rtol), C.byref(h)), "lpgp_pivchol_create")
+        self._h = h
+        self.delta = None
+
+    def close(self) -> bool:
+        """Free the device buffers.  Refused (False, the handle kept) while a `DevicePCG` borrows the factor."""
+        if getattr(self, "_h", None) and self.ctx._h:
+            if lib.lpgp_pivchol_destroy(self._h) != 0:
+                return False
+            self._h = None
+        return True
+
+    def __del__(self):  # pragma: no cover
+        # finalised before a borrower (cycle collection, interpreter shutdown): the handle stays, and the last borrower's
+        # finaliser closes it (`DevicePCG.__del__`)
+        self._orphaned = True
+        self.close()
+
+    def pivot(self) -> "tuple[int, float]":
+        """(pivot, remaining diagonal there); pivot -1: a stop rule holds"""
+        p, v = C.c_int64(), C.c_double()
+        check(lib.lpgp_pivchol_pivot(self.ctx._h, self._h, C.byref(p), C.byref(v)), "lpgp_pivchol_pivot")
+        return p.value, v.value
+
+    def row(self, kdesc, X_i: Points, l: int, X_j: Points, col_off: int) -> None:
+        arr = _kdesc_array(kdesc)
+        check(lib.lpgp_pivchol_row(self.ctx._h, self._h, arr, len(arr), X_i._h, int(l), X_j._h, int(col_off)), "lpgp_pivchol_row")
+
+    def commit(self, noise_pp: float = 0.0) -> None:
+        check(lib.lpgp_pivchol_commit(self.ctx._h, self._h, float(noise_pp)), "lpgp_pivchol_commit")
+
+    def finish(self, delta_floor: float) -> "tuple[float, np.ndarray]":
+        """(delta, S = delta I + L L^T as a rank x rank host array); closes the object"""
+        r = self.rank
+        S = np.empty((r, r))
+        delta = C.c_double()
+        check(lib.lpgp_pivchol_finish(self.ctx._h, self._h, float(delta_floor), C.byref(delta), as_pd(S) if r else None), "lpgp_pivchol_finish")
+        self.delta = delta.value
+        return delta.value, S
+
+    @property
+    def rank(self) -> int:
+        r = C.c_int32()
+        check(lib.lpgp_pivchol_info(self._h, C.byref(r), None, None), "lpgp_pivchol_info")
+        return r.value
+
+    @property
+    def d0(self) -> float:
+        v = C.c_double()
+        check(lib.lpgp_pivchol_info(self._h, None, C.byref(v), None), "lpgp_pivchol_info")
+        return v.value
+
+    @property
+    def pivots(self) -> np.ndarray:
+        out = np.empty(self.rank, dtype=np.int64)
+        check(lib.lpgp_pivchol_info(self._h, None, None, out.ctypes.data_as(C.POINTER(C.c_int64))), "lpgp_pivchol_info")
+        return out
+
+    def to_host(self, what: str = "L") -> np.ndarray:
+        """"L": the factor (rank x n); "d": the remaining diagonal; "row": the row buffer"""
+        code = {"L": 0, "d": 1, "row": 2}[what]
+        out = np.empty((self.rank, self.n)) if code == 0 else np.empty(self.n)
+        check(lib.lpgp_pivchol_to_host(self.ctx._h, self._h, code, as_pd(out)), "lpgp_pivchol_to_host")
+        return out
+
+
 class DevicePCG:
     """Preconditioned conjugate gradients whose iteration is launches only (`lpgp_pcg_*`): `matvec(P, Q)` forms Q = G P on
     `DeviceVectors`; everything else -- dots, step lengths, the low-rank preconditioner -- stays on the device."""
@@ -762,10 +838,26 @@ class DevicePCG:
               "lpgp_pcg_create")
         self._h = h
 
+    @classmethod
+    def from_resident(cls, pc: "DevicePivotedCholesky", m: int, Sinv: np.ndarray | None) -> "DevicePCG":
+        """The same iteration on the factor of a finished `DevicePivotedCholesky`, read where it lies (`lpgp_pcg_create_pivchol`):
+        only `Sinv` (rank x rank) is uploaded.  The handle keeps `pc` alive for as long as it borrows its factor."""
+        self = cls.__new__(cls)
+        self.ctx, self.n, self.m = pc.ctx, pc.n, int(m)
+        self._pc = pc
+        Sc = None if pc.rank == 0 else np.ascontiguousarray(Sinv, dtype=np.double).reshape(pc.rank, pc.rank)
+        h = C.c_void_p()
+        check(lib.lpgp_pcg_create_pivchol(pc.ctx._h, pc._h, self.m, as_pd(Sc) if pc.rank else None, C.byref(h)), "lpgp_pcg_create_pivchol")
+        self._h = h
+        return self
+
     def __del__(self):  # pragma: no cover
         if getattr(self, "_h", None) and self.ctx._h:
             lib.lpgp_pcg_destroy(self._h)
             self._h = None
+        pc = getattr(self, "_pc", None)
+        if pc is not None and getattr(pc, "_orphaned", False):
+            pc.close()                             # the lender was finalised first and could not free its factor then
 
     def start(self, R, Z, P, bnorm: np.ndarray, rtol: float) -> np.ndarray:
         rel = np.empty(self.m)

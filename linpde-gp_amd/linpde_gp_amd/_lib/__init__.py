@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("LPGP_LIB", os.path.join(_HERE, "liblpgp.so"))     # $
 
 MAXD, MAXT, MAXG = 4, 256, 16
 MAXW = 4            # LPGP_MAXW: coefficient functions per variable-coefficient operator
+PIVCHOL_MAX_RANK = 2048   # LPGP_PIVCHOL_MAX_RANK: rows of a pivoted Cholesky built on the device (`lpgp_pivchol_create`)
 MATERN_HALFINT, EXPQUAD, MATERN_ISO, MATERN_RADIAL = 1, 2, 3, 4
 WENDLAND, WENDLAND_ISO = 5, 6     # compactly supported Wendland functions: univariate product-form factor / isotropic over all d
 K_ASSEMBLE, K_SYRK, K_GEMM, K_POTRF_TILE, K_TRSM, K_COUNT = 0, 1, 2, 3, 4, 5
@@ -144,6 +145,15 @@ def _load() -> C.CDLL:
     sig("lpgp_pcg_destroy", C.c_int, vp)
     sig("lpgp_pcg_start", C.c_int, vp, vp, vp, vp, vp, pd, dbl, pd)
     sig("lpgp_pcg_step", C.c_int, vp, vp, vp, vp, vp, vp, vp, dbl, pd)
+    sig("lpgp_pivchol_create", C.c_int, vp, i64, i32, pd, dbl, C.POINTER(vp))
+    sig("lpgp_pivchol_pivot", C.c_int, vp, vp, C.POINTER(i64), pd)
+    sig("lpgp_pivchol_row", C.c_int, vp, vp, pk, i32, vp, i64, vp, i64)
+    sig("lpgp_pivchol_commit", C.c_int, vp, vp, dbl)
+    sig("lpgp_pivchol_finish", C.c_int, vp, vp, dbl, pd, pd)
+    sig("lpgp_pivchol_info", C.c_int, vp, C.POINTER(i32), pd, C.POINTER(i64))
+    sig("lpgp_pivchol_to_host", C.c_int, vp, vp, i32, pd)
+    sig("lpgp_pivchol_destroy", C.c_int, vp)
+    sig("lpgp_pcg_create_pivchol", C.c_int, vp, vp, i64, pd, C.POINTER(vp))
     sig("lpgp_mat_sub_inner", C.c_int, vp, vp, i32, vp)
     sig("lpgp_mat_factor_matmul", C.c_int, vp, vp, pd, i64, pd, pd)
     sig("lpgp_mat_evidence", C.c_int, vp, vp, pd, pd)
@@ -181,6 +191,8 @@ EXPORTED = [
     "lpgp_mat_evidence", "lpgp_mat_inverse_diag", "lpgp_mat_loo", "lpgp_mat_inverse", "lpgp_mat_evidence_grad", "lpgp_mat_evidence_grad_diag", "lpgp_mat_cv",
     "lpgp_dvec_create", "lpgp_dvec_destroy", "lpgp_dvec_set", "lpgp_dvec_get", "lpgp_dvec_axpby", "lpgp_dvec_scale_rows_add", "lpgp_kernel_matvec_dev",
     "lpgp_pcg_create", "lpgp_pcg_destroy", "lpgp_pcg_start", "lpgp_pcg_step",
+    "lpgp_pivchol_create", "lpgp_pivchol_pivot", "lpgp_pivchol_row", "lpgp_pivchol_commit", "lpgp_pivchol_finish", "lpgp_pivchol_info",
+    "lpgp_pivchol_to_host", "lpgp_pivchol_destroy", "lpgp_pcg_create_pivchol",
     "lpgp_rhs_to_host", "lpgp_kernel_diag", "lpgp_kernel_matrix", "lpgp_kernel_matvec", "lpgp_gram_assemble_grid", "lpgp_kron_fits", "lpgp_profile_enable", "lpgp_profile_reset",
     "lpgp_profile_get",
     ]

@@ -55,6 +55,12 @@ matrix_free_maxiter: int = 5000
 matrix_free_rhs_chunk: int = 64                  # prediction points per block of variance solves
 matrix_free_device_iteration: bool = True        # iterates / residuals / search directions resident in HBM, one iteration = launches only
                                                  # (`lpgp_pcg_step`, round 6); False: the host loop of round 5 (NumPy vector algebra around `lpgp_kernel_matvec`)
+# The pivoted-Cholesky preconditioner built ON THE DEVICE (`lpgp_pivchol_*`, csrc/pivchol.hip) where every noise term is a diagonal:
+# the rows never visit the host, the factor stays in HBM and every device solve reads it in place (`lpgp_pcg_create_pivchol`) instead
+# of uploading it again.  Ranks up to 2 048 (`LPGP_PIVCHOL_MAX_RANK`); min(rank, n) beyond that is built by the host loop.  Same pivot rule, same stop rules, same delta as the host build; the rows differ in rounding only.  Off by
+# default: tests/test_gpu_mfree_solve.py pins the host-built object the solves are handed (MEASUREMENTS.md, "Pivoted Cholesky on the
+# device").  `gram.pivoted_cholesky()` builds on the device whatever this says.
+matrix_free_device_preconditioner: bool = False
 
 # Lazy mode: a block that was only assembled stays unfactored across FURTHER conditionings -- to be factored together with them,
 # the prediction riding inside -- only if it has at least this many rows; smaller ones are factored when the next conditioning

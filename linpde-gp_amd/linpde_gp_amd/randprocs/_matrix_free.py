@@ -5,7 +5,7 @@ This is the slot the reference fills with KeOps lazy tensors (`_keops_lazy_tenso
 `covfuncs/linfuncops/diffops/_matern.py:112-135,231-264`; probnum's `LinearOperator.solve` then iterates on the lazy product):
 observation sets beyond the dense memory of one device -- 190 000 points are a 289-GB Gram matrix -- and the CPU-die
 experiment's 2-D model (`experiments/0001_cpu_stationary_2d.ipynb`).  Same surface as `ConditionalGaussianProcess`:
-`mean`, `var`, `std`, `predict`, `cov.matrix`, `representer_weights`, `gram` (`@`, `solve`), re-entrant
+`mean`, `var`, `std`, `predict`, `cov.matrix`, `representer_weights`, `gram` (`@`, `solve`, `pivoted_cholesky`), re-entrant
 `condition_on_observations` (the previous weights warm-start the next solve).
 
 What runs where: every kernel entry -- Gram products, cross-covariance products, the rows the preconditioner is built from --
@@ -19,14 +19,15 @@ object anywhere.
 
 Preconditioner: rank-r pivoted Cholesky `G ~ L^T L` (r rows of G, greedy on the remaining diagonal) plus `delta I`, applied by
 the Woodbury identity -- the standard choice for kernel matrices with a noise floor; `delta` is the mean of the diagonal the
-low-rank part leaves unexplained.
+low-rank part leaves unexplained.  With `config.matrix_free_device_preconditioner` it is built on the device (`lpgp_pivchol_*`,
+csrc/pivchol.hip) and every device solve reads the resident factor in place.
 """
 
 from __future__ import annotations
 
 import numpy as np
 
-from .. import _engine, config, functions, randvars
+from .. import _engine, _lib, config, functions, randvars
 from . import covfuncs
 
 
@@ -137,13 +138,29 @@ class PivotedCholeskyPreconditioner:
     `(R - L^T S^-1 L R) / delta` cancels log10(lambda_max(L^T L) / delta) digits, so at delta = 1e-12 d0 the operator applied was
     not M^-1 any more (||M M^-1 R - R|| / ||R|| of 1e-2 to 3e-1) and the device form did not converge.  With 1e-8 d0 = sqrt(u) d0
     the applied operator is M^-1 to 1e-5 and full-rank solves take the two or three iterations of the exact M^-1 (MEASUREMENTS.md,
-    "Matrix-free solves against a dense reference": 1e-10 d0 still trails it, 1e-6 d0 and above cost iterations at noise 1e-6)."""
+    "Matrix-free solves against a dense reference": 1e-10 d0 still trails it, 1e-6 d0 and above cost iterations at noise 1e-6).
 
-    def __init__(self, G: GramProduct, rank: int, rtol: float = 1e-6):
+    The loop below is the statement of the algorithm.  With `device` (default: `config.matrix_free_device_preconditioner`, and only
+    where every noise term of G is a diagonal) the same loop runs on the device (`lpgp_pivchol_*`, csrc/pivchol.hip): the host asks
+    for the pivot, names the block pairs of its row and the noise entry, and reads 16 bytes per pivot; L stays in HBM, where
+    `pcg_device` reads it in place, and comes down only when `.L` is asked for."""
+
+    def __init__(self, G: GramProduct, rank: int, rtol: float = 1e-6, device: "bool | None" = None):
+        self._device = None
+        self._L = None
+        if device is None:
+            device = bool(config.matrix_free_device_preconditioner)
+        device_ok = getattr(G, "device_ok", None)
+        # (the device build holds at most `_lib.PIVCHOL_MAX_RANK` rows -- its commit kernel stages a column of L in LDS; a larger
+        #  request is the host loop's, as is a Gram operator with a dense noise block)
+        if device and device_ok is not None and device_ok() and min(int(rank), G.n) <= _lib.PIVCHOL_MAX_RANK:
+            self._build_on_device(G, rank, rtol)
+            return
         n = G.n
         d = G.diag().copy()
         d0 = float(np.max(d))
         L = np.zeros((min(rank, n), n))
+        pivots = []
         k = 0
         while k < L.shape[0]:
             p = int(np.argmax(d))
@@ -155,15 +172,46 @@ class PivotedCholeskyPreconditioner:
             L[k] = r / np.sqrt(d[p])
             d = np.maximum(d - L[k] * L[k], 0.0)
             d[p] = 0.0
+            pivots.append(p)
             k += 1
-        self.L = L[:k]
+        self._L = L[:k]
         self.rank = k
+        self.pivots = np.array(pivots, dtype=np.int64)
         self.delta = max(float(np.mean(d)), DELTA_FLOOR * d0)
         if self.rank:
             S = self.delta * np.eye(self.rank) + self.L @ self.L.T
             self._chol = np.linalg.cholesky(S)
         else:
             self._chol = None
+
+    def _build_on_device(self, G: GramProduct, rank: int, rtol: float):
+        pc = _engine.DevicePivotedCholesky(G.ctx, G.n, min(int(rank), G.n), G.diag(), rtol)
+        lowered = {}                              # a block pair's descriptor, asked for once per pair
+        while True:
+            p, _ = pc.pivot()
+            if p < 0:
+                break
+            i = int(np.searchsorted(G.offs, p, side="right") - 1)
+            l = p - int(G.offs[i])
+            for j, bj in enumerate(G.blocks):
+                if G.sizes[j]:
+                    if (i, j) not in lowered:
+                        lowered[i, j] = G.desc(i, j)
+                    pc.row(lowered[i, j], G.blocks[i].points, l, bj.points, int(G.offs[j]))
+            nz = G._noise[i]
+            pc.commit(0.0 if nz is None else float(nz[l]))
+        self.delta, S = pc.finish(DELTA_FLOOR)
+        self.rank = pc.rank
+        self.pivots = pc.pivots
+        self._chol = np.linalg.cholesky(S) if self.rank else None
+        self._device = pc
+
+    @property
+    def L(self):
+        """The factor as a host array (rank x n); after a device build it is downloaded at first use."""
+        if self._L is None:
+            self._L = self._device.to_host("L")
+        return self._L
 
     def solve(self, R):
         if self._chol is None:
@@ -222,7 +270,12 @@ def pcg_device(G: "GramProduct", B, precond=None, X0=None, rtol: float = 1e-10, 
         R.axpby(R, Q, -1.0)                       # R = B - G X0
     bn = np.linalg.norm(B2, axis=0)
     bn[bn == 0.0] = 1.0
-    if precond is not None and precond.rank:
+    resident = getattr(precond, "_device", None)
+    if resident is not None:
+        # the factor was built on the device and is read where it lies: only the small inverse goes up
+        Sinv = np.linalg.inv(precond._chol @ precond._chol.T) if precond.rank else None
+        it_ = _engine.DevicePCG.from_resident(resident, m, None if Sinv is None else 0.5 * (Sinv + Sinv.T))
+    elif precond is not None and precond.rank:
         Sinv = np.linalg.inv(precond._chol @ precond._chol.T)
         it_ = _engine.DevicePCG(ctx, n, m, precond.L, 0.5 * (Sinv + Sinv.T), precond.delta)
     else:
@@ -262,6 +315,17 @@ class _MatrixFreeGram:
     def solve(self, B):
         X, info = self._gp._solve(B)
         return X
+
+    def pivoted_cholesky(self, rank=None, rtol: float = 1e-6):
+        """The greedy low-rank factor `G ~ L^T L` of the operator: a `PivotedCholeskyPreconditioner` (`.L` rank x n, `.pivots` in
+        their order, `.rank`, `.delta`).  `rank=None`: `config.matrix_free_preconditioner_rank`.  Built on the device
+        (`lpgp_pivchol_*`) where every noise term is a diagonal and min(rank, n) is at most 2 048 (`LPGP_PIVCHOL_MAX_RANK`), whatever
+        `config.matrix_free_device_preconditioner` says; the host loop otherwise."""
+        G = self._gp._G
+        rank = int(config.matrix_free_preconditioner_rank) if rank is None else int(rank)
+        if rank < 0:
+            raise ValueError(f"rank must not be negative, got {rank}")
+        return PivotedCholeskyPreconditioner(G, rank, rtol, device=G.device_ok())
 
     def todense(self):
         raise NotImplementedError("a matrix-free Gram operator has no dense form (that is its point); use `@` and `solve`")
