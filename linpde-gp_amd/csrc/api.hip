@@ -1076,7 +1076,8 @@ int lpgp_mat_factor_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host) {
 }
 
 // ---- factor + solve -----------------------------------------------------------------------
-int lpgp_potrf(lpgp_ctx* ctx, lpgp_mat* mat, int32_t* info) {
+// lpgp_potrf, in the form `form` (TileForm::newton: lpgp_mat_cv's large folds, single GPU; such a factorisation runs without the resident chain)
+extern "C++" int lpgp::potrf_mat(lpgp_ctx* ctx, lpgp_mat* mat, int32_t* info, TileForm form) {
   LPGP_CHECK(ctx && mat, "lpgp_potrf: null argument");
   LPGP_DEVICE(ctx);
   LPGP_MAT_ALIVE(mat, "lpgp_potrf");
@@ -1085,9 +1086,10 @@ int lpgp_potrf(lpgp_ctx* ctx, lpgp_mat* mat, int32_t* info) {
   LPGP_CHECK(mat->hidden.empty(), "lpgp_potrf: a strict prefix of the blocks is in view");
   int32_t h = 0;
   LPGP_CHECK(!ctx->dist_broken, "lpgp_potrf: the communicator was aborted after an earlier failure");
+  LPGP_CHECK(form == TileForm::plain || !ctx->distributed(), "lpgp_potrf: the multi-GPU factorisation has the plain tile form only");
   int rc = ctx->distributed()
                ? dist_fail(ctx, potrf_dist(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, &h))
-               : potrf_blocked(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, &h);
+               : potrf_blocked(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, &h, form);
   if (rc != 0) {
     mat->poison();                   // (the matrix is partly overwritten in place, pn_fact unchanged: not a state to factor again from)
     return rc;
@@ -1096,6 +1098,8 @@ int lpgp_potrf(lpgp_ctx* ctx, lpgp_mat* mat, int32_t* info) {
   mat->factored(h);
   return 0;
 }
+
+int lpgp_potrf(lpgp_ctx* ctx, lpgp_mat* mat, int32_t* info) { return potrf_mat(ctx, mat, info, TileForm::plain); }
 
 int lpgp_potrf_enqueue(lpgp_ctx* ctx, lpgp_mat* mat) {
   LPGP_CHECK(ctx && mat, "lpgp_potrf_enqueue: null argument");
@@ -1313,7 +1317,7 @@ int lpgp_solve_weights(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, doubl
   // (round 6; until then two blocking copies through pageable memory around 2 x T dependent launches)
   LPGP_TRY(ensure_stage(ctx, pn));
   double* const hs = ctx->h_stage;
-  int* const hinfo = ctx->h_info_pinned + 6;
+  int* const hinfo = ctx->h_info_pinned + lpgp_ctx::PIN_SOLVE_WEIGHTS;
   mat->scatter_padded(r_host, hs);
   LPGP_HIP(hipMemcpyAsync(mat->w, hs, (size_t)pn * sizeof(double), hipMemcpyHostToDevice, ctx->s_main));
   if (ctx->distributed()) {
@@ -1621,7 +1625,6 @@ int lpgp_potrf_predict(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_rhs* K, const double* 
   double* zcol = K->v + (int64_t)K->m * K->ld;          // the residual rides as the spare column: z = L^{-1} r, mean = V^T z
   LPGP_HIP(hipMemcpyAsync(zcol, mat->r(), (size_t)mat->pn * sizeof(double), hipMemcpyDeviceToDevice, ctx->s_main));
   const bool fresh = mat->pn_fact < mat->pn;
-  ctx->d_info_cur = mat->d_status;
   const int rc = potrf_predict_blocked(ctx, mat, mat->pn_fact / TILE, mat->pn / TILE, K->v, K->ld, K->m_pad);
   if (rc != 0) {
     if (fresh) mat->poison();        // (partly factored in place with pn_fact unchanged -- a retry would factor a half-factored matrix)
@@ -1632,7 +1635,7 @@ int lpgp_potrf_predict(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_rhs* K, const double* 
   // mean, variance and the status word of the factorisation come back together: two asynchronous copies into pinned memory,
   // ONE wait (until round 5: two blocking copies into pageable memory here and a third in lpgp_mat_check, ~25 us each --
   // a tenth of a step of the reference's own problem sizes)
-  int* const hinfo = ctx->h_info_pinned + 4;
+  int* const hinfo = ctx->h_info_pinned + lpgp_ctx::PIN_POTRF_PREDICT;
   LPGP_TRY(reduce_read_back(ctx, mat, K, zcol, true, prior_mean_host, kxx_host, mean_host, var_host, hinfo));
   mat->status_read_back(*hinfo);
   return 0;

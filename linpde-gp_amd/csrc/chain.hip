@@ -396,7 +396,8 @@ __global__ __launch_bounds__(256, 2) void panel_chain_rows_kernel(ChainArgs g) {
 // rows_here = false: the factor workgroup and the twelve in-block row workgroups only; the rows below follow through the flags
 // in a launch of their own (launch_panel_chain_rows).
 // ahead = true: the look-ahead update by the previous panel (columns [p0 - 4, p0), all rows from p0 on) is part of the launch.
-int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info, bool rows_here, bool ahead) {
+// *ticket: this launch, for the launches that follow it through its flags.
+int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info, ChainTicket* ticket, bool rows_here, bool ahead) {
   LPGP_CHECK(!ahead || (p0 >= 4 && rows_here), "resident chain: the fused look-ahead needs a previous panel of four tiles and the rows in the same launch");
   if (!ctx->d_chain_flags) {
     LPGP_HIP(hipMalloc(&ctx->d_chain_flags, (size_t)CH_SLOTS * CH_SLOT_INTS * sizeof(int)));
@@ -408,8 +409,7 @@ int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, 
   g.linv = F.inv(p0);
   const int64_t n = ctx->chain_launches++;
   g.slot = ctx->d_chain_flags + (n % CH_SLOTS) * CH_SLOT_INTS;
-  ctx->chain_last_slot = g.slot;
-  ctx->chain_last_p0 = p0;
+  *ticket = ChainTicket{g.slot, p0, n};
   g.slot_clear = ctx->d_chain_flags + ((n + CH_SLOTS / 2) % CH_SLOTS) * CH_SLOT_INTS;
   g.info = d_info;
   g.info_base = p0 * TILE;
@@ -428,20 +428,19 @@ int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, 
   return 0;
 }
 
-// rows below the diagonal block of panel p0 (down to tile T), following the chain launched LAST (launch_panel_chain(..., rows_here = false))
-int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info) {
-  LPGP_CHECK(ctx->chain_last_slot && ctx->chain_last_p0 == p0, "resident chain: no chain launch of panel %d to follow", p0);
+// the arguments of a launch that follows the launch `chain` of panel p0's chain through its flags: it reads them and clears none
+static int follower_args(FactorView F, const ChainTicket& chain, int p0, int* d_info, ChainArgs* g) {
+  LPGP_CHECK(chain.slot && chain.p0 == p0, "resident chain: the ticket is for panel %d, not for panel %d", chain.p0, p0);
+  *g = ChainArgs{F.diag(p0), F.ld, F.inv(p0), chain.slot, nullptr, d_info, p0 * TILE, 0};
+  return 0;
+}
+
+// rows below the diagonal block of panel p0 (down to tile T), following the launch `chain` (launch_panel_chain(..., rows_here = false))
+int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, FactorView F, const ChainTicket& chain, int p0, int T, int* d_info) {
+  ChainArgs g;
+  LPGP_TRY(follower_args(F, chain, p0, d_info, &g));
   const int below = T - p0 - 4;
   if (below <= 0) return 0;
-  ChainArgs g;
-  g.a = F.diag(p0);
-  g.ld = F.ld;
-  g.linv = F.inv(p0);
-  g.slot = ctx->chain_last_slot;
-  g.slot_clear = nullptr;
-  g.info = d_info;
-  g.info_base = p0 * TILE;
-  g.n_below = 0;
   const size_t shmem = (size_t)(32 * 64 + TSV_RING) * sizeof(double);          // one row group's fragment image + the stage ring: 69 632 B
   LPGP_TRY_RC(ensure_lds_attr(ctx, reinterpret_cast<const void*>(&panel_chain_rows_kernel), shmem));
   prof_begin(ctx, stream, LPGP_K_PANEL, (double)below * TILE * 512.0 * 512.0, 0.0);
@@ -451,19 +450,11 @@ int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int
   return 0;
 }
 
-// V: first row of the panel's rows of the right-hand side (rows p0 * 128 ...), `cols` columns (a multiple of 128); the chain of
-// panel p0 must be the LAST one launched (launch_panel_chain), its flag slot is the one this launch follows.
-int launch_panel_chain_v(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, double* V, int64_t ldv, int64_t cols, int* d_info) {
-  LPGP_CHECK(ctx->chain_last_slot && ctx->chain_last_p0 == p0, "resident chain: no chain launch of panel %d to follow", p0);
+// V: first row of the panel's rows of the right-hand side (rows p0 * 128 ...), `cols` columns (a multiple of 128); `chain`: the
+// launch of panel p0's chain (launch_panel_chain), whose flag slot this launch follows.
+int launch_panel_chain_v(lpgp_ctx* ctx, hipStream_t stream, FactorView F, const ChainTicket& chain, int p0, double* V, int64_t ldv, int64_t cols, int* d_info) {
   ChainArgs g;
-  g.a = F.diag(p0);
-  g.ld = F.ld;
-  g.linv = F.inv(p0);
-  g.slot = ctx->chain_last_slot;
-  g.slot_clear = nullptr;
-  g.info = d_info;
-  g.info_base = p0 * TILE;
-  g.n_below = 0;
+  LPGP_TRY(follower_args(F, chain, p0, d_info, &g));
   const size_t shmem = (size_t)(2 * 32 * 64 + TSV_RING) * sizeof(double);          // the row role's fragment image + stage ring
   LPGP_TRY_RC(ensure_lds_attr(ctx, reinterpret_cast<const void*>(&panel_chain_v_kernel), shmem));
   prof_begin(ctx, stream, LPGP_K_PANEL, (double)cols * 512.0 * 512.0, 0.0);

@@ -279,7 +279,7 @@ static int allreduce_max_int(lpgp_ctx* ctx, hipStream_t st, int* h_value) {
   // through PINNED host memory: a copy to or from pageable memory is synchronous -- it would wait, unwatched, behind a
   // collective whose peer is gone; like this only sync_stream waits, and it watches RCCL's error state
   int* d = ctx->d_info;
-  int* hp = ctx->h_info_pinned;
+  int* hp = ctx->h_info_pinned + lpgp_ctx::PIN_ALLREDUCE;
   *hp = *h_value;
   LPGP_HIP(hipMemcpyAsync(d, hp, sizeof(int), hipMemcpyHostToDevice, st));
   DTRACE(ctx, "all-reduce: enqueue");
@@ -665,7 +665,7 @@ static int factor_diag_block(lpgp_ctx* ctx, hipStream_t st, lpgp_mat* mat, const
     for (int j = 0; j < kw; ++j) {
       double* dj = D + (int64_t)j * TILE * (ld + 1);
       double* linv = mat->linv + (int64_t)(c0 + j) * TILE * TILE;
-      LPGP_TRY(launch_potrf_tile(ctx, st, dj, ld, linv, ctx->d_info, (c0 + j) * TILE));
+      LPGP_TRY(launch_potrf_tile(ctx, st, dj, ld, linv, ctx->d_info, (c0 + j) * TILE, TileForm::plain));
       if (j + 1 < kw) {
         double* X = dj + TILE;
         LPGP_TRY(launch_trsm_tile(ctx, st, X, ld, linv, dj, ld, kw - j - 1, LPGP_K_TRSM));
@@ -838,14 +838,14 @@ int potrf_dist(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, int64_t T64, int3
     LPGP_TRY(panel_part(q, which ^ 1, head_end_of(i + 1)));
   }
   if (have_upd && last_upd) LPGP_HIP(hipStreamWaitEvent(sP, last_upd, 0));      // join: every update is behind the panel stream
-  LPGP_HIP(hipMemcpyAsync(ctx->h_info_pinned + 1, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, sP));
+  LPGP_HIP(hipMemcpyAsync(ctx->h_info_pinned + lpgp_ctx::PIN_POTRF_DIST, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, sP));
   LPGP_TRY(sync_stream(ctx, sP));
   // A failed pivot is seen by the owner of its diagonal block only -- and the blocks behind it, whose owners are other ranks, fail in
   // their turn once its garbage reaches them: the job's status is the FIRST bad pivot, the smallest positive status of any rank.
   // Agreed on as a maximum of INT_MAX - status.  The kernels launched here write 0 or a pivot's position (potrf_tile.h), never the
   // negative status of a broken hand-over that the single-GPU chain knows; should a rank report one all the same, it outranks every
   // pivot and comes back as -1: its value is not carried through the reduction.
-  const int h_local = ctx->h_info_pinned[1];
+  const int h_local = ctx->h_info_pinned[lpgp_ctx::PIN_POTRF_DIST];
   int key = h_local > 0 ? INT_MAX - h_local : (h_local < 0 ? INT_MAX : 0);
   LPGP_TRY(allreduce_max_int(ctx, sP, &key));
   if (info) *info = key == INT_MAX ? -1 : (key > 0 ? INT_MAX - key : 0);

@@ -162,26 +162,6 @@ struct LPGP_LOCAL MatGuard {                     // a scratch matrix of the larg
   ~MatGuard() { if (m) (void)lpgp_mat_destroy(m); }
 };
 
-// The factorisation of a large fold's S with the Newton sign in the tile Cholesky (lpgp_ctx::tile_newton_inv): mean, variances and
-// covariance of the fold are read off S^{-1}, where a backward error of the factor is multiplied by cond(S) -- with the factorisation's
-// own sign the 150-row fold of tests/test_gpu_cv.py (cond_2(S) = 5e3) was 17 x LAPACK's distance from the truth.  The resident panel
-// chain carries the factorisation's sign, so it is kept off for this one factorisation: per-tile launches, the schedule of
-// LPGP_CHAIN_RESIDENT=-1.  Restored on every way out.
-struct LPGP_LOCAL LargeFoldFactor {
-  lpgp_ctx* ctx;
-  int chain_rows;
-  explicit LargeFoldFactor(lpgp_ctx* c) : ctx(c), chain_rows(c->chain_resident_max_rows) {
-    ctx->tile_newton_inv = 1;
-    ctx->chain_resident_max_rows = -1;
-  }
-  LargeFoldFactor(const LargeFoldFactor&) = delete;
-  LargeFoldFactor& operator=(const LargeFoldFactor&) = delete;
-  ~LargeFoldFactor() {
-    ctx->tile_newton_inv = 0;
-    ctx->chain_resident_max_rows = chain_rows;
-  }
-};
-
 // what the call keeps on the device: [w (r on entry) | y | lrow] as staged, the scratch of the solve, [mean | var] per member and
 // [logp | total]; the table as int32: [prow | start | tile ids | status per tile fold | status of the solve of w]
 struct CvDevice {
@@ -208,11 +188,12 @@ int cv_large_fold(lpgp_ctx* ctx, const lpgp_mat* ginv, const FoldTable& tab, int
   hipLaunchKernelGGL(cv_gather_large_kernel, dim3((unsigned)((b + CV_THREADS - 1) / CV_THREADS), gy, gz), dim3(CV_THREADS), 0, st, (const double*)ginv->a,
                      ginv->lr_cap, (const int32_t*)(D.prow + s), (int)b, S.m->a, S.m->lr_cap);
   LPGP_HIP(hipGetLastError());
+  // S is factored with the Newton sign in the tile Cholesky (TileForm::newton): mean, variances and covariance of the fold are read off
+  // S^{-1}, where a backward error of the factor is multiplied by cond(S) -- with the factorisation's own sign the 150-row fold of
+  // tests/test_gpu_cv.py (cond_2(S) = 5e3) was 17 x LAPACK's distance from the truth.  The resident panel chain carries the
+  // factorisation's sign, so a factorisation of this form runs without it: per-tile launches, the schedule of LPGP_CHAIN_RESIDENT=-1.
   int32_t info = 0;
-  {
-    LargeFoldFactor scope(ctx);
-    LPGP_TRY(lpgp_potrf(ctx, S.m, &info));
-  }
+  LPGP_TRY(potrf_mat(ctx, S.m, &info, TileForm::newton));
   LPGP_CHECK(info == 0, "lpgp_mat_cv: fold %d: pivot %d of G^-1[B, B] is not positive", f, info);
   std::vector<double> wB((size_t)spn, 0.0);      // (single block: the padded layout is the logical one with a zero tail)
   for (int64_t i = 0; i < b; ++i) wB[(size_t)i] = w_pad[tab.prow[(size_t)(s + i)]];

@@ -96,9 +96,7 @@ struct lpgp_ctx : lpgp::Options {     // tuning options: options.h
   hipEvent_t ev_append[2] = {nullptr, nullptr};
   hipEvent_t ev_chain_rows = nullptr;
   int* d_chain_flags = nullptr;        // ring of flag slots (zeroed; a launch zeroes the slot half a ring ahead)
-  int64_t chain_launches = 0;
-  int* chain_last_slot = nullptr;      // flag slot and panel of the last chain launch: the substitution's panel step that follows it
-  int chain_last_p0 = -1;              // through the same flags (panel_chain_v_kernel)
+  int64_t chain_launches = 0;          // resident chain launches so far: launch n takes slot n % ring (its followers get the slot by ChainTicket)
   // Route counters (read-only through lpgp_get_option, keys "route_*"): incremented on the host where a forward substitution
   // picks its branch, for the tests that must prove which branch they ran (the profiling slots cannot tell these apart).
   struct RouteCounts {
@@ -121,11 +119,6 @@ struct lpgp_ctx : lpgp::Options {     // tuning options: options.h
   int64_t inverse_diag_panel = 4096;
   int64_t cv_fold_batch = 512;     // lpgp_mat_cv (evidence_cv.hip): folds of at most 128 rows per launch, 256 KiB of scratch each -- option "cv_fold_batch"
   int64_t evidence_h2d_bytes = 0, evidence_d2h_bytes = 0;
-  // set by lpgp_mat_cv around the factorisation of a large fold's scratch matrix (evidence_cv.hip: LargeFoldFactor), never by a caller:
-  // launch_potrf_tile launches the tile Cholesky with the Newton sign (potrf_tile.h).  The resident panel chain has no such form, so
-  // the same scope keeps it off (chain_resident_max_rows = -1) and every diagonal tile goes through launch_potrf_tile.
-  int tile_newton_inv = 0;
-  int panel_lds_extra = 0;         // bytes of LDS a fused panel launch asks for beyond its own 69 632 (set by the two-level forward substitution around its launches)
   // workspace
   // descriptor ring: an assembly launch copies its lowered descriptor into a pinned host slot,
   // from there (truly asynchronously) into the slot's device copy; the slot is reused only
@@ -135,8 +128,14 @@ struct lpgp_ctx : lpgp::Options {     // tuning options: options.h
   DescSlot desc_ring[DESC_RING];
   int desc_next = 0;
   int* d_info = nullptr;           // potrf info word
-  int* d_info_cur = nullptr;       // the word the running factorisation reports to (d_info, or the matrix's own sticky word)
-  int* h_info_pinned = nullptr;    // pinned mirror (multi-GPU: a device-to-host copy into pageable memory would BLOCK behind a collective that waits for a dead peer)
+  int* h_info_pinned = nullptr;    // pinned mirror, 16 ints (multi-GPU: a device-to-host copy into pageable memory would BLOCK behind a collective that waits for a dead peer)
+  enum PinnedSlot {                // one slot of h_info_pinned per reader, so that no two of them share a word
+    PIN_ALLREDUCE = 0,             // allreduce_max_int (dist.hip): the value on its way to the device and back
+    PIN_POTRF_DIST = 1,            // potrf_dist: this rank's own status, before the ranks agree on one
+    PIN_POTRF_PREDICT = 4,         // lpgp_potrf_predict: the matrix's sticky word, read back with the prediction's results
+    PIN_POTRF = 5,                 // potrf_blocked_impl: the status of a factorisation that reports to the caller (lpgp_potrf)
+    PIN_SOLVE_WEIGHTS = 6,         // lpgp_solve_weights: the status of the single-vector solve
+  };
   double* d_tmp = nullptr;         // small scratch (vectors)
   int64_t tmp_cap = 0;
   double* h_stage = nullptr;       // pinned host staging for the results of a prediction: ONE asynchronous device-to-host copy and
@@ -463,9 +462,11 @@ int launch_trsv_tile(lpgp_ctx* ctx, hipStream_t stream, double* V, int64_t ldv, 
 int launch_trsm_tile(lpgp_ctx* ctx, hipStream_t stream, double* X, int64_t ldx, const double* linv, const double* L, int64_t ldl,
                      int mt, int prof_kernel);
 // the whole chain of a panel of the forward substitution in one launch (solve_panel.h: panel_solve_kernel): V (nt_rows <= 4
-// tiles of rows, top row at V) <- L_KK^{-1} V; linv: the panel's tile inverses (contiguous), L: its diagonal block
+// tiles of rows, top row at V) <- L_KK^{-1} V; linv: the panel's tile inverses (contiguous), L: its diagonal block.
+// lds_extra: bytes of LDS the launch asks for beyond the kernel's own 69 632, at most PANEL_LDS_PAD (solve_panel.h: launch_panel_solve_rg)
+constexpr int PANEL_LDS_PAD = 20480;
 int launch_trsv_panel(lpgp_ctx* ctx, hipStream_t stream, double* V, int64_t ldv, const double* linv, const double* L, int64_t ldl,
-                      int nt_rows, int nt_cols, int prof_kernel);
+                      int nt_rows, int nt_cols, int prof_kernel, int lds_extra = 0);
 // the same chain for rows: X (mt tiles of rows x nt_cols <= 4 tile columns) <- X L_KK^{-T}, L_KK already factored
 // the same with the look-ahead update by the previous panel (4 tiles = 512 solved rows right above V) fused in front (solve4p.hip)
 int launch_trsv_panel_ahead(lpgp_ctx* ctx, hipStream_t stream, double* V, int64_t ldv, const double* linv, const double* L, const double* Lprev,
@@ -473,15 +474,27 @@ int launch_trsv_panel_ahead(lpgp_ctx* ctx, hipStream_t stream, double* V, int64_
 int launch_trsm_panel(lpgp_ctx* ctx, hipStream_t stream, double* X, int64_t ldx, const double* linv, const double* L, int64_t ldl,
                       int nt_cols, int mt, int prof_kernel);
 
-// chain.hip: the whole chain of panel [p0, p0 + 4) (rows down to tile T) in one launch
-int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info, bool rows_here = true, bool ahead = false);
-int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info);
-int launch_panel_chain_v(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, double* V, int64_t ldv, int64_t cols, int* d_info);
+// chain.hip: the whole chain of panel [p0, p0 + 4) (rows down to tile T) in one launch.  *ticket: what a launch that follows this
+// chain through its flags is given (launch_panel_chain_rows, launch_panel_chain_v); it names ONE chain launch, whatever is launched after it
+struct ChainTicket {
+  int* slot = nullptr;             // the launch's flag slot in lpgp_ctx::d_chain_flags
+  int p0 = -1;                     // its panel
+  int64_t seq = -1;                // lpgp_ctx::chain_launches when the slot was taken (the slot is recycled 32 launches later)
+};
+int launch_panel_chain(lpgp_ctx* ctx, hipStream_t stream, FactorView F, int p0, int T, int* d_info, ChainTicket* ticket, bool rows_here = true, bool ahead = false);
+int launch_panel_chain_rows(lpgp_ctx* ctx, hipStream_t stream, FactorView F, const ChainTicket& chain, int p0, int T, int* d_info);
+int launch_panel_chain_v(lpgp_ctx* ctx, hipStream_t stream, FactorView F, const ChainTicket& chain, int p0, double* V, int64_t ldv, int64_t cols, int* d_info);
 // potrf.hip -------------------------------------------------------------------------------
 int debug_tile_xcc(int32_t* out8, int reset);
+// The form of a factorisation's tile Cholesky.  newton: the Newton sign in the last correction of a pivot's reciprocal square root
+// (potrf_tile.h), for factors whose results are read off the inverse (lpgp_mat_cv's large folds).  The resident panel chain has no
+// such form: a factorisation of this form runs without it, every diagonal tile through launch_potrf_tile.
+enum class TileForm : int { plain, newton };
 int launch_potrf_tile(lpgp_ctx* ctx, hipStream_t stream, double* a, int64_t lda, double* linv,
-                      int* d_info, int info_base);
-int potrf_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t T, int32_t* info);
+                      int* d_info, int info_base, TileForm form);
+int potrf_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t T, int32_t* info, TileForm form = TileForm::plain);
+// api.hip: lpgp_potrf in a given form (checks, distributed or single GPU, the matrix's state transitions)
+int potrf_mat(lpgp_ctx* ctx, lpgp_mat* mat, int32_t* info, TileForm form);
 int potrf_predict_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t T, double* v, int64_t ldv, int64_t m_pad);
 // dist.hip: Pr x Pc block-cyclic factorisation and panel-streaming solves
 int potrf_dist(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t T, int32_t* info);

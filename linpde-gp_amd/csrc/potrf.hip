@@ -12,9 +12,6 @@
 //   (high-priority stream, followed immediately by the next panel factorisation) and the
 //   remainder (second stream): look-ahead of one panel.
 
-#include <climits>
-#include <cstdlib>
-
 #include <algorithm>
 
 #include "lpgp_internal.h"
@@ -31,7 +28,7 @@ __global__ __launch_bounds__(TILE_WAVES * 64) void potrf_tile_kernel(double* __r
 }
 
 // the same with the Newton sign in the last correction of a pivot's reciprocal square root (potrf_tile.h): the factorisations of
-// lpgp_mat_cv's large folds, whose results are read off S^{-1} (lpgp_ctx::tile_newton_inv)
+// lpgp_mat_cv's large folds, whose results are read off S^{-1} (TileForm::newton)
 __global__ __launch_bounds__(TILE_WAVES * 64) void potrf_tile_newton_kernel(double* __restrict__ a, int64_t lda,
                                                                  double* __restrict__ linv, int* __restrict__ info,
                                                                  int info_base) {
@@ -51,9 +48,9 @@ int debug_tile_xcc(int32_t* out8, int reset) {
 }
 
 int launch_potrf_tile(lpgp_ctx* ctx, hipStream_t stream, double* a, int64_t lda, double* linv,
-                      int* d_info, int info_base) {
+                      int* d_info, int info_base, TileForm form) {
   const size_t shmem = (size_t)TILE_LDS_DOUBLES * sizeof(double);
-  void (*kfn)(double*, int64_t, double*, int*, int) = ctx->tile_newton_inv ? potrf_tile_newton_kernel : potrf_tile_kernel;
+  void (*kfn)(double*, int64_t, double*, int*, int) = form == TileForm::newton ? potrf_tile_newton_kernel : potrf_tile_kernel;
   LPGP_TRY_RC(ensure_lds_attr(ctx, reinterpret_cast<const void*>(kfn), shmem));
   prof_begin(ctx, stream, LPGP_K_POTRF_TILE, (double)TILE * TILE * TILE / 3.0, 0.0);
   hipLaunchKernelGGL(kfn, dim3(1), dim3(TILE_WAVES * 64), shmem, stream, a, lda, linv, d_info, info_base);
@@ -90,9 +87,9 @@ static int rhs_update(lpgp_ctx* ctx, hipStream_t st, FactorView F, RhsView V, in
 }
 
 // The panel step of the forward substitution: V[q0:q1] <- L[q0:q1, q0:q1]^{-1} V[q0:q1] (at most four tile rows where `fused`), as ONE
-// launch (panel_solve_kernel) or tile by tile with the rank-128 updates of the panel's own rows in between
-static int solve_panel(lpgp_ctx* ctx, hipStream_t st, FactorView F, RhsView V, int q0, int q1, bool fused) {
-  if (fused) return launch_trsv_panel(ctx, st, V.rows(q0), V.ld, F.inv(q0), F.diag(q0), F.ld, q1 - q0, V.mtl, LPGP_K_PANEL);
+// launch (panel_solve_kernel; lds_extra: its LDS padding, see launch_panel_solve_rg) or tile by tile with the rank-128 updates of the panel's own rows in between
+static int solve_panel(lpgp_ctx* ctx, hipStream_t st, FactorView F, RhsView V, int q0, int q1, bool fused, int lds_extra = 0) {
+  if (fused) return launch_trsv_panel(ctx, st, V.rows(q0), V.ld, F.inv(q0), F.diag(q0), F.ld, q1 - q0, V.mtl, LPGP_K_PANEL, lds_extra);
   for (int jt = q0; jt < q1; ++jt) {
     LPGP_TRY(launch_trsv_tile(ctx, st, V.rows(jt), V.ld, F.inv(jt), F.diag(jt), F.ld, V.mtl, LPGP_K_TRSM));
     LPGP_TRY(rhs_update(ctx, st, F, V, jt, jt + 1, jt + 1, q1));
@@ -138,14 +135,28 @@ struct Ride {
   std::vector<std::pair<int, int>> held;
   int64_t chain_launches0 = 0;   // resident chain launches before this factorisation (flag slots are recycled half a ring later)
 };
-static int ride_panel_now(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ride* rd, bool sync_first, bool resident = false);
+// One running factorisation, as potrf_blocked_impl hands it to its phases: what is factored, where its status goes, in which form.
+struct Factorisation {
+  lpgp_ctx* ctx;
+  FactorView F;
+  int T, TR;                 // tile columns to factor; tile ROWS of the matrix (TR >= T, see factor_columns)
+  int* status;               // the device word this factorisation reports to: the context's, or the matrix's sticky one
+  TileForm form;
+  int resident_max_rows;     // row limit of the resident chain in THIS factorisation (< 0: none)
+  Ride* ride;                // the substitution riding inside it (null: none)
+  // a panel `width` tiles wide with `rows_below` tile rows under it is taken by the resident chain (max_rows: the row limit of the form asked about)
+  bool chain_takes(int width, int rows_below, int max_rows) const { return resident_max_rows >= 0 && width == 4 && rows_below <= max_rows && !ctx->distributed(); }
+  bool chain_takes(int width, int rows_below) const { return chain_takes(width, rows_below, resident_max_rows); }      // (the one-launch form)
+};
+static int ride_panel_now(const Factorisation& fc, int p0, int p1, bool sync_first, const ChainTicket* chain = nullptr);
 
 // panel [p0, p1) of the factor is final on the panel stream from here on: enqueue its substitution step(s)
-// (resident: the panel's chain was the resident kernel, launched last on the panel stream -- the step may follow it flag by flag)
-static int ride_panel(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ride* rd, bool old_panel = false, bool resident = false) {
+// (chain: the panel's chain was the resident kernel, this launch of it the last on the panel stream -- the step may follow it flag by flag)
+static int ride_panel(const Factorisation& fc, int p0, int p1, bool old_panel = false, const ChainTicket* chain = nullptr) {
+  lpgp_ctx* const ctx = fc.ctx; Ride* const rd = fc.ride; const int T = fc.T;
   // (steps of OLD panels -- a block append pushes its rows through them before it factors anything -- may pass the gate: they fill
   //  the start-up of the append, the first panel chain on an otherwise idle chip; ride_old_ungated)
-  if (!rd->open && old_panel && ctx->ride_old_ungated && rd->held.empty()) return ride_panel_now(ctx, F, T, p0, p1, rd, true);
+  if (!rd->open && old_panel && ctx->ride_old_ungated && rd->held.empty()) return ride_panel_now(fc, p0, p1, true);
   if (!rd->open) {
     if ((int64_t)(T - p1) * 100 > (int64_t)rd->gate_pct * T && p1 < T) {
       rd->held.emplace_back(p0, p1);
@@ -154,17 +165,18 @@ static int ride_panel(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ride* 
     rd->open = true;
     bool first = true;
     for (auto& h : rd->held) {
-      LPGP_TRY(ride_panel_now(ctx, F, T, h.first, h.second, rd, first));
+      LPGP_TRY(ride_panel_now(fc, h.first, h.second, first));
       first = false;
     }
     const bool none_held = rd->held.empty();
     rd->held.clear();
-    return ride_panel_now(ctx, F, T, p0, p1, rd, true, resident && none_held);
+    return ride_panel_now(fc, p0, p1, true, none_held ? chain : nullptr);
   }
-  return ride_panel_now(ctx, F, T, p0, p1, rd, true, resident);
+  return ride_panel_now(fc, p0, p1, true, chain);
 }
 
-static int ride_panel_now(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ride* rd, bool sync_first, bool resident) {
+static int ride_panel_now(const Factorisation& fc, int p0, int p1, bool sync_first, const ChainTicket* chain) {
+  lpgp_ctx* const ctx = fc.ctx; Ride* const rd = fc.ride; const FactorView F = fc.F; const int T = fc.T;
   const bool two = rd->stream2 != nullptr && rd->stream2 != rd->stream && rd->V.mtl >= 8;
   // A panel of the RESIDENT chain, a right-hand side of few columns: the panel step does not wait for the chain kernel to end
   // -- it follows the factor workgroup through the chain's own flags (chain.hip: panel_chain_v_kernel) and ends one tile solve
@@ -173,8 +185,9 @@ static int ride_panel_now(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ri
   // (Wide right-hand sides stay behind the event: c3's 132 workgroups following the LAST panel -- no update beside it they could be
   //  in the way of -- made the step 0.5 ms slower, 50.7-50.9 against 50.2-50.3: by then the substitution lags the chain anyway,
   //  and 32 columns per workgroup is the slower panel step of the two when nothing is left to overlap with.)
-  const bool vchain = resident && sync_first && !two && ctx->fused_solve && p1 - p0 == 4 && ctx->ride_vchain_max_wgs > 0 &&
-                      rd->V.mtl * 4 <= ctx->ride_vchain_max_wgs && ctx->chain_last_p0 == p0 && ctx->chain_launches - rd->chain_launches0 <= 24;
+  // (chain->seq + 1: the resident launches up to and including the one the step follows)
+  const bool vchain = chain && sync_first && !two && ctx->fused_solve && p1 - p0 == 4 && ctx->ride_vchain_max_wgs > 0 &&
+                      rd->V.mtl * 4 <= ctx->ride_vchain_max_wgs && chain->p0 == p0 && chain->seq + 1 - rd->chain_launches0 <= 24;
   // ... and are not dispatched before the chain kernel itself can be (everything in front of it on the panel stream is done):
   // they would only hold their CUs waiting.  (Under a profiler that SERIALISES kernels -- rocprofv3 --pmc -- a follower that is
   // picked before its chain kernel waits out its poll limit and the step fails with a negative status: LPGP_RIDE_VCHAIN=0 there.)
@@ -182,7 +195,7 @@ static int ride_panel_now(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ri
   if (vchain) ++ctx->route.ride_vchain;
   if (two) ++ctx->route.ride_two;
   if (vchain)
-    LPGP_TRY(launch_panel_chain_v(ctx, rd->stream, F, p0, rd->V.rows(p0), rd->V.ld, (int64_t)rd->V.mtl * TILE, ctx->d_info_cur));
+    LPGP_TRY(launch_panel_chain_v(ctx, rd->stream, F, *chain, p0, rd->V.rows(p0), rd->V.ld, (int64_t)rd->V.mtl * TILE, fc.status));
   if (sync_first && (rd->stream != ctx->s_main || two)) {
     hipEvent_t ev = rd->ev[rd->it++ & 1];
     LPGP_HIP(hipEventRecord(ev, ctx->s_main));
@@ -229,7 +242,8 @@ static int ride_panel_now(lpgp_ctx* ctx, FactorView F, int T, int p0, int p1, Ri
 // On return the panel stream is behind every update of the call.
 // TR >= T: the matrix has TR tile ROWS (rows beyond tile T belong to a block that is solved and updated but never factored: the
 // augmented form of potrf_predict_blocked); T stays the limit of the COLUMNS.
-static int factor_columns(lpgp_ctx* ctx, FactorView F, int T, int c0, int cl, hipStream_t sU, hipEvent_t dep, Ride* ride, int TR) {
+static int factor_columns(const Factorisation& fc, int c0, int cl, hipStream_t sU, hipEvent_t dep) {
+  lpgp_ctx* const ctx = fc.ctx; Ride* const ride = fc.ride; const FactorView F = fc.F; const int T = fc.T, TR = fc.TR;
   const int nbt = (int)(ctx->nb / TILE);
   hipStream_t sP = ctx->s_main;
   bool dep_pending_p = dep != nullptr, dep_pending_u = dep != nullptr;
@@ -255,13 +269,14 @@ static int factor_columns(lpgp_ctx* ctx, FactorView F, int T, int c0, int cl, hi
       dep_pending_p = false;
     }
     // panel factorisation on sP: the resident chain (one launch, chain.hip) where the chain is what bounds the pipeline ...
-    const bool resident = ctx->chain_resident_max_rows >= 0 && p1 - p0 == 4 && TR - p1 <= ctx->chain_resident_max_rows && !ctx->distributed();
+    const bool resident = fc.chain_takes(p1 - p0, TR - p1);
     const bool ahead = ahead_next;          // the previous iteration left this panel's look-ahead update to its chain kernel
     ahead_next = false;
     LPGP_CHECK(!ahead || resident, "factor_columns: a look-ahead update was left to a chain kernel that is not launched");
+    ChainTicket chain;
     if (resident) {
       if (ride && ride->stream != sP && ctx->ride_vchain_pre) LPGP_HIP(hipEventRecord(ctx->ev_chain_pre, sP));      // (see ride_panel_now: the step that follows the chain's flags)
-      LPGP_TRY(launch_panel_chain(ctx, sP, F, p0, TR, ctx->d_info_cur, true, ahead));
+      LPGP_TRY(launch_panel_chain(ctx, sP, F, p0, TR, fc.status, &chain, true, ahead));
     }
     // ... a WIDER panel as two launches (round 6): the factor workgroup and the in-block rows (13 workgroups of 152 KB: thirteen CUs)
     // here, the rows below -- 16 per workgroup, 68 KB, two per CU -- on the outer-update stream, which is idle at these sizes and
@@ -269,25 +284,25 @@ static int factor_columns(lpgp_ctx* ctx, FactorView F, int T, int c0, int cl, hi
     // (the mask leaves it `reserve` of them); the launch is ordered behind everything in front of the chain kernel (an event), so
     // that it is not dispatched before the chain kernel can be.  The substitution's follower is not used with this form.
     hipStream_t sR = ctx->s_outer;
-    const bool resident2 = !resident && ctx->chain_resident2_max_rows > 0 && ctx->chain_resident_max_rows >= 0 && p1 - p0 == 4 && TR - p1 > 0 &&
-                           TR - p1 <= ctx->chain_resident2_max_rows && !ctx->distributed() && !ctx->single_stream && sR && sR != sP && ctx->ev_chain_rows;
+    const bool resident2 = !resident && ctx->chain_resident2_max_rows > 0 && fc.chain_takes(p1 - p0, TR - p1, ctx->chain_resident2_max_rows) && TR - p1 > 0 &&
+                           !ctx->single_stream && sR && sR != sP && ctx->ev_chain_rows;
     if (resident2) {
       LPGP_HIP(hipEventRecord(ctx->ev_chain_pre, sP));
-      LPGP_TRY(launch_panel_chain(ctx, sP, F, p0, TR, ctx->d_info_cur, false));
+      LPGP_TRY(launch_panel_chain(ctx, sP, F, p0, TR, fc.status, &chain, false));
       LPGP_HIP(hipStreamWaitEvent(sR, ctx->ev_chain_pre, 0));
-      LPGP_TRY(launch_panel_chain_rows(ctx, sR, F, p0, TR, ctx->d_info_cur));
+      LPGP_TRY(launch_panel_chain_rows(ctx, sR, F, chain, p0, TR, fc.status));
       LPGP_HIP(hipEventRecord(ctx->ev_chain_rows, sR));
       LPGP_HIP(hipStreamWaitEvent(sP, ctx->ev_chain_rows, 0));
     }
     // ... else tile by tile
     for (int jt = p0; jt < p1 && !resident && !resident2; ++jt) {
-      LPGP_TRY(launch_potrf_tile(ctx, sP, F.diag(jt), F.ld, F.inv(jt), ctx->d_info_cur, jt * TILE));
+      LPGP_TRY(launch_potrf_tile(ctx, sP, F.diag(jt), F.ld, F.inv(jt), fc.status, jt * TILE, fc.form));
       if (jt + 1 < TR) {
         LPGP_TRY(panel_trsm(ctx, sP, F, jt, F.tile(jt + 1, jt), TR - jt - 1));      // rows below, same tile column
         if (jt + 1 < p1) LPGP_TRY(trailing_update(ctx, sP, F, jt, jt + 1, jt + 1, p1, TR, 2, LPGP_K_SYRK_PANEL));
       }
     }
-    if (ride) LPGP_TRY(ride_panel(ctx, F, T, p0, p1, ride, false, resident));          // columns [p0, p1) are final: their substitution step follows on the ride stream
+    if (ride) LPGP_TRY(ride_panel(fc, p0, p1, false, resident ? &chain : nullptr));          // columns [p0, p1) are final: their substitution step follows on the ride stream
     if (p1 >= cl) break;
     const int K = (p1 - p0) * TILE;
     if (dep_pending_p) {
@@ -319,8 +334,7 @@ static int factor_columns(lpgp_ctx* ctx, FactorView F, int T, int c0, int cl, hi
     // long updates (two of the nine in a c3 step took 0.98 and 0.48 ms: profiles/r05_fused_final_trace_compact.txt.gz).  Only
     // where at least `chain_ahead_min_rows` tile rows lie below the next panel: the fused form costs the chain ~35 us (the
     // factor workgroup waits for four products of tile 0's rows), a launch of (a) on a few tiles less than that.
-    const bool fuse_next = ctx->chain_ahead && p1 - p0 == 4 && p2 - p1 == 4 && ctx->chain_resident_max_rows >= 0 &&
-                           TR - p2 <= ctx->chain_resident_max_rows && TR - p2 >= ctx->chain_ahead_min_rows && !ctx->distributed();
+    const bool fuse_next = ctx->chain_ahead && p1 - p0 == 4 && fc.chain_takes(p2 - p1, TR - p2) && TR - p2 >= ctx->chain_ahead_min_rows;
     if (!chain_bound || fuse_next) LPGP_HIP(hipEventRecord(evp, sP));
     // (a) next panel's columns on sP; they were last written by the previous remainder update
     if (have_upd_event) LPGP_HIP(hipStreamWaitEvent(sP, ctx->ev_upd[(it + 1) & 1], 0));
@@ -365,11 +379,11 @@ static int factor_columns(lpgp_ctx* ctx, FactorView F, int T, int c0, int cl, hi
 }
 
 // Factor tile columns [t_done, T) of the padded matrix; columns [0, t_done) already hold L.
-static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, FactorView F, int64_t t_done64, int64_t T64, int32_t* info, Ride* ride, int TR = 0);
-int potrf_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, int64_t T64, int32_t* info) {
+static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, FactorView F, int64_t t_done64, int64_t T64, int32_t* info, Ride* ride, int TR = 0, TileForm form = TileForm::plain);
+int potrf_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done64, int64_t T64, int32_t* info, TileForm form) {
   FactorView F;
   LPGP_TRY(factor_view(mat, &F));
-  return potrf_blocked_impl(ctx, mat, F, t_done64, T64, info, nullptr);
+  return potrf_blocked_impl(ctx, mat, F, t_done64, T64, info, nullptr, 0, form);
 }
 
 // dst[c + r * ldd] = src[r + c * lds] for r < rows, c < cols (both multiples of 32): 32 x 32 tiles through LDS
@@ -463,15 +477,15 @@ int potrf_predict_blocked(lpgp_ctx* ctx, lpgp_mat* mat, int64_t t_done, int64_t 
   return 0;
 }
 
-static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, FactorView F, int64_t t_done64, int64_t T64, int32_t* info, Ride* ride, int TR) {
+static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, FactorView F, int64_t t_done64, int64_t T64, int32_t* info, Ride* ride, int TR, TileForm form) {
   const int T = (int)T64, t_done = (int)t_done64;
   if (TR < T) TR = T;                                 // (TR > T: rows beyond the columns being factored, see factor_columns)
   const int64_t ld = F.ld;
   const int nbt = (int)(ctx->nb / TILE);
   hipStream_t sP = ctx->s_main, sU = ctx->s_upd;
   // info != nullptr: the status is read back at the end (one host synchronisation); nullptr (lpgp_potrf_enqueue): it
-  // accumulates in the matrix's own sticky word and is read by lpgp_mat_check
-  ctx->d_info_cur = info ? ctx->d_info : mat->d_status;
+  // accumulates in the matrix's own sticky word and is read by lpgp_mat_check.  (The resident chain has the plain tile form only.)
+  const Factorisation fc{ctx, F, T, TR, info ? ctx->d_info : mat->d_status, form, form == TileForm::plain ? ctx->chain_resident_max_rows : -1, ride};
   if (info) LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), sP));
 
   // ---- phase A (append): push the new rows through the already factored columns ----
@@ -492,7 +506,7 @@ static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, FactorView F, int64_
                                mk(X, ld, F.tile(jt + 1, jt), ld, F.tile(t_done, jt + 1), ld, mnew, p1 - jt - 1, TILE, -1.0, 1.0, 0),
                                LPGP_K_GEMM));
       }
-      if (ride) LPGP_TRY(ride_panel(ctx, F, T, p0, p1, ride, true));  // the old panel's columns, new rows included, are final
+      if (ride) LPGP_TRY(ride_panel(fc, p0, p1, true));  // the old panel's columns, new rows included, are final
       if (p1 < t_done)
         LPGP_TRY(launch_gemm(ctx, sP, 0, 0,
                              mk(F.tile(t_done, p0), ld, F.tile(p1, p0), ld, F.tile(t_done, p1), ld, mnew, t_done - p1, (p1 - p0) * TILE, -1.0, 1.0, 0),
@@ -542,7 +556,7 @@ static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, FactorView F, int64_
   for (int q0 = t_done; q0 < T; ++oit) {
     const bool outer = la && NBt > nbt && (T - q0) > ctx->nb_outer_min_tiles && (T - q0) > NBt;
     const int q1 = outer ? q0 + NBt : T;
-    LPGP_TRY(factor_columns(ctx, F, T, q0, q1, sU, ev_a1, ride, TR));
+    LPGP_TRY(factor_columns(fc, q0, q1, sU, ev_a1));
     if (q1 >= T) break;
     hipEvent_t ev_fact = ctx->ev_outer_fact[oit & 1];
     LPGP_HIP(hipEventRecord(ev_fact, sP));             // outer panel [q0, q1) is final (factor_columns joins its updates into sP)
@@ -571,7 +585,7 @@ static int potrf_blocked_impl(lpgp_ctx* ctx, lpgp_mat* mat, FactorView F, int64_
   if (ev_b) LPGP_HIP(hipStreamWaitEvent(sP, ev_b, 0));
   if (!info) return 0;
   // (into pinned memory: a copy into pageable memory is staged and blocks twice; this wait is once per conditioning of the default mode)
-  int* const hp = ctx->h_info_pinned + 5;
+  int* const hp = ctx->h_info_pinned + lpgp_ctx::PIN_POTRF;
   LPGP_HIP(hipMemcpyAsync(hp, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, sP));
   LPGP_HIP(hipStreamSynchronize(sP));
   const int h_info = *hp;
@@ -621,14 +635,13 @@ static int trsm_lower_two_level(lpgp_ctx* ctx, FactorView F, int T, RhsView V, i
   hipStream_t sP = ctx->s_main, sU = ctx->s_upd_all;
   bool have_upd_event = false;
   int it = 0;
-  struct PadGuard { lpgp_ctx* c; ~PadGuard() { c->panel_lds_extra = 0; } } pad_guard{ctx};
-  ctx->panel_lds_extra = ctx->panel_exclusive ? 20480 : 0;       // (solve_panel.h: the inner panel chains do not slip into the long outer updates)
+  const int lds_pad = ctx->panel_exclusive ? PANEL_LDS_PAD : 0;       // (solve_panel.h: the inner panel chains do not slip into the long outer updates)
   for (int q0 = 0; q0 < T; q0 += NBt, ++it) {
     const int q1 = (q0 + NBt < T) ? q0 + NBt : T;
     // inner: the block's own rows, right-looking by fused panels
     for (int p0 = q0; p0 < q1; p0 += nbt) {
       const int p1 = (p0 + nbt < q1) ? p0 + nbt : q1;
-      LPGP_TRY(solve_panel(ctx, sP, F, V, p0, p1, true));
+      LPGP_TRY(solve_panel(ctx, sP, F, V, p0, p1, true, lds_pad));
       LPGP_TRY(rhs_update(ctx, sP, F, V, p0, p1, p1, q1));
     }
     if (q1 >= T) break;
@@ -695,9 +708,6 @@ int trsm_lower_blocked(lpgp_ctx* ctx, FactorView F, int64_t T64, double* v, int6
   // of its own the look-ahead update took those slots and the panel chain behind it starved until the remainder update
   // drained: the update stream idled 57-95 us per panel.  Kernel traces: profiles/r04_predict_fused_ahead.txt.)  The fused
   // kernel shares its CUs with the update for most of the update's duration, so it pays only while the update is long.
-  static const int pad_blocked = [] { const char* e = std::getenv("LPGP_PANEL_LDS_EXTRA_BLOCKED"); return e ? std::atoi(e) : 0; }();   // (measurement aid)
-  struct PadGuard { lpgp_ctx* c; ~PadGuard() { c->panel_lds_extra = 0; } } pad_guard{ctx};
-  ctx->panel_lds_extra = pad_blocked;
   const bool ahead_ok = fused && la && nbt == 4 && ctx->fused_ahead != 0;
   bool solved = false;                      // the panel at the top of the loop has been solved by the previous iteration's fused launch
   // (b): the remainder update by panel [p0, p1) -- rows [p2, T) -- on the update stream, behind `evp`

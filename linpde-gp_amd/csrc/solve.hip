@@ -212,11 +212,11 @@ __global__ __launch_bounds__(512, 2) void tile_solve_kernel(TileSolveArgs g) {
   for (int q = 0; q < 8; ++q) pbase[q * pstep] = x[q];
 }
 
-int launch_panel_solve_4(lpgp_ctx* ctx, hipStream_t stream, const PanelSolveArgs& a, int64_t cols, bool kfast);    // solve4.hip
+int launch_panel_solve_4(lpgp_ctx* ctx, hipStream_t stream, const PanelSolveArgs& a, int64_t cols, bool kfast, int lds_extra);    // solve4.hip
 
 template <bool KFAST>
 static int launch_panel_any(lpgp_ctx* ctx, hipStream_t stream, double* V, int64_t ldv, const double* linv, const double* L, int64_t ldl,
-                            int nt_panel, int64_t count, int prof_kernel) {
+                            int nt_panel, int64_t count, int prof_kernel, int lds_extra = 0) {
   if (count <= 0 || nt_panel <= 0) return 0;
   LPGP_CHECK(nt_panel <= 4, "panel solve: at most 4 tiles per panel (got %d)", nt_panel);
   PanelSolveArgs a;
@@ -225,10 +225,10 @@ static int launch_panel_any(lpgp_ctx* ctx, hipStream_t stream, double* V, int64_
   if (prof_kernel >= 0) prof_begin(ctx, stream, prof_kernel, (double)count * (double)(nt_panel * TILE) * (double)(nt_panel * TILE), 0.0);
   int rc;
   switch (nt_panel) {
-    case 1: rc = launch_panel_solve_nt<1, KFAST>(ctx, stream, a, count); break;
-    case 2: rc = launch_panel_solve_nt<2, KFAST>(ctx, stream, a, count); break;
-    case 3: rc = launch_panel_solve_nt<3, KFAST>(ctx, stream, a, count); break;
-    default: rc = launch_panel_solve_4(ctx, stream, a, count, KFAST); break;
+    case 1: rc = launch_panel_solve_nt<1, KFAST>(ctx, stream, a, count, lds_extra); break;
+    case 2: rc = launch_panel_solve_nt<2, KFAST>(ctx, stream, a, count, lds_extra); break;
+    case 3: rc = launch_panel_solve_nt<3, KFAST>(ctx, stream, a, count, lds_extra); break;
+    default: rc = launch_panel_solve_4(ctx, stream, a, count, KFAST, lds_extra); break;
   }
   if (prof_kernel >= 0) prof_end(ctx, stream);
   return rc;
@@ -236,8 +236,8 @@ static int launch_panel_any(lpgp_ctx* ctx, hipStream_t stream, double* V, int64_
 
 // V (nt_rows <= 4 tiles of rows x nt_cols * 128 columns, column-major ldv) <- L_KK^{-1} V in place, L_KK the panel's diagonal block
 int launch_trsv_panel(lpgp_ctx* ctx, hipStream_t stream, double* V, int64_t ldv, const double* linv, const double* L, int64_t ldl,
-                      int nt_rows, int nt_cols, int prof_kernel) {
-  return launch_panel_any<true>(ctx, stream, V, ldv, linv, L, ldl, nt_rows, (int64_t)nt_cols * TILE, prof_kernel);
+                      int nt_rows, int nt_cols, int prof_kernel, int lds_extra) {
+  return launch_panel_any<true>(ctx, stream, V, ldv, linv, L, ldl, nt_rows, (int64_t)nt_cols * TILE, prof_kernel, lds_extra);
 }
 
 // X (mt * 128 rows x nt_cols <= 4 tiles of columns, column-major ldx) <- X L_KK^{-T} in place: the rows below (or appended

@@ -145,7 +145,7 @@ int lpgp_test_potrf_tile(lpgp_ctx* ctx, double* T, double* Linv, int32_t* info) 
   double *const dT = bT.as(), *const dL = bL.as();
   LPGP_HIP(hipMemcpy(dT, T, tbytes, hipMemcpyHostToDevice));
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), ctx->s_main));
-  LPGP_TRY(launch_potrf_tile(ctx, ctx->s_main, dT, TILE, dL, ctx->d_info, 0));
+  LPGP_TRY(launch_potrf_tile(ctx, ctx->s_main, dT, TILE, dL, ctx->d_info, 0, TileForm::plain));
   LPGP_HIP(hipMemcpyAsync(&h, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->s_main));
   LPGP_HIP(hipStreamSynchronize(ctx->s_main));
   LPGP_HIP(hipMemcpy(T, dT, tbytes, hipMemcpyDeviceToHost));

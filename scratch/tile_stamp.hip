@@ -22,7 +22,7 @@ int main() {
     hipMemcpy(dA, A.data(), n * n * 8, hipMemcpyHostToDevice); hipMemset(dinfo, 0, 4);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0);
-    launch_potrf_tile(&ctx, 0, dA, n, dL, dinfo, 0);
+    launch_potrf_tile(&ctx, 0, dA, n, dL, dinfo, 0, TileForm::plain);
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     unsigned long long h[16];

@@ -180,7 +180,17 @@ def test_boundaries_128_and_129(s):
 
 
 def test_blocks(s):
-    got = s.u2.cross_validate("blocks", return_cov=True)
+    limit = s.ctx.get_option("chain_resident_max_rows")
+    s.ctx.profile_enable(True)
+    s.ctx.profile_reset()
+    try:
+        got = s.u2.cross_validate("blocks", return_cov=True)
+        prof = s.ctx.profile_get()
+    finally:
+        s.ctx.profile_enable(False)
+    # the large fold's 150 rows pad to two tiles, factored per tile (the Newton form has no resident chain); no option is touched for it
+    assert prof["potrf_tile"]["launches"] == 2, prof["potrf_tile"]
+    assert s.ctx.get_option("chain_resident_max_rows") == limit
     folds = [np.arange(150), np.arange(150, 220)]
     assert all(np.array_equal(a, b) for a, b in zip(got.folds, folds))
     ref, lap = s.refs("blocks", folds)

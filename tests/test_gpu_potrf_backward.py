@@ -307,6 +307,25 @@ def test_first_bad_pivot(ctx, sched, row):
     check_factor(mat, A, f"after failure {row[0]} a")
 
 
+def test_a_status_goes_to_the_word_of_its_own_factorisation(ctx):
+    """An enqueued factorisation reports to its matrix's sticky word, an eager one to the caller, whatever other factorisation
+    ran in between on the same context (pivot 129: the first of the second tile, inside the first resident panel)."""
+    k = 129
+    A = matrix("a", PIV_N)
+    B = broken(A, lapack(A)[0], k)
+    bad = new_matrix(ctx, B)
+    bad.potrf_enqueue()
+    good = new_matrix(ctx, A)
+    assert good.potrf() == 0
+    assert bad.check() == (k, 0)
+    # the other way round
+    good2, bad2 = new_matrix(ctx, A), new_matrix(ctx, B)
+    good2.potrf_enqueue()
+    assert bad2.potrf() == k
+    assert good2.check() == (0, -1)            # (lpgp_mat_check: no pivot failed, so no block is named)
+    check_factor(good2, A, "enqueued, a failing factorisation behind it a")
+
+
 @pytest.mark.parametrize("enqueue", [False, True], ids=["eager", "enqueued"])
 def test_first_bad_pivot_in_an_appended_block(ctx, enqueue):
     """info counts the PADDED order: row j (0-based) of block b fails as poff(b) + j + 1; the old factor stays bitwise as it
