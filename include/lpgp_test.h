@@ -77,6 +77,27 @@ int  lpgp_test_solve_vec_bwd(lpgp_ctx* ctx, lpgp_mat* mat, const double* y_host_
  * Single GPU, fully factored, status read.                                                                          */
 int  lpgp_test_trsm_lower_t(lpgp_ctx* ctx, lpgp_mat* mat, double* v_host_padded, int64_t m_pad);
 
+/* the raw storage of the view of `mat` -- lpgp_mat_padded_size squared doubles, column-major, leading dimension the padded size, the
+ * padding rows and the tiles above the diagonal included -- read into `host` (set == 0) or overwritten from it (set != 0): what the
+ * padded layout holds, and operands no assembly produces (garbage in the padding, a chosen lower triangle under a factored state).
+ * Single GPU; the state of `mat` (factored or not) is left as it is.                                                  */
+int  lpgp_test_mat_raw(lpgp_ctx* ctx, lpgp_mat* mat, int32_t set, double* host);
+
+/* lpgp_mat_factor_matmul with the chunk size of its first kernel given: kc = 1, 2, 4 or 8 tiles of columns per workgroup, instead
+ * of the one the size and the CU count choose.  Every kc computes the same product.  Refuses what the public call refuses.   */
+int  lpgp_test_factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host,
+                             double* out_host, int32_t kc);
+/* lpgp_mat_evidence, lpgp_mat_loo, lpgp_mat_evidence_grad and lpgp_mat_evidence_grad_diag with at most max_wgs workgroups in the first
+ * stage of their reductions (0: the launch of the public call), so that a thread or a wave takes several rows or columns at a size a
+ * test can afford.  Arguments, results and refusals are the public calls'.                                             */
+int  lpgp_test_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, int32_t max_wgs, double out_host[2]);
+int  lpgp_test_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, int32_t max_wgs, double* mean_host,
+                   double* var_host, double* logp_host);
+int  lpgp_test_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host,
+                             int32_t max_wgs, double out_host[2]);
+int  lpgp_test_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, int32_t bi, const double* v_host, double scalar,
+                                  const double* r_host, int32_t max_wgs, double out_host[2]);
+
 #ifdef __cplusplus
 }
 #endif

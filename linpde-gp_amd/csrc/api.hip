@@ -1749,19 +1749,6 @@ int lpgp_mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const doubl
   return mat_loo(ctx, mat, r_host, y_host, mean_host, var_host, logp_host);
 }
 
-// `other` (the dense inverse, an assembled derivative) lies over the blocks `mat` views: same context, same block layout, not factored
-static int evidence_grad_layout(const lpgp_mat* mat, const lpgp_mat* other, const char* fn, const char* what) {
-  LPGP_CHECK(other->ctx == mat->ctx && !other->poisoned, "%s: %s belongs to another context or is undefined", fn, what);
-  LPGP_CHECK(other->pn == mat->pn && other->blocks.size() == mat->blocks.size() && other->hidden.empty(),
-             "%s: %s has another block layout than the matrix (%lld padded rows in %d blocks against %lld in %d)", fn, what, (long long)other->pn,
-             (int)other->blocks.size(), (long long)mat->pn, (int)mat->blocks.size());
-  for (size_t b = 0; b < mat->blocks.size(); ++b)
-    LPGP_CHECK(other->blocks[b].n == mat->blocks[b].n && other->blocks[b].poff == mat->blocks[b].poff,
-               "%s: block %d of %s has %lld rows, the matrix has %lld", fn, (int)b, what, (long long)other->blocks[b].n, (long long)mat->blocks[b].n);
-  LPGP_CHECK(other->pn_fact == 0, "%s: %s must not be factored", fn, what);
-  return 0;
-}
-
 int lpgp_mat_inverse(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat** out) {
   LPGP_CHECK(ctx && mat && out, "lpgp_mat_inverse: null argument");
   LPGP_EVIDENCE_READY("lpgp_mat_inverse");

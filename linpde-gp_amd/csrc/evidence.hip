@@ -133,7 +133,11 @@ __global__ __launch_bounds__(EV_THREADS) void loo_final_kernel(const double* __r
   if (threadIdx.x == 0) *total = *info < 0 ? ev_status_nan(EV_NAN_HANDOVER) : s;
 }
 
-static int ev_wgs(int64_t pn) { return (int)std::min<int64_t>((pn + EV_THREADS - 1) / EV_THREADS, EV_MAX_WGS); }
+// workgroups of a stage-1 launch; max_wgs > 0 (the test hooks') caps them below what the size asks for
+static int ev_wgs(int64_t pn, int max_wgs) {
+  const int nwg = (int)std::min<int64_t>((pn + EV_THREADS - 1) / EV_THREADS, EV_MAX_WGS);
+  return max_wgs > 0 ? std::min(nwg, max_wgs) : nwg;
+}
 
 static unsigned long long ev_bits(double v) {
   unsigned long long u;
@@ -171,7 +175,7 @@ int ev_download(lpgp_ctx* ctx, double* dst, const double* src, size_t doubles) {
 
 // lpgp_mat_evidence: one forward solve of the residual through the single-vector path (trsv.hip), the two-stage reduction over
 // the solved vector and the factor's diagonal, ONE read-back of 16 bytes.
-int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]) {
+int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2], int max_wgs) {
   const int64_t pn = mat->pn, T = pn / TILE;
   hipStream_t st = ctx->s_main;
   FactorView F;
@@ -188,7 +192,7 @@ int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
   if (ctx->trsv_resident) LPGP_TRY(solve_vec_fwd_resident(ctx, F, T, d, d + o_z, ctx->d_info));
   else LPGP_TRY(solve_vec_fwd(ctx, st, F, T, d, d + o_z));
-  const int nwg = ev_wgs(pn);
+  const int nwg = ev_wgs(pn, max_wgs);
   hipLaunchKernelGGL(evidence_partial_kernel, dim3((unsigned)nwg), dim3(EV_THREADS), 0, st, (const double*)(d + o_z), (const double*)mat->a, mat->lr_cap,
                      reinterpret_cast<const int32_t*>(d + pn), pn, d + o_part);
   hipLaunchKernelGGL(evidence_final_kernel, dim3(1), dim3(EV_THREADS), 0, st, (const double*)(d + o_part), nwg, (const int*)ctx->d_info, d + o_out);
@@ -234,7 +238,8 @@ int mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host) {
 }
 
 // lpgp_mat_loo: w = G^{-1} r (single-vector solve), d = diag(G^{-1}) (above), the fused epilogue; logp_host[n] is the sum
-int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host, double* logp_host) {
+int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host, double* logp_host,
+            int max_wgs) {
   const int64_t pn = mat->pn, n = mat->n, T = pn / TILE;
   hipStream_t st = ctx->s_main;
   FactorView F;
@@ -253,7 +258,7 @@ int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
   LPGP_TRY(solve_vec(ctx, F, T, d, d + o_tmp, ctx->d_info));
   LPGP_TRY(inverse_diag_device(ctx, mat, d + o_d));
-  const int nwg = ev_wgs(pn);
+  const int nwg = ev_wgs(pn, max_wgs);
   hipLaunchKernelGGL(loo_epilogue_kernel, dim3((unsigned)nwg), dim3(EV_THREADS), 0, st, (const double*)d, (const double*)(d + o_d), (const double*)(d + pn),
                      lrow, pn, d + o_res, d + o_part);
   hipLaunchKernelGGL(loo_final_kernel, dim3(1), dim3(EV_THREADS), 0, st, (const double*)(d + o_part), nwg, (const int*)ctx->d_info, d + o_res + 3 * pn);

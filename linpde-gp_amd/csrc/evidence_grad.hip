@@ -153,6 +153,12 @@ int mat_inverse_into(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat* out) {
   return 0;        // asynchronous: consumers are ordered behind it on the main stream
 }
 
+// workgroups of a stage-1 launch with `per` columns or rows each; max_wgs > 0 (the test hooks') caps them below what the size asks for
+static int eg_wgs(int64_t pn, int per, int max_wgs) {
+  const int nwg = (int)std::min<int64_t>((pn + per - 1) / per, EG_MAX_WGS);
+  return max_wgs > 0 ? std::min(nwg, max_wgs) : nwg;
+}
+
 static int eg_finish(lpgp_ctx* ctx, hipStream_t st, double* d_part, int nwg, double* d_out, double out_host[2], StreamDrain* drain, const char* fn) {
   hipLaunchKernelGGL(evidence_grad_final_kernel, dim3(1), dim3(EG_THREADS), 0, st, (const double*)d_part, nwg, (const int*)ctx->d_info, d_out);
   LPGP_HIP(hipGetLastError());
@@ -165,8 +171,22 @@ static int eg_finish(lpgp_ctx* ctx, hipStream_t st, double* d_part, int nwg, dou
   return 0;
 }
 
+// `other` (the dense inverse, an assembled derivative) lies over the blocks `mat` views: same context, same block layout, not factored
+int evidence_grad_layout(const lpgp_mat* mat, const lpgp_mat* other, const char* fn, const char* what) {
+  LPGP_CHECK(other->ctx == mat->ctx && !other->poisoned, "%s: %s belongs to another context or is undefined", fn, what);
+  LPGP_CHECK(other->pn == mat->pn && other->blocks.size() == mat->blocks.size() && other->hidden.empty(),
+             "%s: %s has another block layout than the matrix (%lld padded rows in %d blocks against %lld in %d)", fn, what, (long long)other->pn,
+             (int)other->blocks.size(), (long long)mat->pn, (int)mat->blocks.size());
+  for (size_t b = 0; b < mat->blocks.size(); ++b)
+    LPGP_CHECK(other->blocks[b].n == mat->blocks[b].n && other->blocks[b].poff == mat->blocks[b].poff,
+               "%s: block %d of %s has %lld rows, the matrix has %lld", fn, (int)b, what, (long long)other->blocks[b].n, (long long)mat->blocks[b].n);
+  LPGP_CHECK(other->pn_fact == 0, "%s: %s must not be factored", fn, what);
+  return 0;
+}
+
 // lpgp_mat_evidence_grad: w = G^{-1} r through the single-vector path (trsv.hip), the streaming contraction, ONE read-back of 16 bytes
-int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host, double out_host[2]) {
+int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host, double out_host[2],
+                      int max_wgs) {
   const int64_t pn = mat->pn, T = pn / TILE;
   hipStream_t st = ctx->s_main;
   FactorView F;
@@ -183,7 +203,7 @@ int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const 
   ctx->evidence_h2d_bytes += (int64_t)(h.size() * sizeof(double));
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
   LPGP_TRY(solve_vec(ctx, F, T, d, d + o_tmp, ctx->d_info));
-  const int nwg = (int)std::min<int64_t>((pn + EG_WAVES - 1) / EG_WAVES, EG_MAX_WGS);
+  const int nwg = eg_wgs(pn, EG_WAVES, max_wgs);
   hipLaunchKernelGGL(evidence_grad_partial_kernel, dim3((unsigned)nwg), dim3(EG_THREADS), 0, st, (const double*)ginv->a, ginv->lr_cap, (const double*)dG->a,
                      dG->lr_cap, (const double*)d, reinterpret_cast<const int32_t*>(d + pn), pn, d + o_part);
   LPGP_HIP(hipGetLastError());
@@ -192,7 +212,7 @@ int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const 
 
 // lpgp_mat_evidence_grad_diag: the pair for dG = diag(v) + scalar I on block bi, from w and the diagonal of the inverse
 int mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, int32_t bi, const double* v_host, double scalar, const double* r_host,
-                           double out_host[2]) {
+                           double out_host[2], int max_wgs) {
   const int64_t pn = mat->pn, T = pn / TILE;
   const lpgp_block& B = mat->blocks[(size_t)bi];
   hipStream_t st = ctx->s_main;
@@ -212,7 +232,7 @@ int mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, i
   ctx->evidence_h2d_bytes += (int64_t)(h.size() * sizeof(double));
   LPGP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
   LPGP_TRY(solve_vec(ctx, F, T, d, d + o_tmp, ctx->d_info));
-  const int nwg = (int)std::min<int64_t>((pn + EG_THREADS - 1) / EG_THREADS, EG_MAX_WGS);
+  const int nwg = eg_wgs(pn, EG_THREADS, max_wgs);
   hipLaunchKernelGGL(evidence_grad_diag_partial_kernel, dim3((unsigned)nwg), dim3(EG_THREADS), 0, st, (const double*)ginv->a, ginv->lr_cap,
                      (const double*)(d + pn), (const double*)d, reinterpret_cast<const int32_t*>(d + 2 * pn), pn, d + o_part);
   LPGP_HIP(hipGetLastError());

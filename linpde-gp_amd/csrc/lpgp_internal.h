@@ -515,9 +515,11 @@ int solve_vec_fwd_resident(lpgp_ctx* ctx, FactorView F, int64_t T, const double*
 int solve_vec_bwd(lpgp_ctx* ctx, hipStream_t st, FactorView F, int64_t T, double* y, double* x);
 int solve_vec_bwd_resident(lpgp_ctx* ctx, FactorView F, int64_t T, double* y, double* x, int* info);
 // evidence.hip: the quantities read off the factor of a fully factored single-GPU matrix (lpgp_mat_evidence, lpgp_mat_inverse_diag, lpgp_mat_loo)
-int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2]);
+// (max_wgs > 0, from the test hooks only: a cap on the workgroups of the stage-1 reduction, so that a thread takes several rows)
+int mat_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, double out_host[2], int max_wgs = 0);
 int mat_inverse_diag(lpgp_ctx* ctx, lpgp_mat* mat, double* out_host);
-int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host, double* logp_host);
+int mat_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, double* mean_host, double* var_host, double* logp_host,
+            int max_wgs = 0);
 // ... and their pieces that evidence_cv.hip shares: the host staging of nvec logical vectors into the padded layout (behind them the map
 // padded row -> logical row as pn int32), the counted copies, diag(G^{-1}) into a device vector of pn doubles
 void ev_stage(const lpgp_mat* mat, const double* const* vecs, int nvec, std::vector<double>* h);
@@ -530,11 +532,15 @@ int mat_cv(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const double* r_h
 // evidence_grad.hip: the dense inverse W^T W, W = L^{-1}, into the lower triangle of `out` (same block layout, not factored), and the
 // pair (w^T dG w, tr(G^{-1} dG)) of GPML eq. 5.9 for an assembled dG / for dG = diag(v) + scalar I on block bi
 int mat_inverse_into(lpgp_ctx* ctx, lpgp_mat* mat, lpgp_mat* out);
-int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host, double out_host[2]);
+// what lpgp_mat_evidence_grad, its _diag form and lpgp_mat_cv ask of `other` (the dense inverse, an assembled derivative; `what` names it)
+int evidence_grad_layout(const lpgp_mat* mat, const lpgp_mat* other, const char* fn, const char* what);
+int mat_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host, double out_host[2],
+                      int max_wgs = 0);
 int mat_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, int32_t bi, const double* v_host, double scalar, const double* r_host,
-                           double out_host[2]);
+                           double out_host[2], int max_wgs = 0);
 // trmm.hip: out (n x s, C-order, logical rows) = shift[:, None] + L Z for the lower factor of a fully factored single-GPU matrix
-int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host, double* out_host);
+// (kc_force = 1, 2, 4 or 8, from the test hook only: the chunk size, instead of the one the size and the CU count choose)
+int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host, double* out_host, int kc_force = 0);
 
 // assemble.hip ----------------------------------------------------------------------------
 // Every assembly kernel writes element (row_off + i, col_off + j) of the GLOBAL padded matrix to where `lay` keeps

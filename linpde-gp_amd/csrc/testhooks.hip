@@ -358,7 +358,6 @@ int lpgp_test_trsm_lower_t(lpgp_ctx* ctx, lpgp_mat* mat, double* v_host, int64_t
 
 // the raw storage of the view of `mat` -- pn x pn doubles, column-major, leading dimension pn, padding rows and the tiles above the
 // diagonal included -- read (set == 0) or overwritten (set != 0): what the padded layout holds, and operands with garbage in the padding.
-// Declared by its one caller (tests/test_gpu_evidence_grad.py binds it itself), not in include/lpgp_test.h.
 int lpgp_test_mat_raw(lpgp_ctx* ctx, lpgp_mat* mat, int32_t set, double* host) {
   LPGP_CHECK(ctx && mat && host && mat->pn > 0, "lpgp_test_mat_raw: bad argument");
   LPGP_DEVICE(ctx);
@@ -368,6 +367,54 @@ int lpgp_test_mat_raw(lpgp_ctx* ctx, lpgp_mat* mat, int32_t set, double* host) {
   if (set) LPGP_HIP(hipMemcpy2D(mat->a, ld, host, row, row, (size_t)mat->pn, hipMemcpyHostToDevice));
   else LPGP_HIP(hipMemcpy2D(host, row, mat->a, ld, row, (size_t)mat->pn, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// lpgp_mat_factor_matmul with the chunk size of trmm_lower_kernel given (kc = 1, 2, 4 or 8 tiles of columns per workgroup) instead of
+// chosen from the size and the CU count; refuses what the public call refuses
+int lpgp_test_factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host, double* out_host, int32_t kc) {
+  LPGP_CHECK(ctx && mat && Z_host && out_host && s >= 1, "lpgp_test_factor_matmul: bad argument");
+  LPGP_CHECK(kc == 1 || kc == 2 || kc == 4 || kc == 8, "lpgp_test_factor_matmul: the chunk size is 1, 2, 4 or 8 tiles, not %d", kc);
+  LPGP_DEVICE(ctx);
+  LPGP_TEST_FACTORED(ctx, mat, "lpgp_test_factor_matmul");
+  return factor_matmul(ctx, mat, Z_host, s, shift_host, out_host, kc);
+}
+
+// lpgp_mat_evidence / lpgp_mat_loo / lpgp_mat_evidence_grad / lpgp_mat_evidence_grad_diag with at most max_wgs workgroups in the
+// stage-1 reduction (max_wgs >= 1; 0: the launch of the public call), so that a thread or a wave takes several rows or columns at a size
+// a test can hold a reference for; each refuses what its public call refuses
+int lpgp_test_evidence(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, int32_t max_wgs, double out_host[2]) {
+  LPGP_CHECK(ctx && mat && r_host && out_host && max_wgs >= 0, "lpgp_test_evidence: bad argument");
+  LPGP_DEVICE(ctx);
+  LPGP_TEST_FACTORED(ctx, mat, "lpgp_test_evidence");
+  return mat_evidence(ctx, mat, r_host, out_host, max_wgs);
+}
+
+int lpgp_test_loo(lpgp_ctx* ctx, lpgp_mat* mat, const double* r_host, const double* y_host, int32_t max_wgs, double* mean_host, double* var_host,
+                  double* logp_host) {
+  LPGP_CHECK(ctx && mat && r_host && y_host && mean_host && var_host && logp_host && max_wgs >= 0, "lpgp_test_loo: bad argument");
+  LPGP_DEVICE(ctx);
+  LPGP_TEST_FACTORED(ctx, mat, "lpgp_test_loo");
+  return mat_loo(ctx, mat, r_host, y_host, mean_host, var_host, logp_host, max_wgs);
+}
+
+int lpgp_test_evidence_grad(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, const lpgp_mat* dG, const double* r_host, int32_t max_wgs,
+                            double out_host[2]) {
+  LPGP_CHECK(ctx && mat && ginv && dG && r_host && out_host && max_wgs >= 0, "lpgp_test_evidence_grad: bad argument");
+  LPGP_DEVICE(ctx);
+  LPGP_TEST_FACTORED(ctx, mat, "lpgp_test_evidence_grad");
+  LPGP_TRY(evidence_grad_layout(mat, ginv, "lpgp_test_evidence_grad", "the inverse"));
+  LPGP_TRY(evidence_grad_layout(mat, dG, "lpgp_test_evidence_grad", "the derivative"));
+  return mat_evidence_grad(ctx, mat, ginv, dG, r_host, out_host, max_wgs);
+}
+
+int lpgp_test_evidence_grad_diag(lpgp_ctx* ctx, lpgp_mat* mat, const lpgp_mat* ginv, int32_t bi, const double* v_host, double scalar,
+                                 const double* r_host, int32_t max_wgs, double out_host[2]) {
+  LPGP_CHECK(ctx && mat && ginv && r_host && out_host && max_wgs >= 0, "lpgp_test_evidence_grad_diag: bad argument");
+  LPGP_DEVICE(ctx);
+  LPGP_TEST_FACTORED(ctx, mat, "lpgp_test_evidence_grad_diag");
+  LPGP_CHECK(bi >= 0 && bi < (int32_t)mat->blocks.size(), "lpgp_test_evidence_grad_diag: bad block %d", bi);
+  LPGP_TRY(evidence_grad_layout(mat, ginv, "lpgp_test_evidence_grad_diag", "the inverse"));
+  return mat_evidence_grad_diag(ctx, mat, ginv, bi, v_host, scalar, r_host, out_host, max_wgs);
 }
 
 }  // extern "C"

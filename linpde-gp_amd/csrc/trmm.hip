@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void trmm_reduce_kernel(const double* __restri
   out[(int64_t)lr * s + col] = (shift ? shift[lr] : 0.0) + sum;
 }
 
-int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host, double* out_host) {
+int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s, const double* shift_host, double* out_host, int kc_force) {
   const int64_t pn = mat->pn, n = mat->n;
   const int T = (int)(pn / TILE), nct = (int)((s + TR_ST - 1) / TR_ST);
   LPGP_CHECK(nct <= 65535, "lpgp_mat_factor_matmul: at most %d columns", 65535 * TR_ST);
@@ -124,6 +124,7 @@ int factor_matmul(lpgp_ctx* ctx, lpgp_mat* mat, const double* Z_host, int64_t s,
   int kc = TR_KC_MAX;
   const int64_t want = 2 * (int64_t)(ctx->cus > 0 ? ctx->cus : 256);
   while (kc > 1 && count_chunks(kc) * nct < want) kc /= 2;
+  if (kc_force > 0) kc = kc_force;               // (the test hook's: any chunk size computes the same product)
   const int64_t nchunks = count_chunks(kc);
   // integer tables: [logical row of padded row p, or -1 | first chunk of tile row i (T + 1) | tile row of chunk | first tile of chunk]
   std::vector<int32_t> tab((size_t)(pn + T + 1 + 2 * nchunks), -1);

@@ -107,3 +107,64 @@ def backward_error_t(L, x, y):
     assert not np.any(res[zero] != 0), "a nonzero residual where |L^T||x| + |y| is zero"
     e = np.max(np.where(zero, LD(0), res / np.where(zero, LD(1), den)), axis=0)
     return float(e) if e.ndim == 0 else e.astype(np.float64)
+
+
+# ---- the two-stage reductions of csrc/evidence.hip: their launch shape and the roundings on a path ---------------------------------
+EV_THREADS = 256          # threads of a workgroup of evidence_partial_kernel / loo_epilogue_kernel
+EV_MAX_WGS = 256          # workgroups at most: the final kernel adds one partial per thread
+
+
+def reduction_workgroups(pn, max_wgs=0):
+    """Workgroups of stage 1 over `pn` padded rows: one per 256 rows, at most 256; `max_wgs` > 0 (the test hooks' cap) at most that."""
+    nwg = min(-(-pn // EV_THREADS), EV_MAX_WGS)
+    return min(nwg, max_wgs) if max_wgs > 0 else nwg
+
+
+def reduction_depth(pn, max_wgs=0):
+    """k: the rows a thread of stage 1 adds at most -- row i goes to thread i mod (256 nwg), so k = ceil(pn / (256 nwg))."""
+    return -(-pn // (EV_THREADS * reduction_workgroups(pn, max_wgs)))
+
+
+def sum_roundings(k):
+    """Roundings on the longest path from a term to the result of a two-stage reduction whose threads add k terms each: k in the
+    thread (one fma or add per term, the first onto 0.0), then 6 shuffle adds and 2 adds over the four waves in stage 1, the partial
+    read as it is, 6 shuffle adds and 2 adds over the waves in stage 2: 16 + k."""
+    return 16 + k
+
+
+def sum_ulps(k):
+    """Bound of a sum of terms of one sign, in u x the sum: (1 + u)^m - 1 with m = sum_roundings(k) is below (m + 3) u for every m a
+    launch can have (m u << 1); the margin of 3 is the one the bound has carried at k = 1, where it reads 20."""
+    return float(sum_roundings(k) + 3)
+
+
+def log_ulps(k, base=7.0):
+    """Bound of the log det term in u 2 sum |log L_ii|: `base` covers the reduction at k = 1 (where the per-thread add 0 + log is exact)
+    and the device log's own error; each of the k - 1 further adds of a thread rounds once, at most u x the sum of the moduli."""
+    return float(base + (k - 1))
+
+
+def two_stage_sum(terms, nwg):
+    """The sum of `terms` (float64) in the order of evidence_partial_kernel + evidence_final_kernel with `nwg` workgroups, in float64:
+    thread t of workgroup b adds the terms b 256 + t, + nwg 256, ... in order; lanes by shuffles (offset 32, 16, ..., 1), the four
+    waves as (0 + 1) + (2 + 3); stage 2 the same over the partials, one per thread.  A host model to hold the bound to."""
+    terms = np.asarray(terms, dtype=np.float64)
+
+    def block_sum(v):                             # v: 256 values, one per thread
+        v = v.reshape(4, 64).copy()
+        for off in (32, 16, 8, 4, 2, 1):
+            shifted = np.zeros_like(v)
+            shifted[:, :64 - off] = v[:, off:]
+            shifted[:, 64 - off:] = v[:, 64 - off:]       # (a lane beyond the wave reads its own value; lane 0 never depends on it)
+            v = v + shifted
+        return (v[0, 0] + v[1, 0]) + (v[2, 0] + v[3, 0])
+
+    assert 1 <= nwg <= EV_MAX_WGS
+    part = np.zeros(EV_THREADS)
+    for b in range(nwg):
+        acc = np.zeros(EV_THREADS)
+        for i0 in range(b * EV_THREADS, terms.size, nwg * EV_THREADS):
+            chunk = terms[i0:i0 + EV_THREADS]
+            acc[:chunk.size] = acc[:chunk.size] + chunk
+        part[b] = block_sum(acc)
+    return block_sum(part)

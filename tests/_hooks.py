@@ -18,7 +18,8 @@ HOOKS_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "liblpgp_testhooks.so"
 
 EXPORTED = ["lpgp_test_stair_enumerate", "lpgp_test_gemm", "lpgp_test_gemm_cyc", "lpgp_test_potrf_tile", "lpgp_test_tile_step", "lpgp_test_panel_solve",
             "lpgp_debug_tile_xcc", "lpgp_probe_mfma_f64", "lpgp_probe_hbm_write", "lpgp_test_force_status", "lpgp_test_solve_vec_fwd", "lpgp_test_solve_vec_bwd",
-            "lpgp_test_trsm_lower_t"]
+            "lpgp_test_trsm_lower_t", "lpgp_test_mat_raw", "lpgp_test_factor_matmul", "lpgp_test_evidence", "lpgp_test_loo", "lpgp_test_evidence_grad",
+            "lpgp_test_evidence_grad_diag"]
 
 
 def _load() -> C.CDLL:
@@ -46,6 +47,12 @@ def _load() -> C.CDLL:
     sig("lpgp_test_solve_vec_fwd", C.c_int, vp, vp, pd, pd)
     sig("lpgp_test_solve_vec_bwd", C.c_int, vp, vp, pd, pd)
     sig("lpgp_test_trsm_lower_t", C.c_int, vp, vp, pd, i64)
+    sig("lpgp_test_mat_raw", C.c_int, vp, vp, i32, pd)
+    sig("lpgp_test_factor_matmul", C.c_int, vp, vp, pd, i64, pd, pd, i32)
+    sig("lpgp_test_evidence", C.c_int, vp, vp, pd, i32, pd)
+    sig("lpgp_test_loo", C.c_int, vp, vp, pd, pd, i32, pd, pd, pd)
+    sig("lpgp_test_evidence_grad", C.c_int, vp, vp, vp, vp, pd, i32, pd)
+    sig("lpgp_test_evidence_grad_diag", C.c_int, vp, vp, vp, i32, pd, dbl, pd, i32, pd)
     return lib
 
 
@@ -182,3 +189,82 @@ def trsm_lower_t(ctx: Context, mat, V: np.ndarray) -> np.ndarray:
 def force_status(ctx: Context, mat, value: int) -> None:
     """Leave the status word of `mat` (a `_engine.GramMatrix`) as an enqueued factorisation ending with `value` would."""
     check(lib.lpgp_test_force_status(ctx._h, mat._h, int(value)), "lpgp_test_force_status")
+
+
+def mat_raw(ctx: Context, mat, values: np.ndarray | None = None) -> np.ndarray:
+    """The padded storage of a matrix (`lpgp_test_mat_raw`): `mat.padded_n` squared, element (r, c) at [r, c], padding rows and the
+    part above the diagonal included; `values`: overwrite it with them (and return them)."""
+    pn = mat.padded_n
+    if values is not None and np.shape(values) != (pn, pn):
+        raise ValueError(f"storage must have shape ({pn}, {pn}), got {np.shape(values)}")
+    buf = np.empty((pn, pn)) if values is None else np.ascontiguousarray(np.asarray(values).T, dtype=np.double)      # column-major on the device
+    check(lib.lpgp_test_mat_raw(ctx._h, mat._h, 0 if values is None else 1, buf.ctypes.data_as(C.POINTER(C.c_double))), "lpgp_test_mat_raw")
+    return buf.T
+
+
+def _vector(mat, v, what: str) -> np.ndarray:
+    v = np.ascontiguousarray(v, dtype=np.double)
+    if v.shape != (mat.n,):
+        raise ValueError(f"{what} must have shape ({mat.n},), got {v.shape}")
+    return v
+
+
+def factor_matmul(ctx: Context, mat, Z: np.ndarray, shift: np.ndarray | None, kc: int) -> np.ndarray:
+    """`mat.factor_matmul(Z, shift)` with chunks of `kc` (1, 2, 4 or 8) tiles of columns per workgroup (`lpgp_test_factor_matmul`)
+    instead of the chunk size the device would choose."""
+    Z = np.ascontiguousarray(Z, dtype=np.double)
+    if Z.ndim != 2 or Z.shape[0] != mat.n or Z.shape[1] == 0:
+        raise ValueError(f"shape mismatch: factor of order {mat.n} @ {Z.shape}")
+    if shift is not None:
+        shift = _vector(mat, shift, "shift")
+    out = np.full((mat.n, Z.shape[1]), np.nan)
+    pd = C.POINTER(C.c_double)
+    check(lib.lpgp_test_factor_matmul(ctx._h, mat._h, Z.ctypes.data_as(pd), Z.shape[1], shift.ctypes.data_as(pd) if shift is not None else None,
+                                      out.ctypes.data_as(pd), int(kc)), "lpgp_test_factor_matmul")
+    return out
+
+
+def evidence(ctx: Context, mat, r: np.ndarray, max_wgs: int = 0) -> "tuple[float, float]":
+    """`mat.evidence(r)` with at most `max_wgs` workgroups in the first stage of the reduction (`lpgp_test_evidence`; 0: as the
+    public call)."""
+    r = _vector(mat, r, "residual")
+    out = np.full(2, np.nan)
+    pd = C.POINTER(C.c_double)
+    check(lib.lpgp_test_evidence(ctx._h, mat._h, r.ctypes.data_as(pd), int(max_wgs), out.ctypes.data_as(pd)), "lpgp_test_evidence")
+    return float(out[0]), float(out[1])
+
+
+def loo(ctx: Context, mat, r: np.ndarray, y: np.ndarray, max_wgs: int = 0):
+    """`mat.loo(r, y)` with at most `max_wgs` workgroups in the epilogue (`lpgp_test_loo`; 0: as the public call)."""
+    r, y = _vector(mat, r, "residual"), _vector(mat, y, "observations")
+    n = mat.n
+    mean, var, logp = np.full(n, np.nan), np.full(n, np.nan), np.full(n + 1, np.nan)
+    pd = C.POINTER(C.c_double)
+    check(lib.lpgp_test_loo(ctx._h, mat._h, r.ctypes.data_as(pd), y.ctypes.data_as(pd), int(max_wgs), mean.ctypes.data_as(pd), var.ctypes.data_as(pd),
+                            logp.ctypes.data_as(pd)), "lpgp_test_loo")
+    return mean, var, logp[:n].copy(), float(logp[n])
+
+
+def evidence_grad(ctx: Context, mat, ginv, dG, r: np.ndarray, max_wgs: int = 0) -> "tuple[float, float]":
+    """`mat.evidence_grad(ginv, dG, r)` with at most `max_wgs` workgroups in the contraction (`lpgp_test_evidence_grad`; 0: as the
+    public call)."""
+    r = _vector(mat, r, "residual")
+    out = np.full(2, np.nan)
+    pd = C.POINTER(C.c_double)
+    check(lib.lpgp_test_evidence_grad(ctx._h, mat._h, ginv._h, dG._h, r.ctypes.data_as(pd), int(max_wgs), out.ctypes.data_as(pd)), "lpgp_test_evidence_grad")
+    return float(out[0]), float(out[1])
+
+
+def evidence_grad_diag(ctx: Context, mat, ginv, bi: int, r: np.ndarray, v: np.ndarray | None = None, scalar: float = 0.0,
+                       max_wgs: int = 0) -> "tuple[float, float]":
+    """`mat.evidence_grad_diag(ginv, bi, r, v, scalar)` with at most `max_wgs` workgroups (`lpgp_test_evidence_grad_diag`)."""
+    r = _vector(mat, r, "residual")
+    if v is not None:
+        v = np.ascontiguousarray(v, dtype=np.double)
+        if v.shape != (mat.block_sizes[bi],):
+            raise ValueError("diagonal has the wrong length")
+    out = np.full(2, np.nan)
+    pd = C.POINTER(C.c_double)
+    check(lib.lpgp_test_evidence_grad_diag(ctx._h, mat._h, ginv._h, int(bi), v.ctypes.data_as(pd) if v is not None else None, float(scalar),
+                                           r.ctypes.data_as(pd), int(max_wgs), out.ctypes.data_as(pd)), "lpgp_test_evidence_grad_diag")
+    return float(out[0]), float(out[1])

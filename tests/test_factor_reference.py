@@ -265,3 +265,42 @@ def test_backward_error_t_conventions():
     xbad[2] = 1e-300                                                       # a nonzero over a nonzero denominator: a number
     assert fr.backward_error_t(L, xbad, y) == 1.0
     assert np.isnan(fr.backward_error_t(L, np.array([1.0, np.nan, 0.0]), y))  # a NaN stays a NaN: no bar is met by it
+
+
+# ---- the depth-aware bounds of the two-stage reductions (test_gpu_evidence_backward.py, capped launches) -----------------------
+def test_reduction_depth_by_hand():
+    """k = ceil(pn / (256 nwg)), nwg = min(ceil(pn / 256), 256, cap): the cases of the GPU suite and the edges of the uncapped launch."""
+    assert fr.reduction_workgroups(768) == 3 and fr.reduction_workgroups(768, 1) == 1 and fr.reduction_workgroups(768, 2) == 2
+    assert fr.reduction_workgroups(768, 5) == 3                       # a cap above what the size asks for changes nothing
+    assert (fr.reduction_depth(768), fr.reduction_depth(768, 2), fr.reduction_depth(768, 1)) == (1, 2, 3)
+    assert (fr.reduction_depth(128), fr.reduction_depth(384, 1), fr.reduction_depth(512, 1)) == (1, 2, 2)
+    assert fr.reduction_workgroups(65536) == 256 and fr.reduction_depth(65536) == 1        # 256 x 256: the last size of one row per thread
+    assert fr.reduction_workgroups(65664) == 256 and fr.reduction_depth(65664) == 2        # one tile row more: the stride loop repeats
+
+
+def test_bounds_at_depth_1_2_3_by_hand():
+    """17, 18, 19 roundings; at k = 1 the constants the uncapped tests have always used (SUM_ULPS = 20, LOG_ULPS = 7)."""
+    assert [fr.sum_roundings(k) for k in (1, 2, 3)] == [17, 18, 19]
+    assert [fr.sum_ulps(k) for k in (1, 2, 3)] == [20.0, 21.0, 22.0]
+    assert [fr.log_ulps(k) for k in (1, 2, 3)] == [7.0, 8.0, 9.0]
+    for k in (1, 2, 3, 64):
+        m = fr.sum_roundings(k)
+        assert float((LD(1) + LD(U)) ** m - 1) < fr.sum_ulps(k) * U       # what the bound claims of m roundings
+
+
+@pytest.mark.parametrize("pn,cap", [(768, 0), (768, 2), (768, 1), (384, 1), (1408, 1)])
+def test_host_model_of_the_reduction_meets_the_bound(pn, cap):
+    """`two_stage_sum`, the host model of the order of summation, on non-negative terms over twelve decades: exact on integers
+    (nothing lost, nothing twice), and within sum_ulps(k) u of the long-double sum otherwise (the bound of a sum in ANY order, one
+    rounding per term, would be pn u)."""
+    rng = np.random.default_rng(pn + cap)
+    nwg, k = fr.reduction_workgroups(pn, cap), fr.reduction_depth(pn, cap)
+    ints = rng.integers(0, 65, pn).astype(np.float64)
+    assert fr.two_stage_sum(ints, nwg) == float(np.sum(ints.astype(np.int64)))
+    worst = 0.0
+    for _ in range(20):
+        terms = rng.uniform(0, 1, pn) * 10.0 ** rng.uniform(-6, 6, pn)
+        ref = np.sum(terms.astype(LD))
+        worst = max(worst, float(abs(LD(fr.two_stage_sum(terms, nwg)) - ref) / (U * ref)))
+    print(f"two-stage sum pn={pn} cap={cap}: k={k}, worst error {worst:.2f} u of the sum, bound {fr.sum_ulps(k):.0f} u")
+    assert worst <= fr.sum_ulps(k) < pn

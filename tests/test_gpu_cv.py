@@ -16,6 +16,13 @@ points, noise 1e-2; n = 220 in 256 + 128 = 384 padded rows, so the logical-to-pa
   7  refusals: an unfactored matrix, a `ginv` of another layout, a `fold_of` entry out of range, an empty fold -- each an error, a
      correct call afterwards the bits of before; the byte counters show O(n) bytes without `return_cov`
 
+  8  more folds than one trip takes: a second problem of 200 + 317 noisy values (517 rows in 256 + 384 padded) with 256, 257 and 517
+     singleton folds, the other rows in no fold.  cv_total_kernel adds the log densities in fold order with one thread, 256 per trip
+     of its loop (220 folds above: one trip), so `total` must be the left-to-right float64 sum of the device's own per-fold
+     values bit for bit; 517 folds also cross the default "cv_fold_batch" = 512 without touching the option (two batches, the
+     second of five folds), with the bits of batches of 3 and of 65535; per fold the reference and bar of 1 - 5; 517 singletons
+     against `leave_one_out()` as in 5
+
 Tolerance.  No a-priori bound for the tile Cholesky of S is derived here; the yardstick is measured: the same formulas in float64
 on NumPy / SciPy (LAPACK) from the same device factor (`evaluate_float64`); its distance from the long-double reference, per
 quantity (mean, var, log density per fold, total, covariances) and relative to the quantity's max-abs, is the yardstick, and the
@@ -40,6 +47,8 @@ whole column) the factor of S had a componentwise backward error of 11.7 u again
 showed it: singleton variances 7.0 x the yardstick (82 u componentwise), the folds of the earlier posterior 4.6 x, the 150-row fold
 of "blocks" (cond_2(S) = 5.4e3) 17 x in var and cov, 6.8 x in logp, 5.1 x in total."""
 import ctypes as C
+import functools
+import operator
 
 import numpy as np
 import pytest
@@ -311,3 +320,91 @@ def test_refusals_leave_everything_usable(s):
         up_c, down_c = moved(folds_, True)
         sizes = [f.size for f in folds] if name == "mixed" else ([150, 70] if name == "blocks" else [1] * n)
         assert down_c - down == 8 * sum(b * b for b in sizes) and up <= up_c <= up + 8 * (len(sizes) + 1)
+
+
+# ---- 8: more than 256 folds, more than one default batch -------------------------------------------------------------------
+class Setup517:
+    """Prior Matern-5/2 (lengthscale 0.5) in 1-D, 200 then 317 noisy values at scattered points, noise 1e-2: 517 rows in 256 + 384
+    padded rows.  The references of ALL 517 singleton folds are computed once; a singleton's result does not depend on which other
+    rows are in folds, so the first nf of them are the reference of nf folds."""
+    sizes = (200, 317)
+
+    def __init__(self):
+        import linpde_gp_amd as lp
+        from linpde_gp_amd import randvars
+        cf = lp.randprocs.covfuncs
+        rng = np.random.default_rng(517)
+        u = lp.GaussianProcess(lp.functions.Zero((1,)), cf.Matern((1,), nu=2.5, lengthscales=0.5))
+        ys = []
+        for nb in self.sizes:
+            X = rng.uniform(-1.0, 1.0, (nb, 1))
+            Y = np.sin(3.0 * X[:, 0]) + 0.1 * rng.standard_normal(nb)
+            u = u.condition_on_observations(Y, X, b=randvars.Normal(np.zeros(nb), np.full(nb, 1e-2)))
+            ys.append(Y)
+        self.u, self.y = u, np.concatenate(ys)
+        u._check_current()
+        self.mat = u._state.mat
+        self.ctx = self.mat.ctx
+        assert self.mat.n == 517 and self.mat.padded_n == 640
+        L = self.mat.todense("factor")
+        r = u._residual()
+        assert np.array_equal(r, self.y)             # zero prior mean
+        single = [np.array([i]) for i in range(517)]
+        self.ref, self.lap = cv.evaluate(L, r, self.y, single), cv.evaluate_float64(L, r, self.y, single)
+
+    def first(self, nf):
+        """(reference, LAPACK evaluation) of the folds {0}, ..., {nf - 1}: NaN for the rows in no fold, the total in fold order."""
+        out = []
+        for res in (self.ref, self.lap):
+            mean, var = res.mean.copy(), res.var.copy()
+            mean[nf:], var[nf:] = np.nan, np.nan
+            logp = res.logp[:nf]
+            out.append(cv.CvResult(mean, var, logp, functools.reduce(operator.add, list(logp)), res.cov[:nf]))
+        return out
+
+
+@pytest.fixture(scope="module")
+def s517():
+    setup = Setup517()
+    yield setup
+    del setup.u, setup.mat
+
+
+def same_bits(a, b, what):
+    for name in ("mean", "var", "log_predictive_density"):
+        assert getattr(a, name).tobytes() == getattr(b, name).tobytes(), f"{name} {what}"
+    assert a.total == b.total, f"total {what}"
+    assert (a.cov is None) == (b.cov is None)
+    if a.cov is not None:
+        assert np.concatenate([c.reshape(-1) for c in a.cov]).tobytes() == np.concatenate([c.reshape(-1) for c in b.cov]).tobytes(), f"cov {what}"
+
+
+@pytest.mark.parametrize("nf", [256, 257, 517])
+def test_singleton_folds_beyond_one_trip_of_the_total(s517, nf):
+    folds = [np.array([i]) for i in range(nf)]
+    ref, lap = s517.first(nf)
+    got = s517.u.cross_validate(folds, return_cov=True)
+    assert got.log_predictive_density.shape == (nf,) and len(got.cov) == nf
+    hold_all(f"{nf} singletons", got, lap, ref, folds)
+    assert np.all(np.isnan(got.mean[nf:])) and np.all(np.isnan(got.var[nf:])) and np.all(np.isnan(got.std[nf:]))
+    assert np.all(np.isfinite(got.mean[:nf])) and np.all(np.isfinite(got.var[:nf]))
+    # the total: one thread, fold order -- the left-to-right float64 sum of the device's own values
+    want = functools.reduce(operator.add, [float(v) for v in got.log_predictive_density])
+    print(f"[{nf} singletons] total {got.total!r}, left-to-right sum of the device's logp {want!r}")
+    assert got.total == want, f"total {got.total!r} is not the left-to-right sum {want!r} of the {nf} per-fold values"
+    plain = s517.u.cross_validate(folds)
+    assert plain.cov is None and plain.total == got.total and plain.log_predictive_density.tobytes() == got.log_predictive_density.tobytes()
+    if nf == 517:
+        # two batches at the default option (512 + 5 folds): the bits of batches of 3 and of one batch
+        assert s517.ctx.get_option("cv_fold_batch") == 512
+        with restored(s517.ctx, ("cv_fold_batch",)) as apply:
+            for batch in (3, 65535):
+                apply({"cv_fold_batch": batch})
+                same_bits(s517.u.cross_validate(folds, return_cov=True), got, f"depends on the batch size ({batch} against 512)")
+        assert s517.ctx.get_option("cv_fold_batch") == 512
+        same_bits(s517.u.cross_validate(517, return_cov=True), got, "differs between k = n and the list of singletons")
+        loo = s517.u.leave_one_out()
+        hold("517 leave_one_out mean", loo.mean, lap.mean, ref.mean)
+        hold("517 leave_one_out var", loo.var, lap.var, ref.var)
+        hold("517 leave_one_out logp", loo.log_predictive_density, lap.logp, ref.logp)
+        hold("517 leave_one_out total", [loo.total], [lap.total], [ref.total])

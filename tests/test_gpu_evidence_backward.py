@@ -31,6 +31,23 @@ test_gpu_predict_backward.py for V = L^-1 K).  test_gpu_evidence.py keeps the en
   f  the LOO variance and std through the public `leave_one_out()` on noise "s", componentwise against 1 / d and sqrt(1 / d) from
      the device's L, at the bar of d (LAPACK's d through the same two formulas).
 
+  g  the second regime of the reductions of b, c and e: beyond 65 536 padded rows (the README's c4) a thread of evidence_partial_kernel
+     and loo_epilogue_kernel takes several rows, i = b 256 + t, + 256 nwg, ...  The hooks lpgp_test_evidence and lpgp_test_loo cap the
+     workgroups at 1 and 2, so that at 768 padded rows ("n700", "chain") a thread holds k = ceil(pn / (256 nwg)) = 3 and 2 rows.  The
+     references are those of b, c and e; the bounds follow the depth (tests/_factor_reference.py, held on the CPU in
+     test_factor_reference.py; at k = 1 they are the constants above):
+       b, e-total: a thread adds its k terms by k fmas (adds), one rounding each, the first onto 0.0; the two stages as in b: 16 + k
+               roundings on a path, |q - sum z^2| <= ((1 + u)^(16 + k) - 1) q < sum_ulps(k) u q, sum_ulps(k) = 19 + k (20 at k = 1);
+       c:      the thread's first add 0 + log is exact, each of its k - 1 further adds rounds once, by at most u x the moduli it has
+               added: log_ulps(k) = LOG_ULPS + (k - 1) in u 2 sum |log L_ii|;
+       e, per row: mean, var and logp do not depend on the grid: the bits of the uncapped call.
+     Exact case: the identity factor in the layout of the chain, r integers of [-8, 8]: z = r, every z^2 and every partial sum an
+     integer, log 1 = 0: `evidence` returns (sum r^2, 0.0) exactly for 1, 2 and all workgroups.
+     The status EV_NAN_PADDING ("a padding row of the factor is not a row of the identity"): the diagonal entry of one padding row
+     set to 2.0 through lpgp_test_mat_raw makes `evidence` raise; with one workgroup and a padding row beyond row 255 the count is
+     carried over the trips of the thread's loop; with the entry restored the call returns the bits of before.  A checked error
+     return: nothing faults.
+
 Matrices (tests/_backward.py Appender): Matern-5/2, lengthscale 0.3, scattered points of [0, 1]^2, noise "m" (1: the easy
 control), "b" (1e-8: condition ~1e10) and "s" (rows over twelve decades); for z also "h", noise "b" on the points of [0, 0.5]^2
 (the worst diagonal tile of L has cond >= 1e4 at 700 rows: a tile solve without its refinement step shows).  The right-hand
@@ -297,3 +314,90 @@ def test_public_loo_variance_componentwise(ctx, opts, layout, panel):
         e, e_ref = fr.relative_error(dev, want), fr.relative_error(lap, want)
         print(f"\n[public loo {name} {layout} panel={panel}] relative error {e / U:.1f} u (LAPACK {e_ref / U:.1f} u): ratio {e / e_ref:.3f}; over {span:.1f} decades")
         assert e <= RATIO_D * e_ref, f"LOO {name}: {e / U:.1f} u = {e / e_ref:.2f} x LAPACK's {e_ref / U:.1f} u"
+
+
+# ---- g: several rows per thread (capped launches), the exact case, the padding status --------------------------------------
+CAPPED = ["n700", "chain"]          # 768 padded rows each: k = 3 rows per thread with one workgroup, 2 with two
+
+
+@pytest.mark.parametrize("cap", [1, 2])
+@pytest.mark.parametrize("layout", CAPPED)
+@pytest.mark.parametrize("kind", KINDS)
+def test_evidence_terms_several_rows_per_thread(ctx, kind, layout, cap):
+    import _hooks
+    c = case(ctx, kind, layout)
+    pn = c.mat.padded_n
+    k = fr.reduction_depth(pn, cap)
+    assert pn == 768 and k == {1: 3, 2: 2}[cap] and fr.sum_ulps(1) == SUM_ULPS and fr.log_ulps(1, LOG_ULPS) == LOG_ULPS
+    zp = _hooks.solve_vec_fwd(ctx, c.mat, c.r)
+    q, logdet = _hooks.evidence(ctx, c.mat, c.r, cap)
+    assert _hooks.evidence(ctx, c.mat, c.r, 0) == c.mat.evidence(c.r), "the hook without a cap is not the public call"
+    assert _hooks.evidence(ctx, c.mat, c.r, cap) == (q, logdet)
+    q_ref = np.sum(zp.astype(LD) ** 2)
+    eq = float(abs(LD(q) - q_ref) / (fr.sum_ulps(k) * U * q_ref))
+    ld_ref, scale = fr.logdet(c.diag)
+    el = float(abs(LD(logdet) - ld_ref) / (U * scale))
+    print(f"\n[evidence {kind} {layout} cap={cap} k={k}] q {q:.17e}: {eq:.3f} of the bound; log det {logdet:.17e}: {el:.3f} u 2 sum |log L_ii| "
+          f"(bar {fr.log_ulps(k, LOG_ULPS):.0f})")
+    assert eq <= 1.0, f"r^T G^-1 r is {eq:.2f} x the bound of its reduction at {k} rows per thread"
+    assert el <= fr.log_ulps(k, LOG_ULPS), f"log det is {el:.2f} u 2 sum |log L_ii| from 2 sum log L_ii at {k} rows per thread"
+
+
+@pytest.mark.parametrize("cap", [1, 2])
+@pytest.mark.parametrize("layout", CAPPED)
+@pytest.mark.parametrize("kind", KINDS)
+def test_loo_several_rows_per_thread(ctx, kind, layout, cap):
+    import _hooks
+    c = case(ctx, kind, layout)
+    k = fr.reduction_depth(c.mat.padded_n, cap)
+    base = c.mat.loo(c.r, c.y)
+    free = _hooks.loo(ctx, c.mat, c.r, c.y, 0)
+    assert all(np.asarray(a).tobytes() == np.asarray(b).tobytes() for a, b in zip(base, free)), "the hook without a cap is not the public call"
+    mean, var, logp, total = _hooks.loo(ctx, c.mat, c.r, c.y, cap)
+    for name, a, b in (("mean", mean, base[0]), ("var", var, base[1]), ("logp", logp, base[2])):
+        assert a.tobytes() == b.tobytes(), f"LOO {name} per row depends on the grid"
+    t_ref = np.sum(logp.astype(LD))
+    et = float(abs(LD(total) - t_ref) / (fr.sum_ulps(k) * U * np.sum(np.abs(logp.astype(LD)))))
+    print(f"\n[loo {kind} {layout} cap={cap} k={k}] total {total:.17e}: {et:.3f} of the bound")
+    assert np.isfinite(total) and et <= 1.0, f"sum of the log densities: {et:.2f} x the bound of its reduction at {k} rows per thread"
+
+
+def test_evidence_exact_on_the_identity_factor(ctx):
+    import _exact_operands as ex
+    import _hooks
+    mat = ex.identity_factored(ctx, CHAIN)
+    assert mat.padded_n == 768
+    r = np.random.default_rng(621).integers(-8, 9, mat.n)
+    want = (float(np.sum(r * r)), 0.0)
+    rf = r.astype(np.float64)
+    zp = _hooks.solve_vec_fwd(ctx, mat, rf)
+    assert np.array_equal(zp[ex.logical_mask(CHAIN)], rf), "a solve against the identity factor does not return r exactly"
+    for cap in (1, 2, 0):
+        got = _hooks.evidence(ctx, mat, rf, cap)
+        print(f"\n[evidence exact cap={cap}] {got!r}, want {want!r}")
+        assert got == want and not np.signbit(got[1]), (cap, got, want)
+    assert mat.evidence(rf) == want
+
+
+def test_padding_row_status(ctx):
+    import _exact_operands as ex
+    import _hooks
+    from linpde_gp_amd._lib import LpgpError
+    mat = ex.identity_factored(ctx, CHAIN)
+    mask = ex.logical_mask(CHAIN)
+    r = np.random.default_rng(622).integers(-8, 9, mat.n).astype(np.float64)
+    good = _hooks.mat_raw(ctx, mat).copy()
+    before = {cap: _hooks.evidence(ctx, mat, r, cap) for cap in (0, 1)}
+    assert before[0] == mat.evidence(r)
+    for row, cap in ((200, 0), (400, 1), (767, 1)):          # padding rows of the first trip, the second and the third
+        assert not mask[row] and (cap == 0 or row // 256 == {400: 1, 767: 2}[row])
+        bad = good.copy()
+        bad[row, row] = 2.0
+        _hooks.mat_raw(ctx, mat, bad)
+        with pytest.raises(LpgpError, match="padding row of the factor"):
+            _hooks.evidence(ctx, mat, r, cap)
+        with pytest.raises(LpgpError, match="padding row of the factor"):
+            mat.evidence(r)
+        _hooks.mat_raw(ctx, mat, good)
+        assert _hooks.evidence(ctx, mat, r, cap) == before[cap], "the call after the entry was restored returns other bits"
+    assert mat.evidence(r) == before[0]

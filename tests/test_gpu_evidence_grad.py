@@ -249,17 +249,7 @@ def test_grid_block_of_a_flagged_descriptor(lp, ctx):
 
 
 # ---- the dense inverse ----------------------------------------------------------------------------------------------------------
-_hooks.lib.lpgp_test_mat_raw.restype = C.c_int
-_hooks.lib.lpgp_test_mat_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
-
-
-def mat_raw(ctx, mat, values=None):
-    """The padded storage of a matrix (pn x pn, element (r, c) at [r, c]); `values`: overwrite it."""
-    from linpde_gp_amd._lib import as_pd, check
-    pn = mat.padded_n
-    buf = np.empty((pn, pn)) if values is None else np.ascontiguousarray(values.T, dtype=np.double)       # column-major on the device
-    check(_hooks.lib.lpgp_test_mat_raw(ctx._h, mat._h, 0 if values is None else 1, as_pd(buf)), "lpgp_test_mat_raw")
-    return buf.T
+mat_raw = _hooks.mat_raw
 
 
 def _refined_inverse(G):
@@ -287,27 +277,11 @@ def _value_chain(lp, sizes, seed, noise=1e-2):
     return u, ogp.gram(INV_KERNEL, blocks), ogp.residual(blocks)
 
 
-@pytest.mark.parametrize("sizes", [(200, 317), (129,)], ids=["200+317", "129"])
-def test_inverse_against_lapack(lp, ctx, sizes):
-    """`inverse()`: the lower triangle against `numpy.linalg.inv` of the oracle's Gram matrix (Matern-5/2, noise 1e-2), relative to
-    max |G^-1|, within 4 x LAPACK's own distance from the inverse refined with long-double residuals; the padding rows are the
-    identity's; the factor is bitwise unchanged."""
-    u, G, r = _value_chain(lp, sizes, seed=31)
-    u._check_current()
-    mat = u._state.mat
-    before = mat.todense("factor")
-    ginv = mat.inverse()
-    assert np.array_equal(mat.todense("factor"), before)
-    got = ginv.todense()
-    lapack, exact = _refined_inverse(G)
-    scale = float(np.max(np.abs(exact)))
-    tri = np.tril_indices(len(G))
-    e_lap = float(np.max(np.abs(lapack[tri] - exact[tri]))) / scale
-    e_dev = float(np.max(np.abs(got[tri] - exact[tri]))) / scale
-    print(f"inverse {sizes}: cond2 {np.linalg.cond(G):.2e}  device {e_dev:.2e}, LAPACK {e_lap:.2e} of max |G^-1| from the refined inverse")
-    assert np.linalg.cond(G) < 1e6
-    assert e_dev <= 4.0 * e_lap
-    # padded layout: every block padded to a multiple of 128 with the identity
+INVERSE_PANELS = (128, 256, 384, 4096)          # option "inverse_diag_panel": 384 does not divide 640, the last panel is short
+
+
+def _check_inverse_padding(ctx, ginv, got, sizes):
+    """The padded layout of an inverse: every block padded to a multiple of 128 with the identity."""
     raw = mat_raw(ctx, ginv)
     pn, off = raw.shape[0], 0
     assert pn == sum(-(-n // 128) * 128 for n in sizes)
@@ -322,10 +296,143 @@ def test_inverse_against_lapack(lp, ctx, sizes):
     assert np.array_equal(low[logical][:, logical], np.tril(got))
 
 
+@pytest.mark.parametrize("sizes", [(200, 317), (129,)], ids=["200+317", "129"])
+def test_inverse_against_lapack(lp, ctx, sizes):
+    """`inverse()`: the lower triangle against `numpy.linalg.inv` of the oracle's Gram matrix (Matern-5/2, noise 1e-2), relative to
+    max |G^-1|, within 4 x LAPACK's own distance from the inverse refined with long-double residuals; the padding rows are the
+    identity's; the factor is bitwise unchanged.  At the default column panel (4096: one panel) and at 128, 256 and 384 columns: W = L^-1
+    then comes panel by panel, each panel after the first solved against a trailing sub-factor into W + j0 (pn + 1) with leading
+    dimension pn (five, three and two panels at 640 padded rows, the last of 384 short; one and two at 256)."""
+    from _backward import restored
+    u, G, r = _value_chain(lp, sizes, seed=31)
+    u._check_current()
+    mat = u._state.mat
+    before = mat.todense("factor")
+    lapack, exact = _refined_inverse(G)
+    scale = float(np.max(np.abs(exact)))
+    tri = np.tril_indices(len(G))
+    e_lap = float(np.max(np.abs(lapack[tri] - exact[tri]))) / scale
+    assert np.linalg.cond(G) < 1e6
+    assert ctx.get_option("inverse_diag_panel") == 4096
+    with restored(ctx, ("inverse_diag_panel",)) as apply:
+        for panel in INVERSE_PANELS[::-1]:
+            apply({"inverse_diag_panel": panel})
+            ginv = mat.inverse()
+            assert np.array_equal(mat.todense("factor"), before)
+            got = ginv.todense()
+            e_dev = float(np.max(np.abs(got[tri] - exact[tri]))) / scale
+            print(f"inverse {sizes} panel {panel}: cond2 {np.linalg.cond(G):.2e}  device {e_dev:.2e}, LAPACK {e_lap:.2e} of max |G^-1| from the refined "
+                  f"inverse: ratio {e_dev / e_lap:.2f}")
+            assert e_dev <= 4.0 * e_lap, (panel, e_dev, e_lap)
+            _check_inverse_padding(ctx, ginv, got, sizes)
+    assert ctx.get_option("inverse_diag_panel") == 4096
+
+
+INVERSE_PROBE_RATIO = 1.61       # nine tile rows: probe residual of the device's inverse <= this x LAPACK's (twice the largest measured, 0.804: MEASUREMENTS.md)
+
+
+def _probe_residual(Gl, norm_G, X, probes):
+    """max over the probes v of || v - G (X v) ||_inf / (|| G ||_inf || X ||_inf || v ||_inf), the products in long double."""
+    Xl = X.astype(np.longdouble)
+    norm_X = float(np.max(np.sum(np.abs(Xl), axis=1)))
+    worst = 0.0
+    for v in probes:
+        vl = v.astype(np.longdouble)
+        res = vl - Gl @ (Xl @ vl)
+        worst = max(worst, float(np.max(np.abs(res))) / (norm_G * norm_X * float(np.max(np.abs(v)))))
+    return worst
+
+
+def test_inverse_of_nine_tile_rows(lp, ctx):
+    """One block of 1100 rows, 1152 padded: nine tile rows, so W^T W runs in bands of 4, 4 and 1 tile columns -- a full-width band at
+    a nonzero offset, which the 640 padded rows above (bands of 4 and 1) never have -- at one panel (4096) and at 256 columns (five
+    panels, the last of 128).  The refined long-double inverse costs a minute at this size; the measure is the residual on 8 seeded
+    probes, max_v || v - G (X v) ||_inf / (|| G ||_inf || X ||_inf || v ||_inf) with the products in long double, against the same
+    measure of `numpy.linalg.inv(G)` on the same G and probes: at most INVERSE_PROBE_RATIO x LAPACK's.  Padding and factor as above."""
+    from _backward import restored
+    sizes = (1100,)
+    u, G, r = _value_chain(lp, sizes, seed=32)
+    u._check_current()
+    mat = u._state.mat
+    assert mat.padded_n == 1152
+    before = mat.todense("factor")
+    assert np.linalg.cond(G) < 1e6
+    Gl = G.astype(np.longdouble)
+    norm_G = float(np.max(np.sum(np.abs(G), axis=1)))
+    probes = np.random.default_rng(1100).standard_normal((8, 1100))
+    e_lap = _probe_residual(Gl, norm_G, np.linalg.inv(G), probes)
+    with restored(ctx, ("inverse_diag_panel",)) as apply:
+        for panel in (256, 4096):
+            apply({"inverse_diag_panel": panel})
+            ginv = mat.inverse()
+            assert np.array_equal(mat.todense("factor"), before)
+            got = ginv.todense()
+            assert np.array_equal(got, got.T)
+            e_dev = _probe_residual(Gl, norm_G, got, probes)
+            print(f"inverse (1100,) panel {panel}: probe residual device {e_dev:.3e}, LAPACK {e_lap:.3e}: ratio {e_dev / e_lap:.3f}")
+            assert e_dev <= INVERSE_PROBE_RATIO * e_lap, (panel, e_dev, e_lap)
+            _check_inverse_padding(ctx, ginv, got, sizes)
+
+
+def _exact_contraction(ctx, mat, ginv, dG, sizes, caps, diag_caps):
+    """Integer operands (tests/_exact_operands.py: integers of [-4, 4] in `ginv`, `dG`, `r` and `v`, NaN and 1e30 in every masked
+    position) written over the storage of `ginv` and `dG`; `mat` is the factored identity, so w = r exactly.  Every product and every
+    partial sum of evidence_grad_partial_kernel / evidence_grad_final_kernel is then an integer below 2^53: q and t EQUAL the int64
+    sums whatever the launch -- `caps`: at most that many workgroups (0: the public call's launch) through `lpgp_test_evidence_grad`,
+    `diag_caps` likewise for the diagonal form with v on the last block, scalar = 0."""
+    import _exact_operands as ex
+    raw, r, v, q_ref, t_ref, diag = ex.contraction_operands(sizes, seed=4000 + sum(sizes))
+    n = r.size
+    assert ex.contraction_partial_sum_bound(n) < ex.EXACT_LIMIT and mat.n == n
+    mat_raw(ctx, ginv, raw["ginv"])
+    mat_raw(ctx, dG, raw["dG"])
+    rf = r.astype(np.double)
+    assert np.array_equal(mat.solve_weights(rf), rf), "a solve against the identity factor does not return r exactly"
+    for cap in caps:
+        q, t = _hooks.evidence_grad(ctx, mat, ginv, dG, rf, cap)
+        print(f"exact contraction {sizes} cap {cap}: q {q!r} (int64 {q_ref}), t {t!r} (int64 {t_ref})")
+        assert (q, t) == (float(q_ref), float(t_ref)), (cap, q, t, q_ref, t_ref)
+        assert _hooks.evidence_grad(ctx, mat, ginv, dG, rf, cap) == (q, t)
+    assert mat.evidence_grad(ginv, dG, rf) == (float(q_ref), float(t_ref))
+    bi, lo = len(sizes) - 1, sum(sizes[:-1])
+    vb = v[lo:]
+    qd_ref, td_ref = int(np.sum(vb * r[lo:] * r[lo:])), int(np.sum(vb * diag[lo:]))
+    assert qd_ref != 0 and td_ref != 0
+    for cap in diag_caps:
+        qd, td = _hooks.evidence_grad_diag(ctx, mat, ginv, bi, rf, v=vb.astype(np.double), scalar=0.0, max_wgs=cap)
+        print(f"exact diagonal form {sizes} cap {cap}: q {qd!r} (int64 {qd_ref}), t {td!r} (int64 {td_ref})")
+        assert (qd, td) == (float(qd_ref), float(td_ref)), (cap, qd, td, qd_ref, td_ref)
+    assert mat.evidence_grad_diag(ginv, bi, rf, v=vb.astype(np.double), scalar=0.0) == (float(qd_ref), float(td_ref))
+
+
+def test_contraction_second_trip_of_the_final_kernel(ctx):
+    """Blocks of 130 + 300 + 700 rows: 1408 padded rows, 352 workgroups of four columns -- more than the 256 threads of
+    evidence_grad_final_kernel, whose loop over the partials takes its second trip (pn > 1024; every other case of this file has
+    pn <= 640).  Integer operands, exact; a cap of 1 for the other extreme (352 columns per wave)."""
+    import _exact_operands as ex
+    from linpde_gp_amd import _lib
+    sizes = (130, 300, 700)
+    mat, ginv, dG = ex.identity_factored(ctx, sizes), ex.cleared(ctx, sizes), ex.cleared(ctx, sizes)
+    assert mat.padded_n == 1408 and -(-mat.padded_n // 4) == 352 > 256
+    _exact_contraction(ctx, mat, ginv, dG, sizes, caps=(0, 1), diag_caps=(0, 1))
+    # the hooks refuse what the public calls refuse
+    r = np.ones(mat.n)
+    with pytest.raises(_lib.LpgpError, match="must not be factored"):
+        _hooks.evidence_grad(ctx, mat, ginv, mat, r, 1)
+    with pytest.raises(_lib.LpgpError, match=r"not \(fully\) factored"):
+        _hooks.evidence_grad(ctx, dG, ginv, dG, r, 1)
+    with pytest.raises(_lib.LpgpError, match="block layout"):
+        _hooks.evidence_grad_diag(ctx, mat, ex.cleared(ctx, (1130,)), 2, r, max_wgs=1)
+    with pytest.raises(_lib.LpgpError, match="bad block"):
+        _hooks.evidence_grad_diag(ctx, mat, ginv, 3, r, max_wgs=1)
+
+
 def test_contraction_kernel_alone(lp, ctx):
     """`lpgp_mat_evidence_grad` on seeded random lower triangles in the 200 + 317 layout, NaN and 1e30 in every padding row and
     column and above the diagonal: G = I (so w = r exactly), result = `math.fsum` of the logical terms within n eps sum |terms|,
-    two calls bit-identical.  A padding leak shows here; so does the diagonal / off-diagonal weight."""
+    two calls bit-identical.  A padding leak shows here; so does the diagonal / off-diagonal weight.  Then integer operands under
+    the same garbage (`_exact_contraction`): q and t equal the int64 sums for the public launch (one column per wave) and for 1 and 3
+    workgroups (160 and 54 columns per wave, the `j += nwaves` loop that otherwise repeats only above 8192 padded rows)."""
     from linpde_gp_amd import _engine
     cf = lp.randprocs.covfuncs
     sizes = (200, 317)
@@ -380,6 +487,8 @@ def test_contraction_kernel_alone(lp, ctx):
     vv = np.concatenate([np.zeros(200), v + 0.25])
     assert abs(qd - math.fsum(vv * r * r)) <= n * EPS * np.sum(np.abs(vv * r * r))
     assert abs(td - math.fsum(vv * np.diag(A))) <= n * EPS * np.sum(np.abs(vv * np.diag(A)))
+    # integer operands under the same garbage: exact, for one column per wave (uncapped: 160 workgroups) and for 160 and 54 columns per wave
+    _exact_contraction(ctx, mat, ginv, dG, sizes, caps=(0, 1, 3), diag_caps=(0, 1))
     # refusals: another layout, a factored derivative
     from linpde_gp_amd import _lib
     with pytest.raises(_lib.LpgpError, match="block layout"):

@@ -124,11 +124,11 @@ def test_factor_matmul_entrywise_bound(lp, n):
     `(n + 2) u (|tril(L)| |Z| + |shift|)` (reference product in extended precision), for 1, 5, 128 and 130 columns, with and
     without a shift; row 0 is `shift[0] + L[0, 0] Z[0]` to two roundings; two calls agree bit for bit.
 
-    A further case one would want -- the same bound on a matrix whose storage ABOVE the diagonal tiles was filled with large entries
-    by an assembly before `add_dense` -- cannot be built that way and is dropped: no assembly ever writes a tile above the
-    diagonal of a diagonal block (`lower_only` skips them in every assembly kernel, `lpgp_mat_add_dense` adds to the lower
-    part, and the symmetric `what = 0` copy-out mirrors the lower triangle, so it cannot show them either).  The one writer
-    of those tiles is `lpgp_mat_sub_inner`; `test_sub_inner_then_product_ignores_the_upper_tiles` covers that route."""
+    The case with large entries in the storage ABOVE the diagonal -- inside the diagonal tiles and in the whole tiles above them -- is
+    built in test_gpu_trmm_chunks.py: no assembly writes there (`lower_only` skips those tiles, `lpgp_mat_add_dense` adds to the
+    lower part), but the hook `lpgp_test_mat_raw` overwrites the storage of a factored matrix as it is, and the product of integer
+    operands under NaN and 1e30 is held to exact equality there, at every chunk size of the work split.  The one writer of those
+    tiles in the product, `lpgp_mat_sub_inner`, is covered by `test_sub_inner_then_product_ignores_the_upper_tiles`."""
     rng = np.random.default_rng(100 + n)
     B = rng.standard_normal((n, n))
     A = B @ B.T + n * np.eye(n)
