@@ -61,6 +61,7 @@ typedef struct lpgp_mat lpgp_mat;   /* device-resident SPD matrix -> Cholesky fa
 typedef struct lpgp_rhs lpgp_rhs;   /* device-resident n x m block of right-hand sides    */
 typedef struct lpgp_dvec lpgp_dvec; /* device-resident n x m block of plain vectors (matrix-free path: no Gram matrix behind it) */
 typedef struct lpgp_pcg lpgp_pcg;   /* state of preconditioned conjugate gradients on such blocks */
+typedef struct lpgp_mix lpgp_mix;   /* device-resident stencil table of one block of matrix observations, uploaded once */
 
 /* One term  coef * prod_d  d^{n0[d]}/dx_d^{n0[d]}  d^{n1[d]}/dx'_d^{n1[d]}  k_d(x_d, x'_d)
  * of `TensorProduct_LinDiffOp_LinDiffOp.__init__`
@@ -346,7 +347,37 @@ int  lpgp_cross_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_
                                   const double* w_host, int32_t A,
                                   const lpgp_pts* X_obs, const lpgp_pts* X_test,
                                   lpgp_rhs* rhs, const lpgp_mat* mat, int32_t bi);
-/* The same for ALL observation blocks in one call (round 5): blocks[bi] = {descriptor, observation points} of block bi (kd == NULL:
+/* ---- observations through a matrix,  A @ L  (the reference's `CompositeLinearFunctional(linop=A, ...)`, linfunctls/_arithmetic.py:
+ *      92-174): cell averages and integrals by quadrature, sensor averages, finite differences of observed values, any sparse
+ *      linear mixing of point functionals.  A block of q rows over n points is a stencil table in ELL form: indices idx[q][S]
+ *      into the point set, weights w[q][S], row width 1 <= S <= LPGP_MAXS; a row shorter than S is padded with weight 0.0 and the
+ *      row's first index.  Block entry (r, c) is
+ *        sum_{a < S0} sum_{b < S1}  (w0[r][a] * w1[c][b]) * (kd)(X0[idx0[r][a]], X1[idx1[c][b]]),
+ *      evaluated by ONE fused launch in exactly this order (a outer, b inner, first term a product, the rest fmas; no atomics:
+ *      the same bits on every call): S0 * S1 kernel evaluations per entry, no n x n temporary.  A side without a table is plain
+ *      (S = 1, weight 1, index = row); with both sides plain the block is bit-identical to lpgp_gram_assemble's generic kernel.
+ *      Takes every descriptor the generic kernel takes; tiles of a compactly supported kernel are evaluated, not skipped (a row
+ *      is a stencil over points anywhere in the set).  Single GPU. */
+#define LPGP_MAXS 32                    /* row width of a stencil table: holds 5 x 5 and 3 x 3 x 3 tensor Gauss rules */
+/* idx_host, w_host: q x S, C-order, borrowed for the call; every index is checked against npts on the host.  Refused: S outside
+ * 1 .. LPGP_MAXS, an index outside 0 .. npts - 1, a NULL pointer, q < 1.  The handle is a device resource like lpgp_pts. */
+int  lpgp_mix_create(lpgp_ctx* ctx, int64_t q, int32_t S, const int32_t* idx_host, const double* w_host, int64_t npts, lpgp_mix** out);
+int  lpgp_mix_destroy(lpgp_mix* mix);
+/* block (bi, bj), bi >= bj, of q_bi x q_bj rows: M0 / M1 == NULL means that side is plain and its rows are the points of X0 / X1.
+ * bi == bj: X1 == NULL and M1 == NULL, M0 serves both sides and only the lower triangle is written.  Asynchronous like
+ * lpgp_gram_assemble.  Refused, with the matrix untouched: a table whose q does not match the block (a plain side: X->n), a table
+ * made for another npts than its point set has, a dimension mismatch, a block that is already factored, a strict-prefix view
+ * (lpgp_mat_set_view), a handle of another context, a context inside a multi-GPU job.  Conditioning on such a block goes
+ * through the separate calls, as for weighted blocks: lpgp_mat_add_block(q), one assembly per block of the row,
+ * lpgp_mat_add_diag / lpgp_mat_add_dense, lpgp_potrf. */
+int  lpgp_gram_assemble_mixed(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups,
+                              const lpgp_pts* X0, const lpgp_mix* M0, const lpgp_pts* X1, const lpgp_mix* M1,
+                              lpgp_mat* mat, int32_t bi, int32_t bj);
+/* rows of block bi of K_Xx  <-  sum_a w[r][a] (kd)(X_obs[idx[r][a]], x_test[c]): the cross-covariance of such a block (M == NULL: the
+ * plain block, bit-identical to lpgp_cross_assemble's generic kernel).  The test side is plain. */
+int  lpgp_cross_assemble_mixed(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, const lpgp_pts* X_obs, const lpgp_mix* M,
+                               const lpgp_pts* X_test, lpgp_rhs* rhs, const lpgp_mat* mat, int32_t bi);
+/* lpgp_cross_assemble for ALL observation blocks in one call (round 5): blocks[bi] = {descriptor, observation points} of block bi (kd == NULL:
  * the block has no cross-covariance with the prediction points, its rows stay zero).  Consecutive blocks that share a descriptor
  * -- value observations on several boundary pieces -- are assembled by ONE launch (a table of point sets in the kernel
  * arguments), as lpgp_mat_condition does for a block row of the Gram matrix (_conditional.py:140-153, :270).        */

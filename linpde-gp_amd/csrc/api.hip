@@ -8,6 +8,7 @@
 #include <rccl/rccl.h>
 
 #include "lpgp_internal.h"
+#include "mix_table.h"
 
 namespace lpgp {
 
@@ -926,6 +927,82 @@ int lpgp_gram_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_t 
                            Bj.poff, mat_layout(ctx));
 }
 
+// ---- observations through a matrix: stencil tables (mix_table.h) and their assembly (assemble_mixed_kernel) --------------------
+int lpgp_mix_create(lpgp_ctx* ctx, int64_t q, int32_t S, const int32_t* idx_host, const double* w_host, int64_t npts, lpgp_mix** out) {
+  static_assert(MIX_MAXS == LPGP_MAXS, "the row width of a stencil table");
+  LPGP_CHECK(ctx && out, "lpgp_mix_create: null argument");
+  LPGP_DEVICE(ctx);
+  LPGP_CHECK(!ctx->distributed(), "lpgp_mix_create: single GPU only (this context has joined a multi-GPU job)");
+  MixTable t;
+  std::string err;
+  LPGP_TRY(refused(mix_table_build(q, S, idx_host, w_host, npts, &t, &err), "lpgp_mix_create: " + err));
+  const size_t w_bytes = t.w.size() * sizeof(double), idx_bytes = t.idx.size() * sizeof(int32_t);
+  DevBuf buf;
+  LPGP_TRY(DevBuf::raw(w_bytes + idx_bytes, &buf));
+  {
+    StreamDrain drain{ctx->s_main};                 // (behind `t` and `buf`: the copies out of `t` have landed before either goes)
+    LPGP_HIP(hipMemcpyAsync(buf.as<char>(), t.w.data(), w_bytes, hipMemcpyHostToDevice, ctx->s_main));
+    LPGP_HIP(hipMemcpyAsync(buf.as<char>() + w_bytes, t.idx.data(), idx_bytes, hipMemcpyHostToDevice, ctx->s_main));
+    LPGP_TRY(drain.wait());
+  }
+  std::unique_ptr<lpgp_mix> m(new lpgp_mix());
+  m->ctx = ctx;
+  m->q = t.q;
+  m->S = t.S;
+  m->npts = t.npts;
+  m->w = (double*)buf.release();
+  m->idx = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(m->w) + w_bytes);
+  *out = m.release();
+  return 0;
+}
+
+int lpgp_mix_destroy(lpgp_mix* m) {
+  if (!m) return 0;
+  (void)hipSetDevice(m->ctx->device);
+  (void)hipFree(m->w);                              // (waits for the device: no kernel still reads the table)
+  delete m;
+  return 0;
+}
+
+// what the mixed assemblies ask of one side: points of this context, and a table (if any) of this context, made for these points
+static int mix_side(const char* fn, const lpgp_ctx* ctx, const lpgp_pts* X, const lpgp_mix* M, const char* side, int64_t* rows) {
+  LPGP_CHECK(X->ctx == ctx, "%s: the %s points belong to another context", fn, side);
+  if (M) {
+    LPGP_CHECK(M->ctx == ctx, "%s: the %s stencil table belongs to another context", fn, side);
+    LPGP_CHECK(M->npts == X->n, "%s: the %s stencil table was made for %lld points, the point set has %lld", fn, side, (long long)M->npts,
+               (long long)X->n);
+  }
+  *rows = M ? M->q : X->n;
+  return 0;
+}
+
+int lpgp_gram_assemble_mixed(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, const lpgp_pts* X0, const lpgp_mix* M0, const lpgp_pts* X1,
+                             const lpgp_mix* M1, lpgp_mat* mat, int32_t bi, int32_t bj) {
+  static const char* fn = "lpgp_gram_assemble_mixed";
+  LPGP_CHECK(ctx && kd && X0 && mat, "%s: null argument", fn);
+  LPGP_DEVICE(ctx);
+  LPGP_CHECK(!ctx->distributed(), "%s: single GPU only (this context has joined a multi-GPU job)", fn);
+  LPGP_CHECK(mat->ctx == ctx, "%s: the matrix belongs to another context", fn);
+  LPGP_MAT_ALIVE(mat, "lpgp_gram_assemble_mixed");
+  LPGP_CHECK(mat->hidden.empty(), "%s: a strict prefix of the blocks is in view (lpgp_mat_set_view)", fn);
+  LPGP_TRY(gram_target(fn, mat, bi, bj, X1, "X1"));
+  const bool sym = (bi == bj);
+  LPGP_CHECK(!sym || M1 == nullptr, "%s: M1 must be NULL for a diagonal block (M0 serves both sides)", fn);
+  const lpgp_pts* Xc = sym ? X0 : X1;
+  const lpgp_mix* Mc = sym ? M0 : M1;
+  int64_t rows = 0, cols = 0;
+  LPGP_TRY(mix_side(fn, ctx, X0, M0, "row", &rows));
+  LPGP_TRY(mix_side(fn, ctx, Xc, Mc, "column", &cols));
+  const lpgp_block& Bi = mat->blocks[bi];
+  const lpgp_block& Bj = mat->blocks[bj];
+  LPGP_CHECK(rows == Bi.n, "%s: the row side has %lld rows, block %d has %lld", fn, (long long)rows, bi, (long long)Bi.n);
+  LPGP_CHECK(cols == Bj.n, "%s: the column side has %lld rows, block %d has %lld", fn, (long long)cols, bj, (long long)Bj.n);
+  LPGP_CHECK(Xc->d == X0->d && kd[0].d == X0->d, "%s: dimension mismatch: the descriptor has d=%d, the points d=%d and d=%d", fn, kd[0].d, X0->d, Xc->d);
+  DevDesc desc;
+  LPGP_TRY(lower_kdesc(kd, ngroups, &desc));
+  return assemble_mixed(ctx, ctx->s_main, desc, X0, M0, Xc, Mc, sym, mat->a, mat->lr_cap, Bi.poff, Bj.poff, mat_layout(ctx));
+}
+
 int lpgp_kron_fits(const lpgp_kdesc* kd, int32_t ngroups) { return kron_fits(kd, ngroups) ? 1 : 0; }
 
 int lpgp_gram_assemble_grid(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, const lpgp_pts* const* F0,
@@ -1522,6 +1599,27 @@ int lpgp_cross_assemble_weighted(lpgp_ctx* ctx, const lpgp_wpair* pairs, int32_t
   }
   if (rc == 0 && bi < (int)rhs->assembled.size()) rhs->assembled[bi] = 1;
   return rc;
+}
+
+int lpgp_cross_assemble_mixed(lpgp_ctx* ctx, const lpgp_kdesc* kd, int32_t ngroups, const lpgp_pts* X_obs, const lpgp_mix* M,
+                              const lpgp_pts* X_test, lpgp_rhs* rhs, const lpgp_mat* mat, int32_t bi) {
+  static const char* fn = "lpgp_cross_assemble_mixed";
+  LPGP_CHECK(ctx && kd && X_obs, "%s: null argument", fn);
+  LPGP_DEVICE(ctx);
+  LPGP_CHECK(!ctx->distributed(), "%s: single GPU only (this context has joined a multi-GPU job)", fn);
+  LPGP_TRY(cross_target(fn, X_test, rhs, mat, bi, 1));
+  LPGP_CHECK(rhs->ctx == ctx && mat->ctx == ctx && X_test->ctx == ctx, "%s: a handle belongs to another context", fn);
+  int64_t rows = 0;
+  LPGP_TRY(mix_side(fn, ctx, X_obs, M, "observation", &rows));
+  const lpgp_block& B = mat->blocks[bi];
+  LPGP_CHECK(rows == B.n, "%s: the observation side has %lld rows, block %d has %lld", fn, (long long)rows, bi, (long long)B.n);
+  LPGP_CHECK(X_obs->d == X_test->d && kd[0].d == X_obs->d, "%s: dimension mismatch", fn);
+  DevDesc desc;
+  LPGP_TRY(lower_kdesc(kd, ngroups, &desc));
+  int rc = 0;
+  if (X_test->n > 0) rc = assemble_mixed(ctx, ctx->s_main, desc, X_obs, M, X_test, nullptr, false, rhs->v, rhs->ld, B.poff, 0, Layout2D());
+  if (rc == 0 && bi < (int)rhs->assembled.size()) rhs->assembled[bi] = 1;
+  return rc;       // asynchronous (see lpgp_gram_assemble)
 }
 
 int lpgp_cross_assemble_row(lpgp_ctx* ctx, const lpgp_cross_block* blocks, int32_t nblocks, const lpgp_pts* X_test, lpgp_rhs* rhs,

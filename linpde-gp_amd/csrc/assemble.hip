@@ -307,6 +307,121 @@ __global__ __launch_bounds__(256) void assemble_weighted_kernel(WeightArgs wa, A
 }
 
 // ---------------------------------------------------------------------------------------
+// Observations through a matrix,  A0 @ L0  against  A1 @ L1  (DESIGN.md section 5f): with the rows of A0, A1 as stencil tables
+// (mix_table.h: ELL, slot-major on the device) block entry (r, c) is
+//   sum_{a < S0} sum_{b < S1}  (w0[r][a] * w1[c][b]) * k(X0[idx0[r][a]], X1[idx1[c][b]]),
+// summed in exactly this order -- a outer, b inner, the first term a product and the rest fmas (the weighted kernel's rule: it
+// keeps the sign of a zero) -- in registers, one store per entry: no atomics, no pre-cleared output, the same bits on every
+// call.  A side without a table is plain: S = 1, weight 1.0, index = row; with both sides plain an entry is (1.0 * 1.0) * v == v,
+// the block assemble_kernel writes.  The tile code is assemble_kernel's (64 x 64 tile, lane = row, wave = 16-column slab, AEK
+// entries per pass, lower_only, cyc_local).  A lane gathers its row point per a from global memory (S0 * D cached loads per
+// pass against S0 * S1 * AEK evaluations); the column side goes through LDS in chunks of MIX_CH<D> stencil slots: per pass
+// each wave stages the AEK columns it is about to evaluate -- point and weight of every slot of the chunk, one (slot, column)
+// item per lane -- so a chunk costs at most 24 KB whatever S1 is (several workgroups per CU of 160 KB).  With one chunk (S1 <= MIX_CH) it is staged once per
+// pass, with more it is staged again for every a, since the order of summation puts the chunk loop inside the a loop: one
+// gather of D + 1 words per lane against MIX_CH * AEK evaluations.
+// EV_COMPACT: Wendland tiles are simply evaluated.  The reach test of assemble_kernel works on a tile's own points; here a
+// tile's rows and columns are stencils over points anywhere in the set, so this kernel skips no tiles -- an entry out of reach
+// is a sum of exact zeros.
+// ---------------------------------------------------------------------------------------
+template <int D>
+struct MixChunk {
+  static constexpr int value = D <= 2 ? 16 : 8;   // stencil slots per LDS chunk
+};
+
+struct MixArgs {
+  const int32_t* idx0;            // [S0][n0] row stencils, nullptr: plain
+  const double* w0;
+  const int32_t* idx1;            // [S1][n1] column stencils, nullptr: plain
+  const double* w1;
+  int32_t S0, S1;
+};
+
+template <int D, int VAR = EV_PLAIN>
+__global__ __launch_bounds__(256) void assemble_mixed_kernel(const DevDesc* __restrict__ desc, MixArgs m, AsmArgs a) {
+  constexpr int CH = MixChunk<D>::value;
+  __shared__ double sx1[CH][D][AT];
+  __shared__ double sw1[CH][AT];
+  __shared__ __attribute__((aligned(16))) double s_exp[2 * EXP_TAB_N];
+  const int tr = blockIdx.x % a.tiles_r;
+  const int tc = blockIdx.x / a.tiles_r;
+  const int64_t r0 = (int64_t)tr * AT, c0 = (int64_t)tc * AT;
+  if (a.lower_only && c0 > r0 + AT - 1) return;
+  const int64_t lrow0 = cyc_local(a.lay.rows, a.row_off + r0), lcol0 = cyc_local(a.lay.cols, a.col_off + c0);
+  if (lrow0 < 0 || lcol0 < 0) return;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t row = r0 + lane;
+  const bool row_ok = row < a.n0;
+  s_exp[threadIdx.x] = g_exp_table[threadIdx.x], s_exp[threadIdx.x + 256] = g_exp_table[threadIdx.x + 256];
+  const ExpTab etab{s_exp};
+  const int S0 = m.S0, S1 = m.S1;                  // (uniform: every wave of the workgroup runs the same trips, barriers included)
+  const bool restage = S1 > CH;
+  // the staging item of this lane: slot ss of the chunk, column se of the pass
+  const int ss = lane / AEK, se = lane - ss * AEK;
+#pragma unroll 1
+  for (int pass = 0; pass < 16 / AEK; ++pass) {
+    const int cb = w * 16 + pass * AEK;
+    double acc[AEK];
+#pragma unroll
+    for (int e = 0; e < AEK; ++e) acc[e] = 0.0;
+#pragma unroll 1
+    for (int sa = 0; sa < S0; ++sa) {
+      double xr[D], wrow = 0.0;
+      {
+        int64_t i = row;
+        if (row_ok && m.idx0) { i = m.idx0[(int64_t)sa * a.n0 + row]; wrow = m.w0[(int64_t)sa * a.n0 + row]; }
+        else if (row_ok) wrow = 1.0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) xr[j] = row_ok ? a.x0[j * a.n0_pad + i] : 0.0;
+      }
+#pragma unroll 1
+      for (int b0 = 0; b0 < S1; b0 += CH) {
+        if (restage || sa == 0) {
+          __syncthreads();                             // (the table of exponentials on the first trip; the chunk's readers afterwards)
+          if (ss < CH) {
+            const int sb = b0 + ss;
+            const int64_t col = c0 + cb + se;
+            const bool ok = sb < S1 && col < a.n1;
+            int64_t i = col;
+            double wc = ok ? 1.0 : 0.0;
+            if (ok && m.idx1) { i = m.idx1[(int64_t)sb * a.n1 + col]; wc = m.w1[(int64_t)sb * a.n1 + col]; }
+#pragma unroll
+            for (int j = 0; j < D; ++j) sx1[ss][j][cb + se] = ok ? a.x1[j * a.n1_pad + i] : 0.0;
+            sw1[ss][cb + se] = wc;
+          }
+          __syncthreads();
+        }
+        const int nb = S1 - b0 < CH ? S1 - b0 : CH;
+#pragma unroll 1
+        for (int s = 0; s < nb; ++s) {
+          double dx[D][AEK], res[AEK];
+#pragma unroll
+          for (int j = 0; j < D; ++j)
+#pragma unroll
+            for (int e = 0; e < AEK; ++e) dx[j][e] = xr[j] - sx1[s][j][cb + e];
+          eval_entries_var<VAR, D, AEK>(desc, dx, res, etab);
+          if (sa == 0 && b0 + s == 0) {                // (a product, not fma(w, v, +0.0): keeps the sign of a zero entry)
+#pragma unroll
+            for (int e = 0; e < AEK; ++e) acc[e] = (wrow * sw1[s][cb + e]) * res[e];
+          } else {
+#pragma unroll
+            for (int e = 0; e < AEK; ++e) acc[e] = fma(wrow * sw1[s][cb + e], res[e], acc[e]);
+          }
+        }
+      }
+    }
+    if (row_ok) {
+#pragma unroll
+      for (int e = 0; e < AEK; ++e) {
+        const int64_t c = c0 + cb + e;
+        if (c < a.n1) a.out[(lrow0 + lane) + (lcol0 + cb + e) * a.ld] = acc[e];
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // The common descriptor shapes, specialised (round 3).  assemble_kernel above is written once for every D <= 4, any
 // number of groups, parity classes and degrees: its evaluation is a nest of tiny run-time loops (4 FMAs between a scalar
 // compare-and-branch per coefficient, scalar loads of group parameters per pass), and on the 4096 x 16384 cross-covariance
@@ -847,6 +962,33 @@ int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs
   }
   LPGP_HIP(hipGetLastError());
   return drain.wait();
+}
+
+// One block of matrix observations (assemble_mixed_kernel).  M0 / M1: the stencil tables of the row / column side, nullptr for
+// a plain side, whose rows are the points of X0 / X1.  sym: the column side is the row side (X1 == X0, M1 == M0), only tiles on
+// or below the diagonal are written.  The tables are resident, so nothing is borrowed and the launch is asynchronous like
+// launch_assemble; the lowering has happened before, so nothing here refuses after the launch.  Profiled as LPGP_K_ASSEMBLE
+// with 2 flops (the fma) per kernel evaluation, S0 * S1 evaluations and 8 bytes stored per entry.
+int assemble_mixed(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, const lpgp_pts* X0, const lpgp_mix* M0, const lpgp_pts* X1,
+                   const lpgp_mix* M1, bool sym, double* out, int64_t ld, int64_t row_off, int64_t col_off, const Layout2D& lay) {
+  const int64_t n0 = M0 ? M0->q : X0->n, n1 = M1 ? M1->q : X1->n;
+  const int d = X0->d;
+  LPGP_CHECK(dim_ok(d) && host_desc.d == d && X1->d == d, "assemble_mixed: d=%d", d);
+  LPGP_CHECK((!M0 || M0->npts == X0->n) && (!M1 || M1->npts == X1->n), "assemble_mixed: a stencil table does not belong to its point set");
+  const AsmJob job{X0->x, n0, X0->n_pad, X1->x, n1, X1->n_pad, row_off, col_off, sym ? 1 : 0};
+  AsmArgs a;
+  if (!asm_args(job, out, ld, lay, &a)) return 0;
+  MixArgs m;
+  m.idx0 = M0 ? M0->idx : nullptr; m.w0 = M0 ? M0->w : nullptr; m.S0 = M0 ? M0->S : 1;
+  m.idx1 = M1 ? M1->idx : nullptr; m.w1 = M1 ? M1->w : nullptr; m.S1 = M1 ? M1->S : 1;
+  const int var = desc_variant(host_desc);
+  const double entries = asm_entries(job);
+  const dim3 grid((unsigned)((int64_t)a.tiles_r * a.tiles_c));
+  return launch_staged(ctx, stream, host_desc, LPGP_K_ASSEMBLE, 2.0 * (double)m.S0 * (double)m.S1 * entries, 8.0 * entries, [&](const DevDesc* d_desc) {
+    dispatch_dim(d, false, var, [&](auto D, auto, auto V) {
+      hipLaunchKernelGGL((assemble_mixed_kernel<LPGP_CV(D), LPGP_CV(V)>), grid, dim3(256), 0, stream, d_desc, m, a);
+    });
+  });
 }
 
 bool assemble_same_fast(const DevDesc& p, const DevDesc& q) {

@@ -215,6 +215,16 @@ struct lpgp_pts {
   size_t bytes = 0;                // size of the allocation behind x
 };
 
+// The stencil table of one block of matrix observations (mix_table.h), resident: ONE allocation, weights first.
+struct lpgp_mix {
+  lpgp_ctx* ctx;
+  int64_t q;                       // rows of the block
+  int32_t S;                       // row width, 1 .. LPGP_MAXS
+  int64_t npts;                    // size of the point set the indices were checked against
+  double* w;                       // device, slot-major: w[s * q + r]
+  int32_t* idx;                    // device, behind w: idx[s * q + r]
+};
+
 struct lpgp_mat : lpgp::MatState {  // block table and factor state: mat_state.h
   lpgp_ctx* ctx = nullptr;
   int64_t cap = 0;                 // padded capacity of the GLOBAL matrix (multiple of TILE); single GPU: == leading dimension
@@ -560,6 +570,8 @@ struct AsmJob {
 int assemble_weighted(lpgp_ctx* ctx, hipStream_t stream, const lpgp_wpair* pairs, int npairs, const double* w0_host, int A0,
                       const double* w1_host, int A1, const lpgp_pts* X0, const lpgp_pts* X1, bool sym, double* out, int64_t ld,
                       int64_t row_off, int64_t col_off, const Layout2D& lay);
+int assemble_mixed(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, const lpgp_pts* X0, const lpgp_mix* M0, const lpgp_pts* X1,
+                   const lpgp_mix* M1, bool sym, double* out, int64_t ld, int64_t row_off, int64_t col_off, const Layout2D& lay);
 bool assemble_same_fast(const DevDesc& p, const DevDesc& q);
 int launch_assemble_batch(lpgp_ctx* ctx, hipStream_t stream, const DevDesc& host_desc, const AsmJob* jobs, int njobs, double* out, int64_t ld,
                           const Layout2D& lay);

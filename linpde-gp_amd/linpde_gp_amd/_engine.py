@@ -243,6 +243,32 @@ class Points:
             self._h = None
 
 
+MAXS = 32        # LPGP_MAXS: row width of a stencil table
+
+
+class Mix:
+    """Device-resident stencil table of one block of matrix observations (`lpgp_mix_create`): `idx`, `w` of shape (q, S), the
+    rows of a sparse matrix over a set of `npts` points in padded ELL form (`linfunctls.LinearFunctional.mixing`)."""
+
+    def __init__(self, ctx: Context, idx: np.ndarray, w: np.ndarray, npts: int):
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        w = np.ascontiguousarray(w, dtype=np.double)
+        if idx.ndim != 2 or w.shape != idx.shape:
+            raise ValueError(f"a stencil table needs indices and weights of one shape (q, S), got {idx.shape} and {w.shape}")
+        self.ctx = ctx
+        self.q, self.S = idx.shape
+        self.npts = int(npts)
+        h = C.c_void_p()
+        check(lib.lpgp_mix_create(ctx._h, self.q, self.S, idx.ctypes.data_as(C.POINTER(C.c_int32)), as_pd(w), self.npts, C.byref(h)),
+              "lpgp_mix_create")
+        self._h = h
+
+    def __del__(self):  # pragma: no cover
+        if getattr(self, "_h", None) and self.ctx._h:
+            lib.lpgp_mix_destroy(self._h)
+            self._h = None
+
+
 def _grid_factor_points(ctx: "Context", X_original, X_flat: np.ndarray):
     """Factor point sets of `X_original` if it is a `TensorProductGrid` (carries `.factors`) whose
     points, flattened in C order, are exactly `X_flat` (a sliced or reordered view is not)."""
@@ -381,6 +407,15 @@ class GramMatrix:
         check(lib.lpgp_gram_assemble_weighted(self.ctx._h, arr, len(arr), as_pd(w0), w0.shape[0], as_pd(w1) if w1 is not None else None,
                                               w1.shape[0] if w1 is not None else 0, X0._h, X1._h if X1 is not None else None, self._h, bi, bj),
               "lpgp_gram_assemble_weighted")
+
+    def assemble_mixed(self, kdesc, X0: Points, M0: "Mix | None", X1: "Points | None", M1: "Mix | None", bi: int, bj: int):
+        """Block (bi, bj) <- A0 K(X0, X1) A1^T with the rows of A0 / A1 as stencil tables (`lpgp_gram_assemble_mixed`); a side
+        without a table is plain.  For a diagonal block `X1` and `M1` are None and `M0` serves both sides.  Always entry-wise
+        from the flattened points."""
+        arr = _kdesc_array(kdesc)
+        check(lib.lpgp_gram_assemble_mixed(self.ctx._h, arr, len(arr), X0._h, M0._h if M0 is not None else None,
+                                           X1._h if X1 is not None else None, M1._h if M1 is not None else None, self._h, bi, bj),
+              "lpgp_gram_assemble_mixed")
 
     def add_diag(self, bi: int, v: np.ndarray | None = None, scalar: float = 0.0):
         if v is not None:
@@ -625,6 +660,12 @@ class Rhs:
             raise ValueError(f"weights must have shape (A, {X_obs.n}), got {w.shape}")
         check(lib.lpgp_cross_assemble_weighted(self.ctx._h, arr, len(arr), as_pd(w), w.shape[0], X_obs._h, X_test._h, self._h, self.mat._h, bi),
               "lpgp_cross_assemble_weighted")
+
+    def cross_assemble_mixed(self, kdesc, X_obs: Points, M: "Mix | None", X_test: Points, bi: int):
+        """Rows of block `bi` <- sum_a w[r][a] K(X_obs[idx[r][a]], X_test) (`lpgp_cross_assemble_mixed`); `M` None: the plain block."""
+        arr = _kdesc_array(kdesc)
+        check(lib.lpgp_cross_assemble_mixed(self.ctx._h, arr, len(arr), X_obs._h, M._h if M is not None else None, X_test._h, self._h,
+                                            self.mat._h, bi), "lpgp_cross_assemble_mixed")
 
     def cross_assemble_row(self, entries, X_test: Points):
         """All observation blocks in one call (`lpgp_cross_assemble_row`): entries = [(kdesc, X_obs)] per block, in block order."""

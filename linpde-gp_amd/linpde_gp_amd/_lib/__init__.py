@@ -113,6 +113,10 @@ def _load() -> C.CDLL:
     sig("lpgp_gram_assemble", C.c_int, vp, pk, i32, vp, vp, vp, i32, i32)
     sig("lpgp_gram_assemble_weighted", C.c_int, vp, C.POINTER(WPair), i32, pd, i32, pd, i32, vp, vp, vp, i32, i32)
     sig("lpgp_cross_assemble_weighted", C.c_int, vp, C.POINTER(WPair), i32, pd, i32, vp, vp, vp, vp, i32)
+    sig("lpgp_mix_create", C.c_int, vp, i64, i32, C.POINTER(i32), pd, i64, C.POINTER(vp))
+    sig("lpgp_mix_destroy", C.c_int, vp)
+    sig("lpgp_gram_assemble_mixed", C.c_int, vp, pk, i32, vp, vp, vp, vp, vp, i32, i32)
+    sig("lpgp_cross_assemble_mixed", C.c_int, vp, pk, i32, vp, vp, vp, vp, vp, i32)
     sig("lpgp_mat_add_diag", C.c_int, vp, vp, i32, pd, dbl)
     sig("lpgp_mat_add_dense", C.c_int, vp, vp, i32, pd)
     sig("lpgp_mat_to_host", C.c_int, vp, vp, i32, pd)
@@ -185,7 +189,8 @@ EXPORTED = [
     "lpgp_dist_grid", "lpgp_dist_stats", "lpgp_dist_link_probe", "lpgp_pts_create", "lpgp_pts_destroy", "lpgp_mat_create",
     "lpgp_mat_destroy", "lpgp_mat_add_block", "lpgp_mat_pop_block", "lpgp_mat_set_view", "lpgp_mat_num_blocks",
     "lpgp_mat_num_blocks_total", "lpgp_mat_clone", "lpgp_mat_size", "lpgp_mat_padded_size",
-    "lpgp_gram_assemble", "lpgp_gram_assemble_weighted", "lpgp_cross_assemble_weighted", "lpgp_mat_add_diag", "lpgp_mat_add_dense", "lpgp_mat_to_host", "lpgp_mat_factor_diag",
+    "lpgp_gram_assemble", "lpgp_gram_assemble_weighted", "lpgp_cross_assemble_weighted", "lpgp_mix_create", "lpgp_mix_destroy",
+    "lpgp_gram_assemble_mixed", "lpgp_cross_assemble_mixed", "lpgp_mat_add_diag", "lpgp_mat_add_dense", "lpgp_mat_to_host", "lpgp_mat_factor_diag",
     "lpgp_potrf", "lpgp_potrf_enqueue", "lpgp_mat_condition", "lpgp_mat_check", "lpgp_mat_truncate", "lpgp_potrs", "lpgp_solve_weights", "lpgp_mat_set_residual", "lpgp_rhs_create", "lpgp_rhs_destroy",
     "lpgp_cross_assemble", "lpgp_cross_assemble_row", "lpgp_predict", "lpgp_potrf_predict", "lpgp_trsm_lower", "lpgp_rhs_inner", "lpgp_rhs_matmul", "lpgp_gemm_host", "lpgp_mat_sub_inner", "lpgp_mat_factor_matmul",
     "lpgp_mat_evidence", "lpgp_mat_inverse_diag", "lpgp_mat_loo", "lpgp_mat_inverse", "lpgp_mat_evidence_grad", "lpgp_mat_evidence_grad_diag", "lpgp_mat_cv",

@@ -382,6 +382,9 @@ def condition(prior, Y, X, *, L, b, parent=None):
     if getattr(L, "_variable_coefficients", False) or (hasattr(L, "variable_terms") and L.variable_terms() is not None):
         raise NotImplementedError("variable-coefficient operators (`VariableCoefficientOperator`) are not supported through the "
                                   "`lp.spawn` multi-GPU front (single GPU only)")
+    if hasattr(L, "mixing") and L.mixing() is not None:
+        raise NotImplementedError("observations through a matrix (`A @ L`) are not supported through the `lp.spawn` multi-GPU front "
+                                  "(single GPU only)")
     X = np.asarray(X) if (X is not None and type(X).__name__ == "DeviceArray") else X
     new_id = group.new_id()
     group.request("condition", new_id, None if parent is None else parent._oid, prior if parent is None else None, Y, X, L, b)

@@ -202,10 +202,16 @@ _VARIABLE = "variable-coefficient operators (`VariableCoefficientOperator`)"
 
 
 class _ObservationBlock:
-    __slots__ = ("Y", "L", "b", "X", "coeffs", "points", "pred_mean", "vterms", "weights")
+    __slots__ = ("Y", "L", "b", "X", "coeffs", "points", "pred_mean", "vterms", "weights", "mixing", "mix", "rows")
 
-    def __init__(self, Y, L, b, X, coeffs, points, pred_mean):
+    def __init__(self, Y, L, b, X, coeffs, points, pred_mean, mixing=None):
         self.Y, self.L, self.b, self.X = Y, L, b, X
+        # observations through a matrix (`A @ L`): the rows of A as a stencil table over the points, (idx, w) on the host and
+        # resident on the device; the block then has A's rows, not one row per point
+        self.mixing, self.mix = mixing, None
+        self.rows = points.n if mixing is None else int(mixing[0].shape[0])
+        if mixing is not None:
+            self.mix = _engine.Mix(points.ctx, mixing[0], mixing[1], points.n)
         self.vterms = self.weights = None
         if isinstance(coeffs, _VariableCoeffs):
             # L = sum_a f_a D_a: the coefficient maps of the D_a and the weights f_a(X), (A, n); no single coefficient map
@@ -227,12 +233,45 @@ def _has_variable(blocks) -> bool:
     return any(ob.vterms is not None for ob in blocks)
 
 
+_MIXED = "observations through a matrix (`A @ L`)"
+
+
+def _has_mixed(blocks) -> bool:
+    return any(ob.mix is not None for ob in blocks)
+
+
+def _mix_apply(ob, Z: np.ndarray) -> np.ndarray:
+    """A @ Z for the matrix of a mixed block, Z of shape (points, m); a plain block: Z."""
+    if ob.mixing is None:
+        return Z
+    idx, w = ob.mixing
+    return np.einsum("rs,rsm->rm", w, Z[idx])
+
+
+def _mix_apply_transposed(ob, V: np.ndarray) -> np.ndarray:
+    """A^T @ V for the matrix of a mixed block, V of shape (rows, m); a plain block: V."""
+    if ob.mixing is None:
+        return V
+    idx, w = ob.mixing
+    out = np.zeros((ob.points.n, V.shape[1]))
+    np.add.at(out, idx, w[:, :, None] * V[:, None, :])
+    return out
+
+
 def _assemble_block(mat, base, bi, bj, row_block, col_block):
     """Block (bi, bj) of the Gram matrix, `col_block is row_block` for the diagonal block: the existing call for two
     constant-coefficient blocks, `lpgp_gram_assemble_weighted` (entry-wise from the flattened points, also for tensor grids: a
     weighted block is not a Kronecker product) as soon as either side has variable coefficients -- one pair (a, b) per pair
-    of terms, weight 1 / A = 1 for a constant-coefficient side."""
+    of terms, weight 1 / A = 1 for a constant-coefficient side; `lpgp_gram_assemble_mixed` as soon as either side is a matrix
+    block (`A @ L`), the other side's rows then its points."""
     sym = col_block is row_block
+    if row_block.mix is not None or col_block.mix is not None:
+        # the fused stencil kernel (`lpgp_gram_assemble_mixed`), a side without a table plain
+        if row_block.vterms is not None or col_block.vterms is not None:
+            raise NotImplementedError(f"{_MIXED} and {_VARIABLE} in one chain are not supported")
+        mat.assemble_mixed(_lowered(base, row_block.coeffs, col_block.coeffs), row_block.points, row_block.mix,
+                           None if sym else col_block.points, None if sym else col_block.mix, bi, bj)
+        return
     if row_block.vterms is None and col_block.vterms is None:
         mat.assemble(_lowered(base, row_block.coeffs, col_block.coeffs), row_block.points, None if sym else col_block.points, bi, bj)
         return
@@ -253,7 +292,7 @@ class _GramOperator:
 
     @property
     def shape(self):
-        n = sum(ob.points.n for ob in self._cgp._blocks)
+        n = sum(ob.rows for ob in self._cgp._blocks)
         return (n, n)
 
     dtype = np.dtype(np.double)
@@ -295,6 +334,8 @@ class _GramOperator:
         base = cgp._prior.cov
         tr = 0.0
         for ob in cgp._blocks:
+            if ob.mix is not None:
+                raise NotImplementedError(f"`gram.trace()` is not available on a chain with {_MIXED}")
             if ob.vterms is not None:
                 # sum_i sum_ab f_a(x_i) f_b(x_i) (D_a k D_b'^*)(x_i, x_i)
                 for a, ca in enumerate(ob.vterms):
@@ -303,7 +344,7 @@ class _GramOperator:
                 tr += float(np.sum(_noise_diag(ob)))
                 continue
             k = covfuncs.DifferentiatedCovarianceFunction(covfuncs._base(base), *_combine(base, ob.coeffs, ob.coeffs))
-            tr += ob.points.n * _engine.kernel_diag(cgp._state.ctx, k.lower())
+            tr += ob.rows * _engine.kernel_diag(cgp._state.ctx, k.lower())
             tr += float(np.sum(_noise_diag(ob)))
         return tr
 
@@ -316,10 +357,19 @@ class _GramOperator:
         V2 = V.reshape(n, -1)
         out = np.zeros_like(V2)
         base = cgp._prior.cov
-        offs = np.cumsum([0] + [ob.points.n for ob in cgp._blocks])
+        offs = np.cumsum([0] + [ob.rows for ob in cgp._blocks])
         for i, bi in enumerate(cgp._blocks):
             for j, bj in enumerate(cgp._blocks):
-                if bi.points.n == 0 or bj.points.n == 0:
+                if bi.rows == 0 or bj.rows == 0:
+                    continue
+                if bi.mix is not None or bj.mix is not None:
+                    # A_i K(X_i, X_j) (A_j^T V): the mixing on the host, the product with K matrix-free on the points
+                    if bi.vterms is not None or bj.vterms is not None:
+                        raise NotImplementedError(f"{_MIXED} and {_VARIABLE} in one chain are not supported")
+                    k = covfuncs.DifferentiatedCovarianceFunction(covfuncs._base(base), *_combine(base, bi.coeffs, bj.coeffs))
+                    KV = _engine.kernel_matvec(cgp._state.ctx, k.lower(), bi.points, bj.points,
+                                               np.ascontiguousarray(_mix_apply_transposed(bj, V2[offs[j]:offs[j + 1]])))
+                    out[offs[i]:offs[i + 1]] += _mix_apply(bi, KV)
                     continue
                 if bi.vterms is not None or bj.vterms is not None:
                     # diag(f_a) K_ab diag(g_b) V, pair by pair, the scalings on the host
@@ -337,7 +387,7 @@ class _GramOperator:
                 if bi.b.cov_diag is not None:
                     out[offs[i]:offs[i + 1]] += np.asarray(bi.b.cov_diag)[:, None] * V2[offs[i]:offs[i + 1]]
                 else:
-                    out[offs[i]:offs[i + 1]] += np.asarray(bi.b.cov).reshape(bi.points.n, bi.points.n) @ V2[offs[i]:offs[i + 1]]
+                    out[offs[i]:offs[i + 1]] += np.asarray(bi.b.cov).reshape(bi.rows, bi.rows) @ V2[offs[i]:offs[i + 1]]
         return out.reshape(V.shape)
 
 
@@ -346,7 +396,7 @@ def _noise_diag(ob) -> np.ndarray:
         return np.zeros(0)
     if ob.b.cov_diag is not None:
         return np.asarray(ob.b.cov_diag, dtype=np.double)
-    return np.diag(np.asarray(ob.b.cov).reshape(ob.points.n, ob.points.n))
+    return np.diag(np.asarray(ob.b.cov).reshape(ob.rows, ob.rows))
 
 
 class _GramInverse:
@@ -580,7 +630,7 @@ class EvidenceGradient:
 
 def _block_noise(ob):
     """(scalar, diag, dense) of the noise covariance of an observation block, as `_extend` hands it to the library."""
-    n = ob.points.n
+    n = ob.rows
     scalar, diag, dense = 0.0, None, None
     if ob.b is not None and isinstance(ob.b, randvars.Normal):
         if ob.b.cov_diag is not None:
@@ -603,6 +653,14 @@ def _refuse_variable_off_path(coeffs, ctx=None) -> None:
         raise NotImplementedError(f"{_VARIABLE} are not supported in a multi-GPU job (single GPU only)")
 
 
+def _refuse_mixed_off_path(L, ctx=None):
+    """`L.mixing()`, after refusing a mixed block in a multi-GPU context before any device work (see `_refuse_variable_off_path`)."""
+    mixing = L.mixing()
+    if mixing is not None and (ctx if ctx is not None else _engine.default_context()).distributed:
+        raise NotImplementedError(f"{_MIXED} are not supported in a multi-GPU job (single GPU only)")
+    return mixing
+
+
 _ROWS_SEEN_MAX = 4096        # (a hint only, and only where re-allocation matters: 128 MB; beyond, a copy is noise against the O(n^3) work)
 
 
@@ -614,8 +672,9 @@ class ConditionalGaussianProcess(GaussianProcess):
         #  and again -- new data, new hyperparameters' worth of right-hand sides -- and a matrix that outgrows its allocation in the
         #  middle of a chain is re-allocated and copied: eight launches of a 1 152-row problem's sixty)
         _refuse_variable_off_path(coeffs)
+        mixing = _refuse_mixed_off_path(Lf)
         state = _DeviceState(_engine.default_context(), capacity_hint=getattr(prior, "_rows_seen", 0))
-        block = _ObservationBlock(Yf, Lf, bf, Xpts, coeffs, Lf.device_points(state.ctx), pred_mean)
+        block = _ObservationBlock(Yf, Lf, bf, Xpts, coeffs, Lf.device_points(state.ctx), pred_mean, mixing)
         return cls._extend(prior, state, (), block)
 
     @classmethod
@@ -626,10 +685,11 @@ class ConditionalGaussianProcess(GaussianProcess):
         an earlier one -- takes the eager separate-call path whatever `config.lazy_factorization` says: factorisations still
         deferred are flushed and verified first, then `lpgp_mat_add_block`, one `lpgp_gram_assemble_weighted` per block of
         the row where either side is variable (the existing assembly otherwise), the noise, `lpgp_potrf`; a Gram matrix
-        that is not positive definite pops the block and raises exactly as the one-call path does."""
+        that is not positive definite pops the block and raises exactly as the one-call path does.  A chain with a matrix
+        block (`A @ L`, `lpgp_gram_assemble_mixed`) goes the same way."""
         from .. import config
 
-        if new_block.points.n == 0:
+        if new_block.rows == 0:
             # no observations: nothing to assemble or factor, the factor in HBM stays as it is (and
             # stays valid for the object this one was derived from)
             return cls(prior=prior, blocks=tuple(old_blocks), state=state, representer_weights=None)
@@ -648,10 +708,11 @@ class ConditionalGaussianProcess(GaussianProcess):
                 raise np.linalg.LinAlgError(state.failure)
             if len(state.blocks) != len(old_blocks):
                 state = _DeviceState(state.ctx, state.mat.clone(len(old_blocks)), old_blocks)
-        variable = new_block.vterms is not None or _has_variable(old_blocks)
+        mixed = new_block.mix is not None or _has_mixed(old_blocks)
+        variable = new_block.vterms is not None or _has_variable(old_blocks) or mixed      # (a chain with a matrix block goes the same way)
         if variable:
             if state.ctx.distributed:
-                raise NotImplementedError(f"{_VARIABLE} are not supported in a multi-GPU job (single GPU only)")
+                raise NotImplementedError(f"{_MIXED if mixed else _VARIABLE} are not supported in a multi-GPU job (single GPU only)")
             state.verify()
             if not state.owns(old_blocks):
                 raise np.linalg.LinAlgError(state.failure or "the Gram matrix of this posterior is not positive definite")
@@ -674,7 +735,7 @@ class ConditionalGaussianProcess(GaussianProcess):
         # called on intact, as in the reference: the library drops the new block again, the leading factor is never touched.
         row = [(_lowered(base, new_block.coeffs, ob.coeffs), ob.points) for ob in old_blocks]
         row.append((_lowered(base, new_block.coeffs, new_block.coeffs), None))
-        n = new_block.points.n
+        n = new_block.rows
         scalar, diag, dense = 0.0, None, None
         if new_block.b is not None and isinstance(new_block.b, randvars.Normal):
             if new_block.b.cov_diag is not None:
@@ -711,7 +772,7 @@ class ConditionalGaussianProcess(GaussianProcess):
         mat, base = state.mat, prior.cov
         state.invalidate()
         scalar, diag, dense = _block_noise(new_block)
-        bi = mat.add_block(new_block.points.n)
+        bi = mat.add_block(new_block.rows)
         try:
             for j, ob in enumerate(tuple(old_blocks) + (new_block,)):
                 _assemble_block(mat, base, bi, j, new_block, ob)
@@ -840,10 +901,14 @@ class ConditionalGaussianProcess(GaussianProcess):
         Yf, Lf, bf, Xpts, coeffs, pred_mean = self._preprocess_observations(
             prior=self._prior, Y=Y, X=X, L=L, b=b)
         _refuse_variable_off_path(coeffs, self._state.ctx)
-        block = _ObservationBlock(Yf, Lf, bf, Xpts, coeffs, Lf.device_points(self._state.ctx), pred_mean)
+        mixing = _refuse_mixed_off_path(Lf, self._state.ctx)
+        block = _ObservationBlock(Yf, Lf, bf, Xpts, coeffs, Lf.device_points(self._state.ctx), pred_mean, mixing)
         from .. import config
         if config.matrix_free_above and not self._state.ctx.distributed and \
-                sum(ob.points.n for ob in self._blocks) + block.points.n > int(config.matrix_free_above):
+                sum(ob.rows for ob in self._blocks) + block.rows > int(config.matrix_free_above):
+            if block.mix is not None or _has_mixed(self._blocks):
+                raise NotImplementedError(f"{_MIXED} are not supported on matrix-free posteriors (this chain has outgrown "
+                                          "`config.matrix_free_above`)")
             if block.vterms is not None or _has_variable(self._blocks):
                 raise NotImplementedError(f"{_VARIABLE} are not supported on matrix-free posteriors (this chain has outgrown "
                                           "`config.matrix_free_above`)")
@@ -853,7 +918,7 @@ class ConditionalGaussianProcess(GaussianProcess):
             from ._matrix_free import MatrixFreeConditionalGaussianProcess
             warm = None
             if self._representer_weights is not None:
-                warm = np.concatenate([np.asarray(self._representer_weights, dtype=np.double), np.zeros(block.points.n)])
+                warm = np.concatenate([np.asarray(self._representer_weights, dtype=np.double), np.zeros(block.rows)])
             return MatrixFreeConditionalGaussianProcess(self._prior, self._blocks + (block,), warm_start=warm)
         return ConditionalGaussianProcess._extend(self._prior, self._state, self._blocks, block)
 
@@ -904,11 +969,14 @@ class ConditionalGaussianProcess(GaussianProcess):
         st = self._state
         rhs = _engine.Rhs(st.ctx, st.mat, Xtest_pts.n)
         base = self._prior.cov
-        if _has_variable(self._blocks):
+        if _has_variable(self._blocks) or _has_mixed(self._blocks):
             # block by block: sum_a diag(f_a(X_obs)) (D_a k Ltest'^*)(X_obs, x) for a variable-coefficient block
-            # (`lpgp_cross_assemble_weighted`), the plain call for the others
+            # (`lpgp_cross_assemble_weighted`), A (L k Ltest'^*)(X_obs, x) by the stencil kernel for a matrix block
+            # (`lpgp_cross_assemble_mixed`), the plain call for the others
             for bi, ob in enumerate(self._blocks):
-                if ob.vterms is None:
+                if ob.mix is not None:
+                    rhs.cross_assemble_mixed(_lowered(base, ob.coeffs, self._test_coeffs), ob.points, ob.mix, Xtest_pts, bi)
+                elif ob.vterms is None:
                     rhs.cross_assemble(_lowered(base, ob.coeffs, self._test_coeffs), ob.points, Xtest_pts, bi)
                 else:
                     rhs.cross_assemble_weighted([(_lowered(base, c, self._test_coeffs), a, 0) for a, c in enumerate(ob.vterms)],
@@ -1056,7 +1124,7 @@ class ConditionalGaussianProcess(GaussianProcess):
         as `leave_one_out`."""
         if not self._blocks:
             raise ValueError("`cross_validate` needs observations: this process has been conditioned on none")
-        fold_of, lists = _normalise_folds(folds, [ob.points.n for ob in self._blocks])
+        fold_of, lists = _normalise_folds(folds, [ob.rows for ob in self._blocks])
         _evidence_context("cross_validate")
         self._check_current()
         mat = self._state.mat
@@ -1081,6 +1149,8 @@ class ConditionalGaussianProcess(GaussianProcess):
         lengthscale derivative here; use a `TensorProduct` prior), and so does a prior with a Wendland summand."""
         if _has_variable(self._blocks):
             raise NotImplementedError(f"`log_marginal_likelihood_gradient` is not available on a chain with {_VARIABLE} yet")
+        if _has_mixed(self._blocks):
+            raise NotImplementedError(f"`log_marginal_likelihood_gradient` is not available on a chain with {_MIXED} yet")
         base = self._prior.cov
         base_groups = covfuncs._base(base)._base_groups()
         G, d = len(base_groups), max(int(np.prod(self._prior.input_shape, dtype=int)), 1)
@@ -1111,7 +1181,7 @@ class ConditionalGaussianProcess(GaussianProcess):
                 for i, bi in enumerate(blocks):
                     row = [(derive(pair[i][j]), bj.points) for j, bj in enumerate(blocks[:i])]
                     row.append((derive(pair[i][i]), None))
-                    info = scratch.condition(bi.points.n, bi.points, row, noise_dense=dense if i == dense_block else None, lazy=2)
+                    info = scratch.condition(bi.rows, bi.points, row, noise_dense=dense if i == dense_block else None, lazy=2)
                     assert info == 0
                 q, t = mat.evidence_grad(ginv, scratch, r)
             finally:

@@ -358,6 +358,9 @@ class MatrixFreeConditionalGaussianProcess:
         if isinstance(coeffs, _VariableCoeffs):
             raise NotImplementedError(f"{_VARIABLE} are not supported on matrix-free posteriors (`config.matrix_free`, "
                                       "`config.matrix_free_above`); condition on the dense path")
+        if Lf.mixing() is not None:
+            raise NotImplementedError("observations through a matrix (`A @ L`) are not supported on matrix-free posteriors "
+                                      "(`config.matrix_free`, `config.matrix_free_above`); condition on the dense path")
         ctx = _engine.default_context()
         block = _ObservationBlock(Yf, Lf, bf, Xpts, coeffs, Lf.device_points(ctx), pred_mean)
         old = () if previous is None else previous._blocks
