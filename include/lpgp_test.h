@@ -63,6 +63,14 @@ int  lpgp_probe_hbm_write(lpgp_ctx* ctx, int64_t bytes, double* gbps);
  * a resident kernel timed out): the error path of lpgp_mat_check without a broken device                          */
 int  lpgp_test_force_status(lpgp_ctx* ctx, lpgp_mat* mat, int32_t value);
 
+/* Fill mode of the device pool: the library never clears a buffer it hands out ("What a buffer holds"), and this makes
+ * every result's independence of stale storage testable.  byte in 0..255: from now on every buffer the pool hands out, cached or
+ * fresh, and every (re)allocation of the persistent scratch is first filled with that byte, enqueued on the panel stream; the scratch
+ * the context holds now is filled at once.  byte == -1: off (the default); the device is waited for and every cached pool buffer is
+ * freed, so that later work starts from fresh allocations as it does without the hook.  filled (may be NULL): the buffers and
+ * bytes filled since the last call, which resets them.  Refused: a context of a multi-GPU job, any other value of byte.  */
+int  lpgp_test_pool_fill(lpgp_ctx* ctx, int32_t byte, int64_t filled[2]);
+
 /* the forward half of the single-vector solve alone, z = L^{-1} r, as lpgp_mat_evidence runs it: r_host (logical order,
  * lpgp_mat_size doubles) is staged into the padded layout with zeros in the padding rows, solved by the form the option
  * trsv_resident selects (1: the resident kernel of trsv.hip, 0: one launch per tile row, potrf.hip), and z comes back in the

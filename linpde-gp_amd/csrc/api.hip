@@ -125,6 +125,15 @@ __global__ __launch_bounds__(256) void col_reduce2_kernel(const double* __restri
   }
 }
 
+// the fill mode of the test hook (ctx->pool_fill >= 0): on the panel stream, where the reuse of a pool buffer is ordered -- a first
+// use on another stream that does not wait for the panel stream is overtaken by the fill, and shows
+static int pool_fill_buffer(lpgp_ctx* ctx, void* p, size_t bytes) {
+  LPGP_HIP(hipMemsetAsync(p, ctx->pool_fill, bytes, ctx->s_main));
+  ctx->pool_filled[0] += 1;
+  ctx->pool_filled[1] += (int64_t)bytes;
+  return 0;
+}
+
 int pool_alloc(lpgp_ctx* ctx, void** out, size_t bytes, bool* fresh) {
   int best = -1;
   for (int i = 0; i < (int)ctx->pool.size(); ++i) {
@@ -134,9 +143,15 @@ int pool_alloc(lpgp_ctx* ctx, void** out, size_t bytes, bool* fresh) {
     if (b.bytes >= bytes && b.bytes <= bytes + bytes / 2 + (64 << 10) && (best < 0 || b.bytes < ctx->pool[best].bytes)) best = i;
   }
   if (best >= 0) {
-    *out = ctx->pool[best].p;
+    const lpgp_ctx::PoolBuf taken = ctx->pool[best];
+    *out = taken.p;
     ctx->pool.erase(ctx->pool.begin() + best);
     if (fresh) *fresh = false;
+    if (ctx->pool_fill >= 0 && pool_fill_buffer(ctx, taken.p, bytes) != 0) {
+      ctx->pool.push_back(taken);              // (nobody owns it yet: back where it came from)
+      *out = nullptr;
+      return -1;
+    }
     return 0;
   }
   hipError_t e = hipMalloc(out, bytes);
@@ -151,6 +166,11 @@ int pool_alloc(lpgp_ctx* ctx, void** out, size_t bytes, bool* fresh) {
     return -1;
   }
   if (fresh) *fresh = true;
+  if (ctx->pool_fill >= 0 && pool_fill_buffer(ctx, *out, bytes) != 0) {
+    (void)hipFree(*out);
+    *out = nullptr;
+    return -1;
+  }
   return 0;
 }
 
@@ -234,6 +254,7 @@ static int ensure_tmp(lpgp_ctx* ctx, int64_t n) {
   ctx->tmp_cap = 0;
   LPGP_HIP(hipMalloc(&ctx->d_tmp, (size_t)n * sizeof(double)));
   ctx->tmp_cap = n;
+  if (ctx->pool_fill >= 0) LPGP_TRY(pool_fill_buffer(ctx, ctx->d_tmp, (size_t)n * sizeof(double)));
   return 0;
 }
 

@@ -147,6 +147,10 @@ struct lpgp_ctx : lpgp::Options {     // tuning options: options.h
   // of a multi-GB Gram matrix costs more than the factorisation of a small problem)
   struct PoolBuf { void* p; size_t bytes; };
   std::vector<PoolBuf> pool;
+  // Test hook (lpgp_test_pool_fill; never set by the product): >= 0: every buffer pool_alloc or ensure_tmp hands out is first
+  // filled with this byte, on the panel stream, so that a read of storage nobody wrote shows in the results
+  int pool_fill = -1;
+  int64_t pool_filled[2] = {0, 0};   // buffers and bytes filled since the hook last asked
   // Point sets handed over per call (the reference's calling convention: NumPy arrays) come and go with every step of a small
   // problem: their device buffers are recycled here (hipMalloc + hipFree cost ~50 us a pair, and hipFree waits for the device),
   // their uploads go through a ring of pinned slots on the panel stream -- where every kernel that reads a point set runs --

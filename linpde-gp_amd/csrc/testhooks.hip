@@ -267,6 +267,34 @@ int lpgp_test_force_status(lpgp_ctx* ctx, lpgp_mat* mat, int32_t value) {
   return 0;
 }
 
+// The fill mode of the device pool (ctx->pool_fill, api.hip pool_alloc / ensure_tmp).  byte 0..255: on, and the persistent scratch is
+// filled at once; -1: off, the device waited for and every cached pool buffer freed, so that what runs next starts from fresh
+// allocations as it does without the hook.  filled (may be NULL): buffers and bytes filled since the last call, then reset.
+int lpgp_test_pool_fill(lpgp_ctx* ctx, int32_t byte, int64_t filled[2]) {
+  LPGP_CHECK(byte >= -1 && byte <= 255, "lpgp_test_pool_fill: the fill is a byte (0..255) or -1 (off), not %d", byte);
+  LPGP_DEVICE(ctx);
+  LPGP_CHECK(!ctx->distributed(), "lpgp_test_pool_fill: single GPU only");
+  if (byte >= 0) {
+    ctx->pool_fill = byte;
+    if (ctx->d_tmp && ctx->tmp_cap > 0) {
+      LPGP_HIP(hipMemsetAsync(ctx->d_tmp, byte, (size_t)ctx->tmp_cap * sizeof(double), ctx->s_main));
+      ctx->pool_filled[0] += 1;
+      ctx->pool_filled[1] += ctx->tmp_cap * (int64_t)sizeof(double);
+    }
+  } else {
+    ctx->pool_fill = -1;
+    LPGP_HIP(hipDeviceSynchronize());
+    for (auto& b : ctx->pool) (void)hipFree(b.p);
+    ctx->pool.clear();
+  }
+  if (filled) {
+    filled[0] = ctx->pool_filled[0];
+    filled[1] = ctx->pool_filled[1];
+  }
+  ctx->pool_filled[0] = ctx->pool_filled[1] = 0;
+  return 0;
+}
+
 // the refusals the hooks on a factor share: single GPU, fully factored, status read
 #define LPGP_TEST_FACTORED(ctx, mat, who)                                                                                          \
   do {                                                                                                                             \

@@ -4,6 +4,7 @@ distributed tile enumeration.  TEST INFRASTRUCTURE -- the product package never 
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -19,7 +20,7 @@ HOOKS_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "liblpgp_testhooks.so"
 EXPORTED = ["lpgp_test_stair_enumerate", "lpgp_test_gemm", "lpgp_test_gemm_cyc", "lpgp_test_potrf_tile", "lpgp_test_tile_step", "lpgp_test_panel_solve",
             "lpgp_debug_tile_xcc", "lpgp_probe_mfma_f64", "lpgp_probe_hbm_write", "lpgp_test_force_status", "lpgp_test_solve_vec_fwd", "lpgp_test_solve_vec_bwd",
             "lpgp_test_trsm_lower_t", "lpgp_test_mat_raw", "lpgp_test_factor_matmul", "lpgp_test_evidence", "lpgp_test_loo", "lpgp_test_evidence_grad",
-            "lpgp_test_evidence_grad_diag"]
+            "lpgp_test_evidence_grad_diag", "lpgp_test_pool_fill"]
 
 
 def _load() -> C.CDLL:
@@ -53,6 +54,7 @@ def _load() -> C.CDLL:
     sig("lpgp_test_loo", C.c_int, vp, vp, pd, pd, i32, pd, pd, pd)
     sig("lpgp_test_evidence_grad", C.c_int, vp, vp, vp, vp, pd, i32, pd)
     sig("lpgp_test_evidence_grad_diag", C.c_int, vp, vp, vp, i32, pd, dbl, pd, i32, pd)
+    sig("lpgp_test_pool_fill", C.c_int, vp, i32, C.POINTER(i64))
     return lib
 
 
@@ -189,6 +191,25 @@ def trsm_lower_t(ctx: Context, mat, V: np.ndarray) -> np.ndarray:
 def force_status(ctx: Context, mat, value: int) -> None:
     """Leave the status word of `mat` (a `_engine.GramMatrix`) as an enqueued factorisation ending with `value` would."""
     check(lib.lpgp_test_force_status(ctx._h, mat._h, int(value)), "lpgp_test_force_status")
+
+
+def set_pool_fill(ctx: Context, byte: int) -> "tuple[int, int]":
+    """`lpgp_test_pool_fill`: byte 0..255 switches the fill mode of the device pool on (every buffer handed out is first filled with
+    that byte on the panel stream), -1 off (and frees the cached buffers).  Returns (buffers, bytes) filled since the last call."""
+    filled = (C.c_int64 * 2)(0, 0)
+    check(lib.lpgp_test_pool_fill(ctx._h, int(byte), filled), "lpgp_test_pool_fill")
+    return int(filled[0]), int(filled[1])
+
+
+@contextlib.contextmanager
+def pool_fill(ctx: Context, byte: int):
+    """The fill mode on with `byte` inside the block, always off behind it.  Yields take(): the (buffers, bytes) filled since the
+    last take (or since the mode went on)."""
+    set_pool_fill(ctx, byte)
+    try:
+        yield lambda: set_pool_fill(ctx, byte)
+    finally:
+        set_pool_fill(ctx, -1)
 
 
 def mat_raw(ctx: Context, mat, values: np.ndarray | None = None) -> np.ndarray:

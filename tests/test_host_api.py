@@ -51,6 +51,18 @@ def test_product_library_exports_no_test_hooks():
                 assert "import scipy" not in text and "testhooks" not in text and "import oracle" not in text and "from oracle" not in text, os.path.join(dirpath, f)
 
 
+def test_pool_fill_hook_refuses_what_is_no_byte_and_a_null_context():
+    """`lpgp_test_pool_fill` (the fill mode of the device pool, tests/test_gpu_stale_storage.py): the value is checked before the
+    context is touched, so both refusals show without a GPU."""
+    import _hooks
+    for byte in (-2, 256, 1 << 20):
+        with pytest.raises(_lib.LpgpError, match="byte"):
+            _lib.check(_hooks.lib.lpgp_test_pool_fill(None, byte, None), "lpgp_test_pool_fill")
+    for byte in (-1, 0, 255):
+        with pytest.raises(_lib.LpgpError, match="null context"):
+            _lib.check(_hooks.lib.lpgp_test_pool_fill(None, byte, None), "lpgp_test_pool_fill")
+
+
 def test_multi_index_and_coefficients_algebra():
     mi = diffops.MultiIndex((1, 2, 0))
     assert mi.order == 3 and mi.is_mixed and mi == diffops.MultiIndex([1, 2, 0]) and hash(mi) == hash(diffops.MultiIndex([1, 2, 0]))
